@@ -373,13 +373,32 @@ def time_variant(variant, args, dev, steps=3, warmup=2, frames=None, accum=1, ba
     return out
 
 
+DUMP_SAMPLE = 2_000_000          # parameters sampled per array: 8 MB each in fp32
+
+
+def dump_outputs(out_dir, losses, model, optimizer):
+    """What the timed path computed in its last step, as DIR/<name>.npy: the loss dict train_step returned (one fp32 scalar per loss)
+    and the state the step left, the bf16 parameters and the fp32 masters, at DUMP_SAMPLE positions drawn with a fixed seed
+    (the same positions in every run of the same configuration). Called right after the timed region, before anything else runs."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, f"loss_{k}.npy"), np.asarray(float(v.detach()) if torch.is_tensor(v) else float(v), dtype=np.float32))
+    flat = model.arena.flat
+    n = flat.numel()
+    idx = np.unique(np.random.default_rng(0).integers(0, n, size=min(DUMP_SAMPLE, n)))
+    idx_d = torch.from_numpy(idx).to(flat.device)
+    np.save(os.path.join(out_dir, "param_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "param_sample.npy"), flat[idx_d].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "master_sample.npy"), optimizer.master[idx_d].float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs of this node. Without a launcher (no WORLD_SIZE in the environment) "
                     "N > 1 re-executes this script under torch.distributed.run with N ranks")
     ap.add_argument("--sim-world", type=int, default=8, help="also time the contrastive block at the global batch of this many ranks "
                     "(single-GPU runs only; 0 = off)")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (ms_per_step = their wall time / steps)")
     ap.add_argument("--warmup", type=int, default=5, help="untimed steps (the first ones allocate: static K|V buffers, the caching allocator's pools)")
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch (config: 512 global / 8 GPUs)")
     ap.add_argument("--frames", type=int, default=8)
@@ -401,7 +420,11 @@ def main():
                          "(VideoSwin-B + BERT text); large: BASELINE configs[3]/[4] (VideoSwin-L embed 192 / 2-2-18-2 + BERT-large "
                          "24 x 1024, the reference classes at large hyper-parameters; --frames 16 for configs[4]); clip_large: the "
                          "reference's shipped config/pretrain-VALOR-large.json (CLIP ViT-L/14 at 224 px + shared BERT-base, task prompt)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as "
+                    "DIR/<name>.npy (rank 0): its losses and a fixed sample of the updated parameters (bf16 weights and fp32 masters)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         # no launcher: become one. One process per GPU, rendezvous on the loopback address (the container hostname may not resolve).
@@ -520,6 +543,8 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     trace, engine.trace = engine.trace, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model, engine.optimizer)
     # what the host did per optimizer step: launch_ms = time inside train_step minus the `max_ahead` throttle wait (pure issue time),
     # wait_ms = the throttle wait (the host was AHEAD of the device); and what the device saw: gpu_span_ms = first launch -> last
     # launch of a step on the step's stream, gpu_idle_ms = the gap between a step's last kernel and the next step's first one (> 0 only

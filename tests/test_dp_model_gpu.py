@@ -22,6 +22,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 TASK = "pt_contra%tva%tv%ta_caption%tva%tv%ta_mlm%tva"
 B_LOCAL, FRAMES, SLICES = 2, 2, 1
+RANKS_PER_GPU = 4          # rank processes sharing one device at most (rank r runs on GPU r % device_count; the test process holds GPU 0 too)
+
+
+def _skip_unless_gpus_for(world):
+    """decided before any work: `world` ranks at RANKS_PER_GPU per device need this many GPUs"""
+    need, have = -(-world // RANKS_PER_GPU), torch.cuda.device_count()
+    if have < need:
+        pytest.skip(f"{world} ranks need {need} GPUs ({RANKS_PER_GPU} ranks per GPU), found {have}")
 
 
 def _setup(world=2):
@@ -50,8 +58,9 @@ def _worker(rank, world, port, outdir):
         spec, sd, full = _setup(world)
         from valor_amd.engine import TrainEngine
         from valor_amd.model.valor import VALOR
-        torch.cuda.set_device(0)
-        model = VALOR({"dropout": 0.0}, spec=spec, dtype=torch.float32, device="cuda:0")
+        device = torch.device("cuda", rank % torch.cuda.device_count())
+        torch.cuda.set_device(device)
+        model = VALOR({"dropout": 0.0}, spec=spec, dtype=torch.float32, device=device)
         if rank == 0:
             model.load_state_dict(sd, strict=True)          # rank 1 starts from zeros: TrainEngine's broadcast must fix that
         opts = SimpleNamespace(learning_rate=1e-3, weight_decay=0.01, clip_lr=1e-3, clip_lr_text=1e-3, new_lr=0.0, decoder_lr=-1,
@@ -89,7 +98,8 @@ def _worker(rank, world, port, outdir):
 
 @pytest.mark.parametrize("W", [2, 4, 8])
 def test_ranks_match_the_reference_semantics(dev, tmp_path, W):
-    """world 2 / 4 / 8 (every rank a process on the one GPU of the test box, gloo): nothing above world 2 had ever executed before round 4"""
+    """world 2 / 4 / 8 (every rank a process, RANKS_PER_GPU of them per GPU, gloo): nothing above world 2 had ever executed before round 4"""
+    _skip_unless_gpus_for(W)
     spec, sd, full = _setup(W)
     import valor_oracle as VO
     from valor_amd import synth
@@ -297,9 +307,11 @@ def test_bench_gpus_flag_launches_that_many_ranks():
 
 
 def test_bench_with_eight_ranks_on_one_gpu():
-    """the driver's 8-GPU command line (`bench.py --gpus 8`) with the eight ranks sharing this box's one GPU over gloo, at a batch that
-    fits eight replicas: eight ranks really run, the losses are finite and every replica holds bit-identical parameters after the
-    timed steps (the line's `replicas_identical` = an all-gathered checksum of the parameter arena)"""
+    """the driver's 8-GPU command line (`bench.py --gpus 8`) with the eight ranks sharing the node's GPUs over gloo (bench.py puts rank r
+    on GPU r % device_count, RANKS_PER_GPU per device at most), at a batch that fits eight replicas: eight ranks really run, the losses
+    are finite and every replica holds bit-identical parameters after the timed steps (the line's `replicas_identical` = an
+    all-gathered checksum of the parameter arena)"""
+    _skip_unless_gpus_for(8)
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
