@@ -377,6 +377,17 @@ int valor_adamw_set_nt(int v);
 int valor_adamw(void* stream, int dtype, float* master, float* exp_avg, float* exp_avg_sq, void* grad, void* param,
                 const int8_t* chunk_group, int64_t n, const float* lr, const float* wd, int ngroups, float beta1,
                 float beta2, float eps, int step, int correct_bias, const float* gscale_dev, int zero_grad);
+/* valor_adamw with the Adam step count on the device: tensor_step int32 [ntensors] (the count of each tensor before this step),
+ * chunk_tensor int32 [n/chunk] (tensor of each chunk; a tensor's chunks are consecutive), chunk_bc fp32 scratch [2*n/chunk]. The
+ * bias correction of every chunk uses its tensor's count + 1; afterwards the count of every active tensor advances by one, unless
+ * the step was skipped (non-finite *gscale_dev). Three launches, no host sync. */
+int valor_adamw_counted(void* stream, int dtype, float* master, float* exp_avg, float* exp_avg_sq, void* grad, void* param,
+                        const int8_t* chunk_group, const int32_t* chunk_tensor, int32_t* tensor_step, int ntensors, float* chunk_bc,
+                        int64_t n, const float* lr, const float* wd, int ngroups, float beta1, float beta2, float eps,
+                        int correct_bias, const float* gscale_dev, int zero_grad);
+/* total_norm = sqrt(sum of squares of the active chunks) * norm_mul; gscale = norm_mul * min(1, max_norm / (total_norm + 1e-6)),
+ * max_norm <= 0: no clipping; gscale = NaN if total_norm is not finite (valor_adamw* then skip the update and only clear the
+ * gradients). partial: fp32 scratch >= 1024 floats. */
 int valor_grad_norm_clip(void* stream, int dtype, const void* grad, const int8_t* chunk_group, int64_t n, float norm_mul,
                          float max_norm, float* partial, float* total_norm, float* gscale);
 

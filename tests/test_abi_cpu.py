@@ -68,6 +68,40 @@ def test_argument_validation_without_gpu():
     assert so.valor_cross_attn_bwd_fused(None, 0, None, 3, buf, buf, buf, buf, 1, 128, 1, 0, 64, 0, 64, 0, 64, 0, 64, 0.125, 0.0, None) == -1
 
 
+def test_adamw_argument_validation_without_gpu():
+    """valor_adamw / valor_adamw_counted / valor_grad_norm_clip refuse bad sizes and group counts before any launch; n = 0 is a no-op"""
+    from valor_amd import lib
+    so = lib.load()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.addressof(buf)
+    lr = (ctypes.c_float * 17)(*([1e-3] * 17))
+    wd = (ctypes.c_float * 17)(*([0.0] * 17))
+
+    def adamw(n, ngroups, dtype=0):
+        return so.valor_adamw(None, dtype, p, p, p, p, p, p, n, lr, wd, ngroups, 0.9, 0.98, 1e-6, 1, 1, None, 1)
+
+    def counted(n, ngroups, dtype=0, ntensors=1, chunk_bc=p):
+        return so.valor_adamw_counted(None, dtype, p, p, p, p, p, p, p, p, ntensors, chunk_bc, n, lr, wd, ngroups, 0.9, 0.98, 1e-6, 1, None, 1)
+
+    for f in (adamw, counted):
+        assert f(1000, 10) == -1 and f(2048 + 1, 10) == -1            # n % 1024 != 0
+        assert f(2048, 0) == -1 and f(2048, 17) == -1                 # ngroups outside 1..16
+        assert f(2048, 10, dtype=7) == -1                             # unknown dtype
+        assert f(0, 10) == 0 and f(0, 0) == 0                         # nothing to update: no-op
+    assert counted(2048, 10, ntensors=0) == -1 and counted(2048, 10, chunk_bc=None) == -1
+    assert so.valor_grad_norm_clip(None, 0, p, p, 1000, 1.0, 5.0, p, p, p) == -1
+    assert so.valor_grad_norm_clip(None, 0, p, p, 0, 1.0, 5.0, p, p, p) == -1
+
+
+def test_engine_refuses_grad_norm_the_fused_clip_would_misread():
+    """the reference clips unless grad_norm == -1; the fused clip treats max_norm <= 0 as "off", so 0 / negative values are refused"""
+    from types import SimpleNamespace
+    from valor_amd.engine import TrainEngine
+    for bad in (0.0, -2.0, -0.5):
+        with pytest.raises(ValueError, match="grad_norm"):
+            TrainEngine(None, SimpleNamespace(grad_norm=bad))
+
+
 def test_per_call_gemm_policy_without_touching_process_state():
     """valor_gemm_policy (include/valor_hip.h): the kernel-family choice of ONE call, -1 = the process default. The family query is host
     logic, so the contract is checkable without a GPU: a policy changes the answer for its call only, the process defaults stay."""

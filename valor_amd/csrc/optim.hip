@@ -29,7 +29,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void adamw_kernel(float* master, float* m, float* v, T* grad, T* param,
                                                     const int8_t* chunk_group, int64_t nchunks, AdamGroups groups,
                                                     float beta1, float beta2, float eps, float bc1, float bc2_sqrt,
-                                                    const float* gscale_dev, int zero_grad, int nt) {
+                                                    const f32x2_t* chunk_bc, const float* gscale_dev, int zero_grad, int nt) {
     const float gs = gscale_dev ? *gscale_dev : 1.0f;
     // a non-finite global gradient norm (clip_finalize_kernel hands over gscale = NaN then) skips the whole update, the gradients are
     // still cleared: what apex amp's dynamic loss scaler did for the reference on overflow (apex/amp/scaler.py:197-217), without a
@@ -64,7 +64,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* master, float* m, flo
                 continue;
             }
             const float lr = groups.lr[gid[u]], wd = groups.wd[gid[u]];
-            const float step_size = lr * bc2_sqrt / bc1;
+            // chunk_bc: per-chunk (bc1, bc2_sqrt) of the chunk's tensor (valor_adamw_counted), else the scalars of the call
+            const f32x2_t bc = chunk_bc ? chunk_bc[cc[u]] : (f32x2_t){bc1, bc2_sqrt};
+            const float step_size = lr * bc[1] / bc[0];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float gk = g[u][k] * gs;
@@ -162,6 +164,19 @@ static int g_adamw_nt = [] { const char* e = getenv("VALOR_ADAMW_NT"); return e 
 // non-temporal state accesses of the update kernel (bit 0 loads, bit 1 stores); returns the previous value, v < 0 only queries
 extern "C" int valor_adamw_set_nt(int v) { const int o = g_adamw_nt; if (v >= 0) g_adamw_nt = v; return o; }
 
+static int adamw_launch(hipStream_t st, int dtype, float* master, float* exp_avg, float* exp_avg_sq, void* grad, void* param,
+                        const int8_t* chunk_group, int64_t nchunks, const float* lr, const float* wd, int ngroups, float beta1, float beta2,
+                        float eps, float bc1, float bc2s, const f32x2_t* chunk_bc, const float* gscale_dev, int zero_grad) {
+    AdamGroups g;
+    for (int i = 0; i < ADAMW_MAX_GROUPS; ++i) { g.lr[i] = i < ngroups ? lr[i] : 0.f; g.wd[i] = i < ngroups ? wd[i] : 0.f; }
+    int blocks = (int)(nchunks < 8192 ? nchunks : 8192);
+    if (dtype == VALOR_DT_BF16)
+        hipLaunchKernelGGL((adamw_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (bf16_t*)grad, (bf16_t*)param, chunk_group, nchunks, g, beta1, beta2, eps, bc1, bc2s, chunk_bc, gscale_dev, zero_grad, g_adamw_nt);
+    else
+        hipLaunchKernelGGL((adamw_kernel<float>), dim3(blocks), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (float*)grad, (float*)param, chunk_group, nchunks, g, beta1, beta2, eps, bc1, bc2s, chunk_bc, gscale_dev, zero_grad, g_adamw_nt);
+    return valor_launch_status();
+}
+
 // n must be a multiple of valor_adamw_chunk(); chunk_group: int8 [n / chunk] (-1 = inactive).
 // lr / wd: host arrays of ngroups floats. step = 1-based Adam step of the active tensors.
 extern "C" int valor_adamw(void* stream, int dtype, float* master, float* exp_avg, float* exp_avg_sq, void* grad,
@@ -171,21 +186,68 @@ extern "C" int valor_adamw(void* stream, int dtype, float* master, float* exp_av
     if (n <= 0) return VALOR_OK;
     if ((n % ADAMW_CHUNK) || ngroups <= 0 || ngroups > ADAMW_MAX_GROUPS || !master || !exp_avg || !exp_avg_sq || !grad || !chunk_group)
         return VALOR_ERR_ARG;
-    AdamGroups g;
-    for (int i = 0; i < ADAMW_MAX_GROUPS; ++i) { g.lr[i] = i < ngroups ? lr[i] : 0.f; g.wd[i] = i < ngroups ? wd[i] : 0.f; }
+    if (dtype != VALOR_DT_BF16 && dtype != VALOR_DT_F32) return VALOR_ERR_ARG;
     float bc1 = 1.f, bc2s = 1.f;
     if (correct_bias) {
         bc1 = (float)(1.0 - pow((double)beta1, (double)step));
         bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     }
+    return adamw_launch((hipStream_t)stream, dtype, master, exp_avg, exp_avg_sq, grad, param, chunk_group, n / ADAMW_CHUNK, lr, wd, ngroups,
+                        beta1, beta2, eps, bc1, bc2s, nullptr, gscale_dev, zero_grad);
+}
+
+// valor_adamw_counted: the Adam step count lives on the device, one int32 per tensor. (bc1, bc2_sqrt) of each chunk's tensor at step
+// count + 1, in double exactly like valor_adamw's host code -- one thread per chunk, so the update kernel reads its chunk's pair next to its
+// group byte instead of behind a second table lookup.
+__global__ __launch_bounds__(256) void adamw_bc_kernel(const int32_t* chunk_tensor, const int32_t* tensor_step, int ntensors, int64_t nchunks,
+                                                       float beta1, float beta2, int correct_bias, f32x2_t* chunk_bc) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nchunks) return;
+    const int t = chunk_tensor[c];
+    float bc1 = 1.f, bc2s = 1.f;
+    if (correct_bias && t >= 0 && t < ntensors) {
+        const double s = (double)tensor_step[t] + 1.0;
+        bc1 = (float)(1.0 - pow((double)beta1, s));
+        bc2s = (float)sqrt(1.0 - pow((double)beta2, s));
+    }
+    chunk_bc[c] = (f32x2_t){bc1, bc2s};
+}
+
+// after the update: the first chunk of every active tensor advances its count, unless the step was skipped (non-finite gscale). A skipped
+// step leaves the count where it was: apex amp's skip_step replaced optimizer.step for the reference, so AdamW's state['step'] += 1 never ran.
+__global__ __launch_bounds__(256) void adamw_count_kernel(const int8_t* chunk_group, const int32_t* chunk_tensor, int32_t* tensor_step,
+                                                          int ntensors, int64_t nchunks, const float* gscale_dev) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nchunks) return;
+    if (gscale_dev && !(fabsf(*gscale_dev) < INFINITY)) return;
+    const int t = chunk_tensor[c];
+    if (chunk_group[c] < 0 || t < 0 || t >= ntensors || (c > 0 && chunk_tensor[c - 1] == t)) return;
+    tensor_step[t] += 1;
+}
+
+// chunk_tensor: int32 [n / chunk], the tensor of each chunk (a tensor's chunks are consecutive; -1 = none); tensor_step: int32 [ntensors]
+// device counts, read for the bias correction and advanced for the active tensors of a step that was not skipped; chunk_bc: fp32 scratch
+// [2 * n / chunk]. The rest as valor_adamw.
+extern "C" int valor_adamw_counted(void* stream, int dtype, float* master, float* exp_avg, float* exp_avg_sq, void* grad, void* param,
+                                   const int8_t* chunk_group, const int32_t* chunk_tensor, int32_t* tensor_step, int ntensors,
+                                   float* chunk_bc, int64_t n, const float* lr, const float* wd, int ngroups, float beta1, float beta2,
+                                   float eps, int correct_bias, const float* gscale_dev, int zero_grad) {
+    if (n <= 0) return VALOR_OK;
+    if ((n % ADAMW_CHUNK) || ngroups <= 0 || ngroups > ADAMW_MAX_GROUPS || !master || !exp_avg || !exp_avg_sq || !grad || !chunk_group
+        || !chunk_tensor || !tensor_step || ntensors <= 0 || !chunk_bc)
+        return VALOR_ERR_ARG;
+    if (dtype != VALOR_DT_BF16 && dtype != VALOR_DT_F32) return VALOR_ERR_ARG;
     const int64_t nchunks = n / ADAMW_CHUNK;
-    int blocks = (int)(nchunks < 8192 ? nchunks : 8192);
+    const int tb = (int)((nchunks + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == VALOR_DT_BF16)
-        hipLaunchKernelGGL((adamw_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (bf16_t*)grad, (bf16_t*)param, chunk_group, nchunks, g, beta1, beta2, eps, bc1, bc2s, gscale_dev, zero_grad, g_adamw_nt);
-    else if (dtype == VALOR_DT_F32)
-        hipLaunchKernelGGL((adamw_kernel<float>), dim3(blocks), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (float*)grad, (float*)param, chunk_group, nchunks, g, beta1, beta2, eps, bc1, bc2s, gscale_dev, zero_grad, g_adamw_nt);
-    else return VALOR_ERR_ARG;
+    hipLaunchKernelGGL(adamw_bc_kernel, dim3(tb), dim3(256), 0, st, chunk_tensor, tensor_step, ntensors, nchunks, beta1, beta2, correct_bias,
+                       (f32x2_t*)chunk_bc);
+    int rc = valor_launch_status();
+    if (rc != VALOR_OK) return rc;
+    rc = adamw_launch(st, dtype, master, exp_avg, exp_avg_sq, grad, param, chunk_group, nchunks, lr, wd, ngroups, beta1, beta2, eps, 1.f, 1.f,
+                      (const f32x2_t*)chunk_bc, gscale_dev, zero_grad);
+    if (rc != VALOR_OK) return rc;
+    hipLaunchKernelGGL(adamw_count_kernel, dim3(tb), dim3(256), 0, st, chunk_group, chunk_tensor, tensor_step, ntensors, nchunks, gscale_dev);
     return valor_launch_status();
 }
 

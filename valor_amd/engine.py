@@ -14,6 +14,11 @@ from .optim import FusedAdamW, get_lr_sched
 
 class TrainEngine:
     def __init__(self, model, opts, optimizer=None, manage_gc=True, graphs=None):
+        # the reference clips unless grad_norm == -1 (train_utils.py:358): 0 would clip every gradient to zero, a negative value flip
+        # its sign -- the fused clip treats any max_norm <= 0 as "off", so such values are refused here instead of silently meaning -1
+        grad_norm = float(getattr(opts, "grad_norm", 5.0))
+        if not (grad_norm == -1.0 or grad_norm > 0.0):
+            raise ValueError(f"grad_norm must be -1 (no clipping) or > 0, got {grad_norm}")
         self.model, self.opts = model, opts
         # graphs: replay the encoders as hipGraphs (valor_amd/graphs.py) -- the CLIP ViT or the VideoSwin encoder (stochastic-depth factors
         # as a graph input), the AST encoder and the CLIP text tower; the decoder (data-dependent masked-row counts) and the shared-BERT text
@@ -63,7 +68,7 @@ class TrainEngine:
         import os
         self.alloc_headroom_mb = int(os.environ.get("VALOR_ALLOC_HEADROOM_MB", getattr(opts, "alloc_headroom_mb", 1536)))
         self._headroom_done = False
-        self.grad_norm = float(getattr(opts, "grad_norm", 5.0))
+        self.grad_norm = grad_norm
         self._task = None
         self._micro = 0
         # VALOR_DP_CHECK=1 (debug): every rank must have seen the same task sequence in an accumulation window -- the closing micro-step's

@@ -114,6 +114,8 @@ SIGNATURES = {
     "valor_adamw_chunk": [],
     "valor_adamw_set_nt": [_i],
     "valor_adamw": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _c.POINTER(_f), _c.POINTER(_f), _i, _f, _f, _f, _i, _i, _vp, _i],
+    "valor_adamw_counted": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _c.POINTER(_f), _c.POINTER(_f), _i, _f, _f, _f,
+                            _i, _vp, _i],
     "valor_grad_norm_clip": [_vp, _i, _vp, _vp, _i64, _f, _f, _vp, _vp, _vp],
     "valor_patchify": [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i64],
     "valor_assemble_tokens_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i],

@@ -71,7 +71,14 @@ class FusedAdamW:
         self.master = a.flat.float() if self.separate_master else a.flat      # fp32 parity mode: params ARE the masters
         self.exp_avg = torch.zeros(a.numel, **f32)
         self.exp_avg_sq = torch.zeros(a.numel, **f32)
-        self.steps = {n: 0 for n in a.offsets}                # per-parameter Adam step (adamw.py:62-72)
+        # per-tensor Adam step (adamw.py:62-72) on the device: valor_adamw_counted advances it only for a step that was not skipped, which
+        # only the device knows (a non-finite gradient norm) -- `steps` reads it back
+        self._count = torch.zeros(len(a.offsets), dtype=torch.int32, device=a.device)
+        ct = torch.full((a.numel // a.chunk,), -1, dtype=torch.int32)
+        for i, (o, n, _) in enumerate(a.offsets.values()):
+            ct[o // a.chunk:(o + n + a.chunk - 1) // a.chunk] = i
+        self._chunk_tensor = ct.to(a.device)
+        self._chunk_bc = torch.empty(2 * (a.numel // a.chunk), **f32)     # per-chunk bias corrections of one step (scratch)
         self.total_norm = torch.zeros((), **f32)
         self.gscale = torch.ones((), **f32)
         self._tables = {}
@@ -79,6 +86,17 @@ class FusedAdamW:
         if not hasattr(model, "_optimizers"):
             model._optimizers = []
         model._optimizers.append(weakref.ref(self))
+
+    @property
+    def steps(self):
+        """name -> Adam step count of every arena tensor (a copy read from the device: synchronises with the stream)"""
+        return dict(zip(self.arena.offsets, self._count.tolist()))
+
+    @steps.setter
+    def steps(self, counts):
+        cur = self.steps
+        cur.update({n: int(c) for n, c in counts.items()})
+        self._count.copy_(torch.tensor([cur[n] for n in self.arena.offsets], dtype=torch.int32))
 
     def sync_master(self):
         """Re-derive the fp32 masters from the current parameters (bf16 mode) -- element by element, and ONLY where a master no longer
@@ -135,21 +153,17 @@ class FusedAdamW:
         ws = workspace(a.device)
         lib.call("valor_grad_norm_clip", _stream(), dt, _ptr(a.grad), _ptr(table), a.numel, 1.0 / world_size,
                  float(max_grad_norm), _ptr(ws), _ptr(self.total_norm), _ptr(self.gscale))
-        for n in names:
-            self.steps[n] += 1
-        by_step = {}
-        for n in names:
-            by_step.setdefault(self.steps[n], []).append(n)
         lr = (ctypes.c_float * self.N_GROUPS)(*[g["lr"] for g in self.param_groups])
         wd = (ctypes.c_float * self.N_GROUPS)(*[g["weight_decay"] for g in self.param_groups])
         # (Running the update of everything behind the video tower on the side stream, under the next step's video encoder, was measured:
         #  534.95 / 533.70 vs 534.18 / 534.45 samples/s -- no gain, the HBM-bound update and the encoder's GEMMs share the memory system;
         #  one launch on the step's stream it stays. profiles/r03_step_ab_s7_adamw_split.txt)
-        for st, ns in by_step.items():
-            tb = table if len(by_step) == 1 else self._table(ns)
-            lib.call("valor_adamw", _stream(), dt, _ptr(self.master), _ptr(self.exp_avg), _ptr(self.exp_avg_sq), _ptr(a.grad),
-                     _ptr(a.flat) if self.separate_master else None, _ptr(tb), a.numel, lr, wd, self.N_GROUPS,
-                     self.betas[0], self.betas[1], self.eps, int(st), int(self.correct_bias), _ptr(self.gscale), 1)
+        # each tensor's bias correction from its own device count (tensors at different steps share the launch); the counts of the
+        # active tensors advance unless the norm was not finite and the step was skipped
+        lib.call("valor_adamw_counted", _stream(), dt, _ptr(self.master), _ptr(self.exp_avg), _ptr(self.exp_avg_sq), _ptr(a.grad),
+                 _ptr(a.flat) if self.separate_master else None, _ptr(table), _ptr(self._chunk_tensor), _ptr(self._count), self._count.numel(),
+                 _ptr(self._chunk_bc), a.numel, lr, wd, self.N_GROUPS, self.betas[0], self.betas[1], self.eps, int(self.correct_bias),
+                 _ptr(self.gscale), 1)
         return self.total_norm
 
     # ---- the reference's optimizer checkpoint (optimizer_step_N.pt: utils/save.py:57-64 saves torch's Optimizer.state_dict() of the
@@ -188,6 +202,7 @@ class FusedAdamW:
         optimizer.load_state_dict (and by load_reference_state_dict below)."""
         groups = self.reference_param_groups()
         sl = self._ref_slices()
+        steps = self.steps
         state, pgs, idx = {}, [], 0
         for gi, names in enumerate(groups):
             g = self.param_groups[gi]
@@ -195,8 +210,8 @@ class FusedAdamW:
                         "correct_bias": self.correct_bias, "params": list(range(idx, idx + len(names)))})
             for r in names:
                 o, n, shape, owner = sl[r]
-                if self.steps[owner] > 0:
-                    state[idx] = {"step": self.steps[owner], "exp_avg": self.exp_avg[o:o + n].view(shape).clone().cpu(),
+                if steps[owner] > 0:
+                    state[idx] = {"step": steps[owner], "exp_avg": self.exp_avg[o:o + n].view(shape).clone().cpu(),
                                   "exp_avg_sq": self.exp_avg_sq[o:o + n].view(shape).clone().cpu()}
                 idx += 1
         return {"state": state, "param_groups": pgs}
@@ -211,11 +226,13 @@ class FusedAdamW:
             "optimizer checkpoint does not match this model's parameter groups"
         for names, g in zip(groups, sd["param_groups"]):
             assert len(names) == len(g["params"])
+        steps = {}
         for idx, st in sd["state"].items():
             o, n, shape, owner = sl[order[int(idx)]]
-            self.steps[owner] = int(st["step"])
+            steps[owner] = int(st["step"])
             self.exp_avg[o:o + n].copy_(st["exp_avg"].reshape(-1))
             self.exp_avg_sq[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+        self.steps = steps
         for g, s_ in zip(self.param_groups, sd["param_groups"]):
             g.update({k: s_[k] for k in ("init_lr", "lr", "weight_decay") if k in s_})
         self.sync_master()          # the reference's checkpoint carries no fp32 masters: re-derive them from the loaded parameters
@@ -223,9 +240,10 @@ class FusedAdamW:
     # ---- compact native layout (one entry per arena tensor)
     def state_dict(self):
         state = {}
+        steps = self.steps
         for i, (name, (o, n, shape)) in enumerate(self.arena.offsets.items()):
-            if self.steps[name] > 0:
-                state[i] = {"step": self.steps[name], "exp_avg": self.exp_avg[o:o + n].view(shape).clone(),
+            if steps[name] > 0:
+                state[i] = {"step": steps[name], "exp_avg": self.exp_avg[o:o + n].view(shape).clone(),
                             "exp_avg_sq": self.exp_avg_sq[o:o + n].view(shape).clone()}
         out = {"state": state, "param_groups": [dict(g) for g in self.param_groups], "names": list(self.arena.offsets)}
         if self.separate_master:
@@ -234,12 +252,14 @@ class FusedAdamW:
 
     def load_state_dict(self, sd):
         names = sd.get("names", list(self.arena.offsets))
+        steps = {}
         for i, st in sd["state"].items():
             name = names[int(i)]
             o, n, _ = self.arena.offsets[name]
-            self.steps[name] = int(st["step"])
+            steps[name] = int(st["step"])
             self.exp_avg[o:o + n].copy_(st["exp_avg"].reshape(-1))
             self.exp_avg_sq[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
+        self.steps = steps
         for g, s in zip(self.param_groups, sd.get("param_groups", [])):
             g.update({k: s[k] for k in ("init_lr", "lr", "weight_decay") if k in s})
         if self.separate_master:
