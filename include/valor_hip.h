@@ -426,6 +426,20 @@ int valor_l2norm_bwd(void* stream, int dtype, const void* y, const void* dy, con
 int valor_gather_rows(void* stream, int dtype, const void* src, const int64_t* idx, void* out, int64_t n, int E, int64_t src_ld);
 int valor_scatter_rows(void* stream, int dtype, const void* src, const int64_t* idx, void* dst, int64_t n, int E, int64_t dst_ld);
 int valor_cast_from_f32(void* stream, int dtype, const float* in, void* out, int64_t n);
+/* BERT token masking, modeling.py:134-174, given the per-row mask counts k [b] (int32, 1 <= k[i] <= the row's candidates, drawn by the
+ * host: Binomial(m_i, p) | >= 1). Candidates = positions j >= 1 with tokens[i, j] != 0. Each draws Philox4x32-10(seed, offset + i*T + j);
+ * the row selects its k[i] candidates with the smallest key w0 | w1 << 32 (ties: lower j); a selected position becomes mask_token if
+ * w2 < floor(0.8 * 2^32), else range_start + umulhi(w3, range_end - range_start) if w2 < floor(0.9 * 2^32), else stays (bias of the
+ * random token: below (range_end - range_start) / 2^32). tokens_out / labels [b, T] int64, written in full: labels = the original token
+ * at selected positions, -1 elsewhere. k[i] is clamped to the row's candidate count. T <= 512; no atomics (deterministic). */
+int valor_mask_tokens(void* stream, const int64_t* tokens, const int32_t* k, int b, int T, uint64_t seed, uint64_t offset,
+                      int64_t mask_token, int64_t range_start, int64_t range_end, int64_t* tokens_out, int64_t* labels);
+/* masked-row gather table of a decoder pass, pretrain.py:441,495 (the order of labels.nonzero()): for every group g < G and every
+ * position with labels[i, j] != -1 (row-major), idx[g*n + s] = r0 + (g*b + i)*Ttot + j and lab_out[g*n + s] = labels[i, j], where the
+ * selected positions of row i take slots s = row_off[i], row_off[i] + 1, ... (int32 exclusive cumsum of the per-row counts, n = their
+ * total). A row never writes past row_off[i + 1] (n for the last row). labels [b, T] int64, T <= 512, Ttot >= T; idx / lab_out [G*n]. */
+int valor_masked_rows(void* stream, const int64_t* labels, const int32_t* row_off, int b, int T, int G, int64_t Ttot, int64_t r0,
+                      int64_t n, int64_t* idx, int64_t* lab_out);
 /* The head of one decoding step against a K|V cache, per sequence r with its new token tok[r] at text position *t_dev (device scalar):
  * x[r, j] = BertEmbeddings before its LayerNorm (bert.py:190-218) of tok[r] at position t (j = 0) and of mask_id at t + 1 (j = 1, J = 2);
  * kmask[r, P + t] = tok[r] != 0 ? 0 : neg (bert.py:857,885); amask [R, J, L] = the step's additive attention rows (causal over the text,

@@ -509,3 +509,35 @@ def group_mean_bwd(dout, X):
     din = torch.empty((dout.shape[0] * X, dout.shape[1]), dtype=dout.dtype, device=dout.device)
     lib.call("valor_group_mean_bwd", _stream(), dt_of(dout), _ptr(dout), _ptr(din), dout.shape[0], X, dout.shape[1])
     return din
+
+
+def mask_tokens(tokens, k, seed, offset, mask_token, range_start, range_end):
+    """BERT token masking with host-drawn per-row counts (valor_mask_tokens): tokens [b, T] int64, k [b] int32 (1 <= k[i] <= the row's
+    candidates) -> (tokens_out, labels) [b, T] int64, labels -1 at unselected positions."""
+    _check_gpu(tokens, k)
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.dim() == 2
+    assert k.dtype == torch.int32 and k.is_contiguous() and k.numel() == tokens.shape[0]
+    b, T = tokens.shape
+    out, labels = torch.empty_like(tokens), torch.empty_like(tokens)
+    lib.call("valor_mask_tokens", _stream(), _ptr(tokens), _ptr(k), b, T, int(seed), int(offset), int(mask_token), int(range_start),
+             int(range_end), _ptr(out), _ptr(labels))
+    return out, labels
+
+
+def masked_rows(labels, row_off, n, G=1, Ttot=None, r0=0, idx=None, lab_out=None):
+    """gather indices + labels of the positions with labels != -1 (valor_masked_rows), in the order of labels.nonzero() repeated for G
+    groups: labels [b, T] int64, row_off [b] int32 = the exclusive cumsum of the per-row counts, n = their total. idx / lab_out: [G*n]
+    int64 buffers to write (views into a larger buffer are fine) or None (allocated)."""
+    _check_gpu(labels, row_off, idx, lab_out)
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 2
+    assert row_off.dtype == torch.int32 and row_off.is_contiguous() and row_off.numel() == labels.shape[0]
+    b, T = labels.shape
+    if idx is None:
+        idx = torch.empty(G * n, dtype=torch.int64, device=labels.device)
+    if lab_out is None:
+        lab_out = torch.empty(G * n, dtype=torch.int64, device=labels.device)
+    for t in (idx, lab_out):
+        assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == G * n
+    lib.call("valor_masked_rows", _stream(), _ptr(labels), _ptr(row_off), b, T, G, T if Ttot is None else int(Ttot), int(r0), int(n),
+             _ptr(idx), _ptr(lab_out))
+    return idx, lab_out

@@ -132,6 +132,8 @@ SIGNATURES = {
     "valor_beam_select": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "valor_scatter_rows": [_vp, _i, _vp, _vp, _vp, _i64, _i, _i64],
     "valor_cast_from_f32": [_vp, _i, _vp, _vp, _i64],
+    "valor_mask_tokens": [_vp, _vp, _vp, _i, _i, _u64, _u64, _i64, _i64, _i64, _vp, _vp],
+    "valor_masked_rows": [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _vp, _vp],
     "valor_dact_mul": [_vp, _i, _vp, _vp, _vp, _i64, _i],
     "valor_mean_f32": [_vp, _vp, _i64, _vp],
     "valor_rowdot_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i],

@@ -17,7 +17,8 @@ Design differences (MI355X-first, results identical):
   * pre-LN blocks fuse residual-add + next LayerNorm (+ dropout) in one kernel; post-LN BERT fuses
     bias + dropout + residual + LayerNorm;
   * masked-row gather indices and attention masks come from the host-side TokenMasker (no device
-    round trip, modeling.py:134-174 runs on CPU in the reference too).
+    round trip, modeling.py:134-174 runs on CPU in the reference too); with token_masker='device' the masks are drawn by
+    DeviceTokenMasker (host: per-row counts, device: positions / replacements / gather indices), same law, other draws.
 """
 import math
 import os
@@ -27,6 +28,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .. import kernels as K
 from .. import ops, streams
 from ..arena import ParamArena
 from ..hoststage import HostStage
@@ -90,6 +92,97 @@ def _opt(opts, name, default):
     if isinstance(opts, dict):
         return opts.get(name, default)
     return getattr(opts, name, default)
+
+
+MASKER_MODES = ("host", "device")
+
+
+def token_masker_mode(opts):
+    """the `token_masker` option: 'host' (TokenMasker, the reference's draw order: the parity mode and the default) or 'device'
+    (DeviceTokenMasker); VALOR_MASKER, when set, overrides it."""
+    mode = os.environ.get("VALOR_MASKER") or _opt(opts, "token_masker", "host")
+    if mode not in MASKER_MODES:
+        raise ValueError(f"token_masker / VALOR_MASKER: expected one of {MASKER_MODES}, got {mode!r}")
+    return mode
+
+
+def draw_mask_counts(m, p, rng):
+    """k_i ~ Binomial(m_i, p) conditioned on k_i >= 1, for every row at once: the rows that drew 0 draw again (the reference redraws a
+    row until it selects something, modeling.py:143-158). m: int array of candidate counts, all >= 1."""
+    k = rng.binomial(m, p)
+    redo = np.flatnonzero(k == 0)
+    while redo.size:
+        k[redo] = rng.binomial(m[redo], p)
+        redo = redo[k[redo] == 0]
+    return k
+
+
+def _dp_rank():
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+class MaskedLabels:
+    """the labels of a DeviceTokenMasker draw: `labels` [b, T] int64 on the device (-1 = not selected), `counts` the per-row label counts
+    on the host (numpy), `offsets` their exclusive cumsum on the device (int32 [b]), `src` the unmasked host tokens (attention masks are
+    built from them: masking never writes a 0, so the padding is the same)."""
+    __slots__ = ("labels", "counts", "offsets", "src")
+
+    def __init__(self, labels, counts, offsets, src):
+        self.labels, self.counts, self.offsets, self.src = labels, counts, offsets, src
+
+    @property
+    def n(self):
+        return int(self.counts.sum())
+
+
+def _label_tensor(labels):
+    """what the evaluation outputs carry as txt_labels_*: the [b, T] labels (on the device for a DeviceTokenMasker draw)"""
+    return labels.labels if isinstance(labels, MaskedLabels) else labels
+
+
+class DeviceTokenMasker:
+    """BERT-style masking with TokenMasker's joint law (modeling.py:134-174) but not its draws, decomposed as
+      1. host: per row k_i ~ Binomial(m_i, p) | k_i >= 1 (m_i = candidates: j >= 1, token != 0), numpy Generator seeded from
+         (seed, rank, call index) -- O(b) work, and n = sum(k_i) stays known on the host, so the masked-row gather, the head and the
+         cross-entropy keep their host-known shapes with no device-to-host read;
+      2. device (valor_mask_tokens): the k_i candidates with the smallest Philox keys, 80 / 10 / 10 % [MASK] / random token / kept.
+    A k-smallest-keys subset is uniform among the k-subsets, so 1 + 2 is the reference's distribution. The Philox key folds in the
+    data-parallel rank (ranks draw different patterns); the counter window advances by b*T per call and is the masker's own (not
+    ops.DropoutState's: a step's dropout windows are the same in both modes). State = the plain ints seed / calls / offset.
+    Call shape of TokenMasker: (host tokens, mask_prob) -> (device tokens, MaskedLabels). Not used for QA answer rows (forward_qa): the
+    image-QA tiling indexes the host tensors, so they stay on TokenMasker in both modes."""
+
+    def __init__(self, mask_token, range_start, range_end, put, seed=42):
+        self.mask_token = mask_token
+        self.range = [range_start, range_end]
+        self.put = put              # host tensor -> device tensor (the model's staging ring)
+        self.seed = int(seed)
+        self.calls = 0
+        self.offset = 0
+        self._keys = {}
+
+    def philox_key(self, rank):
+        key = self._keys.get(rank)
+        if key is None:
+            w = np.random.SeedSequence(self.seed, spawn_key=(rank, 0)).generate_state(2, np.uint32)
+            key = self._keys[rank] = int(w[0]) | int(w[1]) << 32
+        return key
+
+    def __call__(self, tokens, mask_prob):
+        src = tokens.cpu().long().contiguous()
+        toks = src.numpy()
+        b, T = toks.shape
+        m = np.count_nonzero(toks[:, 1:], axis=1)
+        if not m.all():
+            raise ValueError("DeviceTokenMasker: a row without maskable tokens never terminates in the reference either")
+        rank = _dp_rank()
+        k = draw_mask_counts(m, mask_prob, np.random.default_rng(np.random.SeedSequence(self.seed, spawn_key=(rank, 1, self.calls))))
+        meta = self.put(torch.from_numpy(np.stack((k, np.cumsum(k) - k)).astype(np.int32)))       # [k ; row offsets]: one upload
+        out, labels = K.mask_tokens(self.put(src), meta[0], self.philox_key(rank), self.offset, self.mask_token, *self.range)
+        self.calls += 1
+        self.offset += b * T
+        return out, MaskedLabels(labels, k, meta[1], src)
 
 
 class _DeferredKV:
@@ -196,6 +289,9 @@ class VALOR(nn.Module):
         self.vocab = {t: i for i, t in enumerate(self.vocab_tokens)}
         self.bos_token, self.eos_token, self.text_mask_token = self.vocab["[CLS]"], self.vocab["[SEP]"], self.vocab["[MASK]"]
         self.text_masker = TokenMasker(self.text_mask_token, 106, self.spec.vocab)     # modeling.py:673
+        self.token_masker = token_masker_mode(opts)
+        self.device_masker = (DeviceTokenMasker(self.text_mask_token, 106, self.spec.vocab, self._dev, seed=int(_opt(opts, "seed", 42)))
+                              if self.token_masker == "device" else None)
         self.reducer = None
         self.stage = HostStage(self.device)
         self._const = {}
@@ -951,13 +1047,14 @@ class VALOR(nn.Module):
                 return torch.cat([r[0] for r in res], dim=0), res[0][1]
             return sum(res) / len(res) if compute_loss else None        # equal row counts per group: the mean of the per-group means
         G, T = len(groups), txt_input.shape[1]
+        dev_lab = isinstance(txt_labels, MaskedLabels)          # token_masker='device': tokens and labels on the device
         ids = self._dev(txt_input)
         x = self._bert_embed(ids, T, None, self._full_attn and casual)
         if prompt_cpu is not None:
             xp = self._bert_embed(self._dev(prompt_cpu), prompt_cpu.shape[1], "prompt")
             x = torch.cat((x, xp), dim=1)
         Ttot = x.shape[1]
-        mask = self._dev(self._bert_mask(txt_input, prompt_cpu, casual, self._full_attn and casual))
+        mask = self._dev(self._bert_mask(txt_labels.src if dev_lab else txt_input, prompt_cpu, casual, self._full_attn and casual))
         if G > 1:
             x = x.repeat(G, 1, 1)
             mask = mask.repeat(G, 1, 1)
@@ -968,18 +1065,23 @@ class VALOR(nn.Module):
             kv_range = self._dev(torch.tensor([list(ranges[g]) for g in groups for _ in range(b)], dtype=torch.int32))
         # kv_b: the K|V batch when it is smaller than the text rows (row r attends to clip r % kv_b: answer-major tiled rows of image QA)
         hidden = self.bert_encoder(x, mask, kv_layers, kv_range, (kv_b or b) if kv_layers is not None else 0)
-        sel = (txt_labels != -1)
-        bi, tj = sel.nonzero(as_tuple=True)                      # host tensors, row-major order == boolean indexing order
-        n = bi.numel()
-        idx = self._dev(torch.cat([(g * b + bi) * Ttot + tj for g in range(G)]))
+        if dev_lab:
+            n = txt_labels.n                                     # host-known: no read-back
+            idx, labels = K.masked_rows(txt_labels.labels, txt_labels.offsets, n, G, Ttot)
+        else:
+            sel = (txt_labels != -1)
+            bi, tj = sel.nonzero(as_tuple=True)                  # host tensors, row-major order == boolean indexing order
+            n = bi.numel()
+            idx = self._dev(torch.cat([(g * b + bi) * Ttot + tj for g in range(G)]))
         rows = ops.gather_rows(hidden.reshape(-1, hidden.shape[-1]), idx)
         h = self.cls_transform(rows)
         P = self.P
-        labels = self._dev(txt_labels[sel].repeat(G))
+        if not dev_lab:
+            labels = self._dev(txt_labels[sel].repeat(G))
         if compute_loss and per_sample:
             # forward_qa_single (pretrain.py:1282-1290): CE summed per sample / that sample's masked-token count, then the mean over
             # samples (and over groups: G * b equally weighted segments). Rows are ordered (group, sample, position).
-            counts = sel.sum(dim=1).tolist()
+            counts = txt_labels.counts.tolist() if dev_lab else sel.sum(dim=1).tolist()
             rows = [r for r, c in enumerate(counts) if c > 0]            # padding rows of a tiled batch carry no labels
             losses = ops.decoder_xent_segments(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], P["cls.decoder.bias"], labels,
                                                [counts[r] for r in rows] * G)
@@ -1038,13 +1140,15 @@ class VALOR(nn.Module):
         P, H, E = self.P, self.spec.heads, self.spec.hidden
         p = self.p_drop if self.training else 0.0
         xs, ssegs, xsegs, idxs, labs, seg_rows, r0 = [], [], [], [], [], [], 0
+        dev_passes = []             # token_masker='device': (slot in idxs, labels, G, Ttot, r0) -- valor_masked_rows writes those slices
         for (tag, txt_input, txt_labels, groups, prompt_cpu, casual) in passes:
             G, T = len(groups), txt_input.shape[1]
+            dev_lab = isinstance(txt_labels, MaskedLabels)
             x = self._bert_embed(self._dev(txt_input), T, None, self._full_attn and casual)
             if prompt_cpu is not None:
                 x = torch.cat((x, self._bert_embed(self._dev(prompt_cpu), prompt_cpu.shape[1], "prompt")), dim=1)
             Ttot = x.shape[1]
-            mask = self._dev(self._bert_mask(txt_input, prompt_cpu, casual, self._full_attn and casual))
+            mask = self._dev(self._bert_mask(txt_labels.src if dev_lab else txt_input, prompt_cpu, casual, self._full_attn and casual))
             if G > 1:
                 x = x.repeat(G, 1, 1)
                 mask = mask.repeat(G, 1, 1)
@@ -1053,11 +1157,17 @@ class VALOR(nn.Module):
             if kv_layers is not None:
                 kvr = self._dev(torch.tensor([list(ranges[g]) for g in groups for _ in range(b)], dtype=torch.int32))
                 xsegs.append((r0, Bp, Ttot, kvr, b))
-            sel = (txt_labels != -1)
-            bi, tj = sel.nonzero(as_tuple=True)
-            idxs.append(torch.cat([r0 + (g * b + bi) * Ttot + tj for g in range(G)]))
-            labs.append(txt_labels[sel].repeat(G))
-            seg_rows.append(G * bi.numel())
+            if dev_lab:
+                dev_passes.append((len(idxs), txt_labels, G, Ttot, r0))
+                idxs.append(None)
+                labs.append(None)
+                seg_rows.append(G * txt_labels.n)
+            else:
+                sel = (txt_labels != -1)
+                bi, tj = sel.nonzero(as_tuple=True)
+                idxs.append(torch.cat([r0 + (g * b + bi) * Ttot + tj for g in range(G)]))
+                labs.append(txt_labels[sel].repeat(G))
+                seg_rows.append(G * bi.numel())
             xs.append(x.reshape(-1, E))
             r0 += Bp * Ttot
         # the bigger pass first: in backward it writes the shared dK|dV buffer, the others accumulate into it
@@ -1085,10 +1195,27 @@ class VALOR(nn.Module):
                     X = ops.checkpoint(lambda X_, i=i: self._decoder_layer(i, X_, None, ssegs, xsegs, dkv), X)
                 else:
                     X = ops.checkpoint(lambda X_, kv_, i=i: self._decoder_layer(i, X_, kv_, ssegs, xsegs, dkv), X, kv)
-        rows = ops.gather_rows(X, self._dev(torch.cat(idxs)))
+        if dev_passes:
+            # one index and one label buffer for all passes; each device-masked pass writes its slice in place, a host-labelled one (caption
+            # type 'lm' beside a device-masked mlm) is uploaded into its slice
+            idx_all = torch.empty(sum(seg_rows), dtype=torch.int64, device=self.device)
+            lab_all = torch.empty_like(idx_all)
+            starts = np.concatenate(([0], np.cumsum(seg_rows)))
+            for (slot, ml, G, Ttot, r0_) in dev_passes:
+                s0, s1 = int(starts[slot]), int(starts[slot + 1])
+                K.masked_rows(ml.labels, ml.offsets, ml.n, G, Ttot, r0_, idx=idx_all[s0:s1], lab_out=lab_all[s0:s1])
+            for slot, (ix, lb) in enumerate(zip(idxs, labs)):
+                if ix is not None:
+                    idx_all[int(starts[slot]):int(starts[slot + 1])].copy_(self._dev(ix))
+                    lab_all[int(starts[slot]):int(starts[slot + 1])].copy_(self._dev(lb))
+        else:
+            idx_all, lab_all = self._dev(torch.cat(idxs)), None
+        rows = ops.gather_rows(X, idx_all)
         h = self.cls_transform(rows)
+        if lab_all is None:
+            lab_all = self._dev(torch.cat(labs))
         losses = ops.decoder_xent_segments(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], P["cls.decoder.bias"],
-                                           self._dev(torch.cat(labs)), seg_rows, smoothing=self._smoothing)
+                                           lab_all, seg_rows, smoothing=self._smoothing)
         res = {}
         for (tag, *_), l in zip(passes, losses):
             res.setdefault(tag, []).append(l)
@@ -1101,12 +1228,12 @@ class VALOR(nn.Module):
         rows -> cross-entropy. Same kernels as the decoder passes of forward_pt."""
         self.stage.begin_step()
         txt = batch["txt_tokens"]["bert_tokens"].cpu()
-        mlm_in, mlm_lab = self.text_masker(txt, 0.15)
+        mlm_in, mlm_lab = self.mask_text(txt, 0.15)
         out = {}
         loss = self._decoder_groups(mlm_in, mlm_lab, ["t"], None, False, None, {}, txt.shape[0], compute_loss, "mlm", out)
         if compute_loss:
             return {"mlm_loss": loss}
-        out["txt_labels_mlm"] = mlm_lab
+        out["txt_labels_mlm"] = _label_tensor(mlm_lab)
         return out
 
     # ------------------------------------------------------------------ the hot path
@@ -1166,7 +1293,9 @@ class VALOR(nn.Module):
         txt = batch["txt_tokens"]["bert_tokens"].cpu()
         nums = [int(n) for n in batch.get("answer_nums", [1] * txt.shape[0])]
         b = len(nums)
-        qa_in, qa_lab = self.caption_inputs(txt, 0.99)                 # in the reference's row order (sample-major): the draw order is the contract
+        # in the reference's row order (sample-major): the draw order is the contract. The host masker in both token_masker modes: the
+        # image-QA tiling below indexes the host tensors
+        qa_in, qa_lab = self.caption_inputs(txt, 0.99, host_masker=True)
         weights = None
         if any(n != 1 for n in nums):
             # image QA (pretrain.py:1243-1265): the reference tiles question / video / audio rows per candidate answer. Here the answer
@@ -1205,9 +1334,17 @@ class VALOR(nn.Module):
                 contra_task = i.split("%")[1:]
         return self._forward_groups(batch, mlm_task, caption_task, contra_task, compute_loss, contra_ratio=self.contra_loss_ratio)
 
-    def caption_inputs(self, txt, mask_prob=0.6):
+    def mask_text(self, txt, mask_prob):
+        """the MLM / caption masker of the configured mode (token_masker): TokenMasker -> host (tokens, labels), DeviceTokenMasker ->
+        device tokens and MaskedLabels"""
+        if self.device_masker is not None:
+            return self.device_masker(txt, mask_prob)
+        return self.text_masker(txt, mask_prob)
+
+    def caption_inputs(self, txt, mask_prob=0.6, host_masker=False):
         """inputs / labels of the caption passes (model/pretrain.py:424-433, :807-816; the answer rows of QA at 0.99, :1225-1234): caption_type 'unimlm' = TokenMasker; 'lm' =
-        the tokens as they are, label = the NEXT token (0 = padding and the last position: ignored, -1)"""
+        the tokens as they are, label = the NEXT token (0 = padding and the last position: ignored, -1). host_masker: TokenMasker
+        whatever the token_masker mode (QA)"""
         if self.caption_type == "unimlm" and self.full_masker:          # full_mask, pretrain.py:137-142
             n = txt.shape[1]
             tokens = torch.cat((txt, torch.full_like(txt, self.text_mask_token)), dim=1)
@@ -1216,7 +1353,7 @@ class VALOR(nn.Module):
             labels[:, n:2 * n - 1][nz] = txt[:, 1:n][nz]
             return tokens, labels
         if self.caption_type == "unimlm":
-            return self.text_masker(txt, mask_prob)
+            return self.text_masker(txt, mask_prob) if host_masker else self.mask_text(txt, mask_prob)
         labels = torch.zeros_like(txt)
         labels[:, :txt.shape[1] - 1] = txt[:, 1:]
         labels[labels == 0] = -1
@@ -1242,6 +1379,7 @@ class VALOR(nn.Module):
         # Host-side token masking FIRST, in the reference's order (the masker consumes the python RNG: caption
         # pretrain.py:428, then mlm :488; nothing else on this path does). Done before any kernel of this step is queued,
         # its Python loops overlap the GPU's tail of the previous step instead of draining the pipeline mid-forward.
+        # (token_masker='device': the two masking launches are the first of the step.)
         cap_in = cap_lab = mlm_in = mlm_lab = None
         if caption_task and self.full_masker and not self._full_attn:
             # forward_pt builds the doubled rows (pretrain.py:425-426) but slices the 'tv' / 'ta' outputs with the ORIGINAL length against the
@@ -1255,7 +1393,7 @@ class VALOR(nn.Module):
             if caption_task:
                 cap_in, cap_lab = self.caption_inputs(txt)
             if mlm_task:
-                mlm_in, mlm_lab = self.text_masker(txt, 0.15)
+                mlm_in, mlm_lab = self.mask_text(txt, 0.15)
         alltasks = "".join(mlm_task + caption_task + contra_task)
         video_output = audio_output = txt_output = None
         clip_text = "t" in "".join(contra_task) and sp.txt_encoder != "bert"
@@ -1448,10 +1586,10 @@ class VALOR(nn.Module):
                 if g in mlm_task:
                     prompt = self.get_task_prompt(PROMPTS["mlm_" + g], bs)
                     self._decoder_groups(mlm_in, mlm_lab, [g], prompt, False, kv_layers, ranges, bs, False, "mlm", out)
-            out["txt_labels_mlm"] = mlm_lab
+            out["txt_labels_mlm"] = _label_tensor(mlm_lab)
         if caption_task:                                                          # pretrain.py:419-481
             groups = [g for g in ("tva", "tv", "ta") if g in caption_task]
             prompt = self.get_task_prompt(PROMPTS["caption"], bs) if self.use_task_prompt else None
             self._decoder_groups(cap_in, cap_lab, groups, prompt, True, kv_layers, ranges, bs, False, "caption", out)
-            out["txt_labels_caption"] = cap_lab
+            out["txt_labels_caption"] = _label_tensor(cap_lab)
         return out
