@@ -8,6 +8,11 @@ with fp32 master weights, task pt_contra%tva%tv%ta_caption%tva%tv%ta_mlm%tva (MG
 64, 8 frames x 224^2, 2 x 5.12 s audio slices, 32 text tokens, dropout 0.1 (the reference's training setting),
 synthetic inputs resident in HBM, random-init weights. A step = forward + backward + gradient all-reduce +
 global-norm clip + fused AdamW. Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the line. For N > 1 the
+set-up includes `comm_probe`, which picks the reduce mode the timed steps run, and the line carries the replica checksum of the
+state they left (one reduction, no run of its own). With --full the bench also runs what takes runs of its own behind the timed
+region: the GEMM roofline steps, `dp_sim`, the other variants, caption generation and the CPU baseline (one GPU).
 """
 import argparse
 import gc
@@ -396,8 +401,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs of this node. Without a launcher (no WORLD_SIZE in the environment) "
                     "N > 1 re-executes this script under torch.distributed.run with N ranks")
-    ap.add_argument("--sim-world", type=int, default=8, help="also time the contrastive block at the global batch of this many ranks "
-                    "(single-GPU runs only; 0 = off)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the roofline "
+                    "steps, dp_sim, the variants, generation and the CPU baseline (single-GPU runs); the --no-* options "
+                    "and --sim-world choose among them")
+    ap.add_argument("--sim-world", type=int, default=8, help="with --full, also time the contrastive block at the global batch of this many "
+                    "ranks (single-GPU runs only; 0 = off)")
     ap.add_argument("--steps", type=int, default=10, help="timed steps (ms_per_step = their wall time / steps)")
     ap.add_argument("--warmup", type=int, default=5, help="untimed steps (the first ones allocate: static K|V buffers, the caching allocator's pools)")
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch (config: 512 global / 8 GPUs)")
@@ -409,12 +417,13 @@ def main():
     ap.add_argument("--graphs", type=int, default=int(os.environ.get("VALOR_GRAPHS", "1")), help="1 (default) = the CLIP ViT / AST / CLIP text encoders replay "
                     "hipGraphs (valor_amd/graphs.py: forward + backward captured on their third step; dropout offsets from a device-resident counter; "
                     "bit-identical to eager issue, profiles/r06_graphs_ab_*.txt), 0 = eager issue")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full, skip the CPU baseline")
     ap.add_argument("--accum", type=int, default=1, help="micro-steps per optimizer step (gradient accumulation, train_utils.py:311-317): the per-GPU batch of "
                     "a step is --batch x --accum. BASELINE configs[4] (VALOR-large, 16 frames, global batch 1024 = 128 per GPU) runs as "
                     "--variant large --frames 16 --batch 64 --accum 2: 128 samples of 16 frames do not fit one forward-backward (182 GB at 64)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the short timed runs of --variant swin / large behind the headline region")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the instrumented steps behind the timed region (roofline = null)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full, skip the short timed runs of --variant swin / large and the "
+                    "generation timing behind the headline region")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full, skip the instrumented steps behind the timed region (roofline = null)")
     ap.add_argument("--variant", choices=["clip", "swin", "large", "clip_large"], default="clip",
                     help="clip: config/pretrain-VALOR-base.json (BASELINE configs[1], the headline); swin: scripts/pretrain.sh "
                          "(VideoSwin-B + BERT text); large: BASELINE configs[3]/[4] (VideoSwin-L embed 192 / 2-2-18-2 + BERT-large "
@@ -486,6 +495,7 @@ def main():
     random.seed(50 + rank)
     DropoutState.reset(1234 + rank)
 
+    # installed (disabled) in plain runs too: the timed steps then issue their GEMMs through the same call path with or without --full
     timer = GemmTimer()
     timer.install()
     probe = None
@@ -562,40 +572,40 @@ def main():
         timing["wait_ms_per_step"] = round(sum(timing["wait_ms"]) / len(timing["wait_ms"]), 1)
     seg1 = torch.cuda.memory_stats().get("segment.all.allocated", 0)
     new_segs_mb = sorted(round(sg["total_size"] / 2 ** 20, 1) for sg in torch.cuda.memory_snapshot() if sg["address"] not in segs_before)
-    # roofline pass: the SAME step, run right after the timed region, with a HIP-event pair (recorded on the launch
+    # roofline pass (--full): the SAME step, run right after the timed region, with a HIP-event pair (recorded on the launch
     # stream) around every 4th valor_gemm launch; 4 instrumented steps with a rotating offset cover every launch once.
-    timer.enabled = True
-    n_inst = 0 if args.no_roofline else 4
-    # kernel durations are only meaningful when the kernel has the chip to itself: the instrumented steps run the encoders on ONE
-    # stream (the timed region above runs them on two, valor_amd/streams.py)
-    two_streams = os.environ.get("VALOR_ENCODER_STREAMS")
-    os.environ["VALOR_ENCODER_STREAMS"] = "0"
-    if n_inst and args.graphs:
-        # ... and only when Python issues it: the instrumented steps run eagerly (a GEMM inside a replayed graph never passes the timer,
-        # and an event pair recorded while a graph is being captured is not a timestamp)
-        model.enable_graphs(False)
-    timer.enabled = False
-    for _ in range(2 if n_inst else 0):          # settle: the audio / text activations move from the side stream's allocator pool to this stream's (device
-        one_step()                          # allocations stall the host, a starved GPU makes event pairs measure launch latency)
-    sync()
-    timer.enabled = True
-    t1 = time.perf_counter()
-    for _ in range(n_inst):
-        one_step()
-        timer.next_step()
-    sync()
-    inst_elapsed = (time.perf_counter() - t1) / max(n_inst, 1)
-    timer.enabled = False
-    if two_streams is None:
-        del os.environ["VALOR_ENCODER_STREAMS"]
-    else:
-        os.environ["VALOR_ENCODER_STREAMS"] = two_streams
+    n_inst = 4 if args.full and not args.no_roofline else 0
+    inst_elapsed = None
+    if n_inst:
+        # kernel durations are only meaningful when the kernel has the chip to itself: the instrumented steps run the encoders on ONE
+        # stream (the timed region above runs them on two, valor_amd/streams.py)
+        two_streams = os.environ.get("VALOR_ENCODER_STREAMS")
+        os.environ["VALOR_ENCODER_STREAMS"] = "0"
+        if args.graphs:
+            # ... and only when Python issues it: the instrumented steps run eagerly (a GEMM inside a replayed graph never passes the timer,
+            # and an event pair recorded while a graph is being captured is not a timestamp)
+            model.enable_graphs(False)
+        for _ in range(2):                  # settle: the audio / text activations move from the side stream's allocator pool to this stream's (device
+            one_step()                      # allocations stall the host, a starved GPU makes event pairs measure launch latency)
+        sync()
+        timer.enabled = True
+        t1 = time.perf_counter()
+        for _ in range(n_inst):
+            one_step()
+            timer.next_step()
+        sync()
+        inst_elapsed = (time.perf_counter() - t1) / n_inst
+        timer.enabled = False
+        if two_streams is None:
+            del os.environ["VALOR_ENCODER_STREAMS"]
+        else:
+            os.environ["VALOR_ENCODER_STREAMS"] = two_streams
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     replicas_identical = None
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         # data parallelism keeps the replicas bit-identical (same reduced gradients, same optimizer): an exact integer checksum of the
-        # parameter arena from every rank must agree
+        # parameter arena from every rank must agree (one reduction of the state the timed steps left, no run of its own: plain runs too)
         cs = model.arena.flat.view(torch.int16).to(torch.int64).sum().reshape(1)
         allcs = [torch.zeros_like(cs) for _ in range(world)]
         torch.distributed.all_gather(allcs, cs)
@@ -655,13 +665,13 @@ def main():
                "roofline": roof}
         if probe is not None:
             res["comm_probe"] = probe
-        if world == 1 and args.sim_world > 1:
+        if args.full and world == 1 and args.sim_world > 1:
             try:
                 res["dp_sim"] = sim_world(model, spec, args.sim_world, args.batch, args.frames, args.audio_slices)
             except Exception as e:
                 res["dp_sim"] = {"error": repr(e)}
-        if world == 1 and args.variant == "clip" and not args.no_variants:
-            # the other configurations this repository claims, driver-visible: a few timed steps each of the VideoSwin-B variant
+        if args.full and world == 1 and args.variant == "clip" and not args.no_variants:
+            # the other configurations this repository claims: a few timed steps each of the VideoSwin-B variant
             # (scripts/pretrain.sh) and of BASELINE configs[3] (VideoSwin-L + BERT-large), same batch / clip length, after the headline region
             del engine, model, batch
             gc.collect()
@@ -679,13 +689,13 @@ def main():
                     res["variants"][v] = {"error": repr(e)}
                 gc.collect()
                 torch.cuda.empty_cache()
-            try:                       # the adjacent consumer of the same kernels, driver-visible: captions/s
+            try:                       # the adjacent consumer of the same kernels: captions/s
                 res["generation"] = time_generation(args, dev)
             except Exception as e:
                 res["generation"] = {"error": repr(e)}
             gc.collect()
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(frames=args.frames, audio_slices=args.audio_slices, variant=args.variant)
             except Exception as e:      # the baseline is a reported number only; never fail the bench on it
