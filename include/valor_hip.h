@@ -332,6 +332,12 @@ int valor_xent_smooth_fwd(void* stream, int dtype, const void* logits, const int
 int valor_xent_smooth_bwd(void* stream, int dtype, void* logits_inout, const int64_t* labels, const float* lse,
                           const float* gscale_dev, float gmul, int64_t rows, int V, int64_t ld, float smoothing);
 int valor_mean_f32(void* stream, const float* x, int64_t n, float* out);
+/* the reward-weighted caption loss of SCST (reward_loss, pretrain.py:166-173: the mean over labelled positions of -r_i logP):
+ * valor_xent_weighted_bwd = valor_xent_bwd with g_i = (*gscale_dev) * gmul * w_rows[i] (w_rows fp32 [rows]; null: valor_xent_bwd);
+ * valor_weighted_mean_f32: *out = sum_i w[i] * x[i] / n. Neither reads anything back to the host. */
+int valor_xent_weighted_bwd(void* stream, int dtype, void* logits_inout, const int64_t* labels, const float* lse, const float* w_rows,
+                            const float* gscale_dev, float gmul, int64_t rows, int V, int64_t ld);
+int valor_weighted_mean_f32(void* stream, const float* x, const float* w, int64_t n, float* out);
 
 /* ---- MGA fine-grained contrastive: compute_fine_matrix_slice (pretrain.py:191-211) + contrastive_loss
  * (modeling.py:418-433). S = featA . featB^T comes from valor_gemm (fp32 [B*T, ldS]). */
@@ -455,6 +461,15 @@ int valor_decode_prologue(void* stream, int dtype, const int64_t* tok, const int
 int valor_beam_select(void* stream, const float* logits, int64_t ld, int64_t row_stride_s, int64_t row_stride_k, const float* lse,
                       const float* seq_logprob, const float* seq_mask, int b, int cur, int V, int beam, float* sel_val,
                       int64_t* sel_idx, float* lse_out);
+/* one step of the sampled caption decode, VALOR.decode_greedy mode 'sample' (pretrain.py:1007-1020): per row r < R of fp32 logits
+ * [R, V] (row pitch ld >= V) with unfinished[r] != 0, the draw w = argmax_w (z_w - log(-log u_w)) (Gumbel-max: w ~ softmax(z);
+ * u_w = (x >> 9) 2^-23 + 2^-24 (exact, in (0, 1)), x = Philox4x32-10(seed, offset + r * ceil(V / 4) + w / 4) word w % 4; ties to the
+ * lower index; a -inf logit
+ * is never drawn). tok[r] = sents[r * sents_ld] = w, logprobs[r * lp_ld] = z_w - logsumexp(z); unfinished[r] = 0 if w == eos. A row
+ * with unfinished[r] == 0 writes eos and logP 0. A row with a NaN logit (or no finite one) writes eos, logP NaN, and finishes.
+ * The caller advances offset by R * ceil(V / 4) per step. One workgroup per row, no atomics: deterministic. */
+int valor_sample_tokens(void* stream, const float* logits, int64_t ld, int R, int V, uint64_t seed, uint64_t offset, int64_t eos,
+                        uint8_t* unfinished, int64_t* tok, int64_t* sents, int64_t sents_ld, float* logprobs, int64_t lp_ld);
 /* backward of a fused activation when no GEMM can absorb it: modeling.py:249-252 */
 int valor_dact_mul(void* stream, int dtype, const void* dh, const void* u, void* du, int64_t n, int act);
 /* Linear(E -> 1) of the fine-weight heads: pretrain.py:104-112 */

@@ -2,7 +2,10 @@
 8 frames + 2 audio slices, group 'tva', greedy and beam-3 decoding to max_generation_len (random weights never emit [SEP]: every row runs
 the full length). Prints where the time goes: the encoders + K|V projections (once per clip) and the decoding loop (re-runs the text rows
 each step like the reference with VALOR_KV_CACHE=0; two rows per sequence against the K|V cache otherwise, decode.py).
-usage: [GEN_MODES=greedy,beam3] python tools/gen_bench.py out.json [batch] [max_len]"""
+Mode 'sample' is the sampled decode of SCST (decode.decode_sample_cached); mode 'scst' times one self-critical training step at the
+caption-msrvtt shape (task cap%tva%tv, a CaptionScorer of 20 synthetic references per clip) split into greedy baseline, encoders +
+sampled decoding, scoring and the loss pass (forward + backward), and one scorer call of B hypotheses.
+usage: [GEN_MODES=greedy,beam3,sample,scst] python tools/gen_bench.py out.json [batch] [max_len]"""
 import json
 import os
 import sys
@@ -36,12 +39,53 @@ def timed(fn, reps=3):
     return (time.perf_counter() - t0) / reps
 
 
+MODES = os.environ.get("GEN_MODES", "greedy,beam3").split(",")
 with torch.no_grad():
     model.eval()
     res["encode_ms"] = round(timed(lambda: decode.encode_for_generation(model, batch, ["tva"])) * 1e3, 1)
-    for name, beam in [(n, k) for n, k in (("greedy", 1), ("beam3", 3)) if n in os.environ.get("GEN_MODES", "greedy,beam3")]:
-        t = timed(lambda: decode.generate_cap(model, batch, ["tva"], beam_size=beam, max_generation_len=L), reps=2)
+    for name, beam, mode in (("greedy", 1, None), ("beam3", 3, None), ("sample", 1, "sample")):
+        if name not in MODES:
+            continue
+        t = timed(lambda: decode.generate_cap(model, batch, ["tva"], beam_size=beam, max_generation_len=L, mode=mode), reps=2)
         res[name] = {"seconds": round(t, 3), "captions_per_s": round(B / t, 1), "tokens_per_s": round(B * L / t, 1),
                      "ms_per_decoding_step": round((t * 1e3 - res["encode_ms"]) / L, 2)}
+
+if "scst" in MODES:
+    import numpy as np
+    from valor_amd import scst
+    rng = np.random.default_rng(0)
+    batch["ids"] = [f"clip{i}" for i in range(B)]
+    model.scorer = scst.CaptionScorer({i: [rng.integers(1000, 3000, size=int(rng.integers(6, 15))).tolist() for _ in range(20)]
+                                       for i in batch["ids"]})
+    model.max_generation_len = L
+    groups = ["tva", "tv"]
+
+    def split():
+        t = {}
+        sync = torch.cuda.synchronize
+        sync(); t0 = time.perf_counter()
+        greedy = model.scst_baseline(batch, groups)
+        sync(); t["greedy_ms"] = time.perf_counter() - t0; t0 = time.perf_counter()
+        vo, ao = model.scst_encode(batch, groups)
+        samples = model.scst_sample(vo, ao, groups)
+        sync(); t["encode_and_sample_ms"] = time.perf_counter() - t0; t0 = time.perf_counter()
+        rewards = {g: model.scorer(batch["ids"], scst.hypotheses(samples[g][0].cpu(), model.eos_token))
+                   - model.scorer(batch["ids"], scst.hypotheses(greedy[g], model.eos_token)) for g in groups}
+        t["score_ms"] = time.perf_counter() - t0; t0 = time.perf_counter()
+        out = model.scst_loss(vo, ao, {g: samples[g][0] for g in groups}, rewards)
+        sum(out.values()).backward()
+        sync(); t["loss_pass_fwd_bwd_ms"] = time.perf_counter() - t0
+        model.zero_grad()
+        return t
+
+    model.train()
+    split()
+    runs = [split() for _ in range(3)]
+    res["scst_step"] = {k: round(1e3 * sum(r[k] for r in runs) / len(runs), 1) for k in runs[0]}
+    hyps = [rng.integers(1000, 3000, size=L).tolist() for _ in range(B)]
+    t0 = time.perf_counter()
+    for _ in range(5):
+        model.scorer(batch["ids"], hyps)
+    res["scorer_ms_per_call"] = round((time.perf_counter() - t0) / 5 * 1e3, 2)
 print(json.dumps(res, indent=1))
 json.dump(res, open(sys.argv[1], "w"), indent=1)

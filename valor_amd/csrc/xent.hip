@@ -5,6 +5,8 @@
 //   backward: dlogits[i, j] = (exp(logits[i,j] - lse[i]) - [j == label[i]]) * g,
 //             g = (*gscale_dev) * gmul     (upstream scalar grad stays on the device: no host sync)
 //             written IN PLACE over the logits (also zero-fills the ld padding).
+//   weighted backward (valor_xent_weighted_bwd): g_i = (*gscale_dev) * gmul * w_rows[i] -- the reward-weighted caption loss of SCST
+//             (pretrain.py:166-173, mean over labelled positions of -r_i logP): dlogits = (softmax - onehot) * r_i * g / N.
 // Label smoothing (LabelSmoothing of model/pretrain.py:46-61, the caption finetune loss when config.label_smoothing > 0, :839-840): the
 // target is t[label] = 1 - eps, t[j] = eps / (V - 1) elsewhere and the row loss KL(t || softmax) = sum_j t_j (log t_j - logp_j)
 //   = (1 - eps) log(1 - eps) + eps log(eps / (V - 1)) - (1 - eps) logp[label] - eps / (V - 1) * (sum_j logp_j - logp[label]),
@@ -53,12 +55,13 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const T* logits, const in
 
 template <typename T>
 __global__ __launch_bounds__(256) void xent_bwd_kernel(T* logits, const int64_t* labels, const float* lse,
-                                                       const float* gscale_dev, float gmul, int V, int64_t ld, float eps) {
+                                                       const float* gscale_dev, float gmul, int V, int64_t ld, float eps, const float* w_rows) {
     const int64_t row = blockIdx.x;
     T* x = logits + row * ld;
     const float l = lse[row];
     const int64_t lab = labels[row];
-    const float g = (gscale_dev ? *gscale_dev : 1.0f) * gmul;
+    float g = (gscale_dev ? *gscale_dev : 1.0f) * gmul;
+    if (w_rows) g *= w_rows[row];
     const float t_other = eps > 0.f ? eps / (float)(V - 1) : 0.f, t_label = 1.0f - eps;
     for (int j = threadIdx.x; j < (int)ld; j += 256) {
         float d = 0.f;
@@ -88,17 +91,27 @@ extern "C" int valor_xent_fwd(void* stream, int dtype, const void* logits, const
     return valor_xent_smooth_fwd(stream, dtype, logits, labels, loss_rows, lse, rows, V, ld, 0.f);
 }
 
-extern "C" int valor_xent_smooth_bwd(void* stream, int dtype, void* logits_inout, const int64_t* labels, const float* lse,
-                                     const float* gscale_dev, float gmul, int64_t rows, int V, int64_t ld, float smoothing) {
+static int xent_bwd_launch(void* stream, int dtype, void* logits_inout, const int64_t* labels, const float* lse, const float* w_rows,
+                           const float* gscale_dev, float gmul, int64_t rows, int V, int64_t ld, float smoothing) {
     if (rows <= 0) return VALOR_OK;
     if (!logits_inout || !labels || !lse || V <= 0 || !(smoothing >= 0.f && smoothing < 1.f) || (smoothing > 0.f && V <= 1)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == VALOR_DT_BF16)
-        hipLaunchKernelGGL((xent_bwd_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, (bf16_t*)logits_inout, labels, lse, gscale_dev, gmul, V, ld, smoothing);
+        hipLaunchKernelGGL((xent_bwd_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, (bf16_t*)logits_inout, labels, lse, gscale_dev, gmul, V, ld, smoothing,
+                           w_rows);
     else if (dtype == VALOR_DT_F32)
-        hipLaunchKernelGGL((xent_bwd_kernel<float>), dim3((unsigned)rows), dim3(256), 0, st, (float*)logits_inout, labels, lse, gscale_dev, gmul, V, ld, smoothing);
+        hipLaunchKernelGGL((xent_bwd_kernel<float>), dim3((unsigned)rows), dim3(256), 0, st, (float*)logits_inout, labels, lse, gscale_dev, gmul, V, ld, smoothing,
+                           w_rows);
     else return VALOR_ERR_ARG;
     return valor_launch_status();
+}
+extern "C" int valor_xent_smooth_bwd(void* stream, int dtype, void* logits_inout, const int64_t* labels, const float* lse,
+                                     const float* gscale_dev, float gmul, int64_t rows, int V, int64_t ld, float smoothing) {
+    return xent_bwd_launch(stream, dtype, logits_inout, labels, lse, nullptr, gscale_dev, gmul, rows, V, ld, smoothing);
+}
+extern "C" int valor_xent_weighted_bwd(void* stream, int dtype, void* logits_inout, const int64_t* labels, const float* lse, const float* w_rows,
+                                       const float* gscale_dev, float gmul, int64_t rows, int V, int64_t ld) {
+    return xent_bwd_launch(stream, dtype, logits_inout, labels, lse, w_rows, gscale_dev, gmul, rows, V, ld, 0.f);
 }
 extern "C" int valor_xent_bwd(void* stream, int dtype, void* logits_inout, const int64_t* labels, const float* lse,
                               const float* gscale_dev, float gmul, int64_t rows, int V, int64_t ld) {

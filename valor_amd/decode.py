@@ -461,10 +461,86 @@ def decode_beam_cached(sess, b, beam, max_len):
     return outputs.contiguous()[:, 0]
 
 
-def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len):
-    """{group: (sequences, logprobs | None)} for the query groups present, through the K|V-cached session or the re-run path"""
+class SampleStream:
+    """the Philox stream of the sampled decode: plain ints (like DeviceTokenMasker). Each decode call draws under its own key, derived
+    from (seed, data-parallel rank, call index): ranks draw different samples and a rerun with the same seed draws the same ones. Inside
+    a call the counter `offset` advances by R * ceil(V / 4) per step (every group and step reads a window of its own)."""
+
+    def __init__(self, seed=42):
+        self.seed = int(seed)
+        self.calls = 0
+        self.key = None
+        self.offset = 0
+
+    def begin_call(self):
+        import numpy as np
+        from .model.valor import _dp_rank
+        w = np.random.SeedSequence(self.seed, spawn_key=(_dp_rank(), 2, self.calls)).generate_state(2, np.uint32)
+        self.key = int(w[0]) | int(w[1]) << 32
+        self.offset = 0
+        self.calls += 1
+        return self
+
+    def take(self, R, V):
+        off = self.offset
+        self.offset += R * ((V + 3) // 4)
+        return self.key, off
+
+
+def sampler_of(model):
+    """the model's SampleStream (seeded from opts.seed at first use)"""
+    s = model.__dict__.get("_sample_stream")
+    if s is None:
+        from .model.valor import _opt
+        s = model.__dict__["_sample_stream"] = SampleStream(int(_opt(model.opts, "seed", 42)))
+    return s
+
+
+def decode_sample_cached(sess, b, max_len, stream):
+    """VALOR.decode_greedy mode 'sample' (pretrain.py:1005-1020) on a DecodeSession: one step, then one valor_sample_tokens launch that draws
+    from softmax(logits), writes the logP of the draw and does the [SEP] bookkeeping. The tokens stay on the device; whether every row has
+    ended is asked every eighth step, as in decode_greedy_cached. -> (sents int64 [b, max_len], logprobs fp32 [b, max_len]); after a row's
+    first [SEP] its tokens are [SEP] and its logprobs 0."""
+    dev = sess.m.device
+    sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
+    logprobs = torch.zeros((b, max_len), device=dev)
+    unfinished = torch.ones(b, dtype=torch.bool, device=dev)
+    tok = torch.empty(b, dtype=torch.long, device=dev)
+    for t in range(max_len):
+        logits = sess.step(None if t == 0 else tok)
+        seed, off = stream.take(b, logits.shape[1])
+        K.sample_tokens(logits, seed, off, EOS, unfinished, tok, sents[:, t], logprobs[:, t])
+        if t % 8 == 7 and t + 1 < max_len and not bool(unfinished.any()):
+            break
+    return sents, logprobs
+
+
+def decode_sample(step, b, max_len, stream):
+    """decode_sample_cached on the re-run path (_Stepper: VALOR_KV_CACHE=0, a cross-attention block per modality); the same draws"""
+    dev = step.m.device
+    sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
+    logprobs = torch.zeros((b, max_len), device=dev)
+    unfinished = torch.ones(b, dtype=torch.bool, device=dev)
+    tok = torch.empty(b, dtype=torch.long, device=dev)
+    state = None
+    for t in range(max_len):
+        logits = step.logits(state, b).contiguous()
+        seed, off = stream.take(b, logits.shape[1])
+        K.sample_tokens(logits, seed, off, EOS, unfinished, tok, sents[:, t], logprobs[:, t])
+        w_host = tok.cpu().unsqueeze(1)
+        state = w_host if state is None else torch.cat((state, w_host), dim=1)
+        if not bool(unfinished.any()):
+            break
+    return sents, logprobs
+
+
+def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None):
+    """{group: (sequences, logprobs | None)} for the query groups present, through the K|V-cached session or the re-run path.
+    stream: a SampleStream (after begin_call) -> sampled decoding (beam 1)"""
     if isinstance(prompt, str):
         prompt = model.get_task_prompt(PROMPTS[prompt], b) if model.use_task_prompt else None
+    if stream is not None:
+        beam = 1
     out = {}
     sess = None
     if kv_cache_enabled() and not isinstance(kv_layers, _BlockKV):      # (a block per modality, bert.py:459-496: the re-run path)
@@ -475,10 +551,16 @@ def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len):
             continue
         if sess is not None:
             sess.begin_group(ranges[g] if kv_layers is not None else None, prompt)
-            out[g] = (decode_beam_cached(sess, b, beam, max_len), None) if beam > 1 else decode_greedy_cached(sess, b, max_len)
+            if stream is not None:
+                out[g] = decode_sample_cached(sess, b, max_len, stream)
+            else:
+                out[g] = (decode_beam_cached(sess, b, beam, max_len), None) if beam > 1 else decode_greedy_cached(sess, b, max_len)
         else:
             step = _Stepper(model, g, kv_layers, ranges, prompt, b)
-            out[g] = (decode_beam(step, b, beam, max_len), None) if beam > 1 else decode_greedy(step, b, max_len)
+            if stream is not None:
+                out[g] = decode_sample(step, b, max_len, stream)
+            else:
+                out[g] = (decode_beam(step, b, beam, max_len), None) if beam > 1 else decode_greedy(step, b, max_len)
     return out
 
 
@@ -501,17 +583,29 @@ def stepper(model, group, b, kv_layers, ranges, prompt="caption"):
     return _Stepper(model, group, kv_layers, ranges, prompt, b)
 
 
+def _sample_stream(model, seed):
+    return (sampler_of(model) if seed is None else SampleStream(seed)).begin_call()
+
+
 @torch.no_grad()
-def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None):
-    """VALOR.generate_cap, model/pretrain.py:914-985 -> {'generated_sequences_t_v' | '_t_va' | '_t_a' (+ 'logprobs_*' when greedy)}."""
+def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, mode=None, seed=None):
+    """VALOR.generate_cap, model/pretrain.py:914-985 -> {'generated_sequences_t_v' | '_t_va' | '_t_a' (+ 'logprobs_*' when greedy or
+    sampled)}. mode: None (beam search when beam_size > 1, else greedy), 'greedy' (whatever beam_size says) or 'sample' (decode_greedy's
+    sample mode, :1007-1011: a draw from softmax(logits) per step, logprobs_* = the logP of the draws). seed: the sampled draws' seed
+    (None: the model's own SampleStream, seeded from opts.seed, advances one call)."""
+    if mode not in (None, "greedy", "sample"):
+        raise ValueError(f"generate_cap: mode {mode!r} (None, 'greedy' or 'sample')")
     beam = model.beam_size if beam_size is None else beam_size
+    if mode is not None:
+        beam = 1
     max_len = model.max_generation_len if max_generation_len is None else max_generation_len
     was_training = model.training
     model.eval()
     try:
         b, kv_layers, ranges = encode_for_generation(model, batch, groups)
         out = {}
-        for g, (seq, lp) in _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len).items():
+        stream = _sample_stream(model, seed) if mode == "sample" else None
+        for g, (seq, lp) in _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, stream).items():
             key = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]
             out["generated_sequences_" + key] = seq
             if lp is not None:

@@ -541,3 +541,17 @@ def masked_rows(labels, row_off, n, G=1, Ttot=None, r0=0, idx=None, lab_out=None
     lib.call("valor_masked_rows", _stream(), _ptr(labels), _ptr(row_off), b, T, G, T if Ttot is None else int(Ttot), int(r0), int(n),
              _ptr(idx), _ptr(lab_out))
     return idx, lab_out
+
+
+def sample_tokens(logits, seed, offset, eos, unfinished, tok, sents, logprobs):
+    """one step of the sampled decode (valor_sample_tokens): logits fp32 [R, V] (row pitch = stride(0)), unfinished bool [R] (updated in
+    place), tok int64 [R] (written: the next input token), sents int64 / logprobs fp32 column views [R] (e.g. sents[:, t]). The caller
+    advances `offset` by R * ceil(V / 4) per call."""
+    _check_gpu(logits, unfinished, tok, sents, logprobs)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert unfinished.dtype == torch.bool and unfinished.is_contiguous() and tok.dtype == torch.int64 and tok.is_contiguous()
+    assert sents.dtype == torch.int64 and logprobs.dtype == torch.float32 and sents.dim() == logprobs.dim() == 1
+    R, V = logits.shape
+    assert unfinished.numel() == tok.numel() == sents.numel() == logprobs.numel() == R
+    lib.call("valor_sample_tokens", _stream(), _ptr(logits), logits.stride(0), R, V, int(seed), int(offset), int(eos), _ptr(unfinished), _ptr(tok),
+             _ptr(sents), sents.stride(0), _ptr(logprobs), logprobs.stride(0))

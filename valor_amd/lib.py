@@ -136,6 +136,9 @@ SIGNATURES = {
     "valor_masked_rows": [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _vp, _vp],
     "valor_dact_mul": [_vp, _i, _vp, _vp, _vp, _i64, _i],
     "valor_mean_f32": [_vp, _vp, _i64, _vp],
+    "valor_xent_weighted_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _i64, _i, _i64],
+    "valor_weighted_mean_f32": [_vp, _vp, _vp, _i64, _vp],
+    "valor_sample_tokens": [_vp, _vp, _i64, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _i64, _vp, _i64],
     "valor_rowdot_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i],
     "valor_rowdot_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i],
     "valor_colsum": [_vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _i, _i],

@@ -266,6 +266,11 @@ class VALOR(nn.Module):
             # loudly instead of dropping the flag silently.
             raise NotImplementedError("full_masker with caption_type='lm' is not supported (no shipped configuration combines them)")
         self._full_attn = False           # full_masker attention / positions for the decoder passes being issued (forward_cap / forward_qa)
+        # self-critical caption finetuning (train_utils.py:655, forward_cap_scst pretrain.py:741-791): forward_cap(compute_loss=True) trains
+        # the reward-weighted loss of sampled captions against a greedy baseline; the reward scorer is attached as model.scorer (train.py:63-68)
+        self.scst_finetuning = bool(_opt(opts, "scst_finetuning", False))
+        self.scorer = None
+        self._dec_nodrop = False          # decoder dropout off for the passes being issued (the SCST sample and loss passes)
         if _opt(opts, "fineweight_type", "one") == "none":
             raise NotImplementedError("fineweight_type='none' is a TypeError in the reference too (pretrain.py:330)")
         self.spec = spec
@@ -855,10 +860,14 @@ class VALOR(nn.Module):
         else:
             x = ops.embed(ids_dev, P[e + "word_embeddings.weight"], P[e + "position_embeddings.weight"], tv, L)
         x = ops.layer_norm(x, P[e + "LayerNorm.weight"], P[e + "LayerNorm.bias"], 1e-12)
-        p = self.p_drop if self.training else 0.0
+        p = self._dec_p()
         if p > 0:
             x = ops.bias_dropout_residual(x, None, None, p)
         return x
+
+    def _dec_p(self):
+        """dropout probability of the multimodal BERT's passes being issued: p_drop in training, 0 in eval or under _decoder_dropout_off"""
+        return self.p_drop if self.training and not self._dec_nodrop else 0.0
 
     def project_cross_kv(self, va_input):
         """K|V of the concatenated [video | audio] tokens, ONCE per decoder layer (shared by every pass). The 12 projections
@@ -988,7 +997,7 @@ class VALOR(nn.Module):
         """BertEncoder / BertLayer.forward bert.py:440-518 (post-LN; va_concate cross-attention).
         self_attn (generation with a K|V cache, valor_amd/decode.py): callable (layer, qkv [B, T, 3E]) -> attention output [B, T, E] that
         stands in for the self-attention over the T rows alone."""
-        P, H, p = self.P, self.spec.heads, (self.p_drop if self.training else 0.0)
+        P, H, p = self.P, self.spec.heads, self._dec_p()
         for i in range(self.spec.layers):
             q = f"multimodal_encoder.encoder.layer.{i}."
             qkv = ops.linear(x, P[q + "attention.self.qkv.weight"], P[q + "attention.self.qkv.bias"])
@@ -1036,8 +1045,9 @@ class VALOR(nn.Module):
         return ops.layer_norm(h, P["cls.layernorm.weight"], P["cls.layernorm.bias"], 1e-12)
 
     def _decoder_groups(self, txt_input, txt_labels, groups, prompt_cpu, casual, kv_layers, ranges, b, compute_loss, tag, out, per_sample=False,
-                        kv_b=None):
-        """Run the decoder for len(groups) query groups as ONE batch (same text input, different K/V rows)."""
+                        kv_b=None, row_weights=None):
+        """Run the decoder for len(groups) query groups as ONE batch (same text input, different K/V rows). row_weights: fp32 device [n]
+        per labelled row (one group): the reward-weighted loss (SCST) instead of the mean CE."""
         blocks = isinstance(kv_layers, _BlockKV)
         if blocks and len(groups) > 1:
             # a block per modality: the groups differ in which blocks a layer runs (bert.py:459-496), so they cannot share a batch
@@ -1086,6 +1096,8 @@ class VALOR(nn.Module):
             losses = ops.decoder_xent_segments(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], P["cls.decoder.bias"], labels,
                                                [counts[r] for r in rows] * G)
             return torch.stack(losses).view(G, len(rows)), rows
+        if compute_loss and row_weights is not None:
+            return self._weighted_loss(h, labels, [n], row_weights)[0]
         if compute_loss:
             # equal row counts per group: the mean over all G*n rows == mean of the per-group means (pretrain.py:473-479)
             return ops.decoder_xent(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], P["cls.decoder.bias"], labels,
@@ -1095,10 +1107,20 @@ class VALOR(nn.Module):
             out[f"{tag}_scores_{g}"] = scores[gi * n:(gi + 1) * n]
         return None
 
-    def _decoder_layer(self, i, X, kv, ssegs, xsegs, dkv):
-        """one BertLayer (bert.py:440-496) on the row-batched stack of every decoder pass"""
+    def _weighted_loss(self, h, labels, seg_rows, row_weights):
+        P = self.P
+        rows_out = [] if self.collect is not None else None
+        losses = ops.decoder_xent_weighted_segments(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], P["cls.decoder.bias"], labels,
+                                                    seg_rows, row_weights, loss_rows_out=rows_out)
+        if rows_out is not None:
+            self.collect.setdefault("scst_loss_rows", []).append(rows_out[0])
+        return losses
+
+    def _decoder_layer(self, i, X, kv, ssegs, xsegs, dkv, p=None):
+        """one BertLayer (bert.py:440-496) on the row-batched stack of every decoder pass (p: its dropout, default _dec_p())"""
         P, H = self.P, self.spec.heads
-        p = self.p_drop if self.training else 0.0
+        if p is None:
+            p = self._dec_p()
         q = f"multimodal_encoder.encoder.layer.{i}."
         # post-LN: every sub-layer input feeds the sub-layer's first GEMM AND the residual add behind it; the two gradients meet in a
         # GradSlot (the LayerNorm backward publishes its residual gradient, the GEMM's dgrad accumulates into it: no add kernels)
@@ -1133,12 +1155,13 @@ class VALOR(nn.Module):
             X = self._decoder_layer(i, X, kv_layers[i], ssegs, xsegs, dkv)
         return X
 
-    def _decoder_fused(self, passes, kv_layers, ranges, b):
+    def _decoder_fused(self, passes, kv_layers, ranges, b, row_weights=None):
         """Training path: ALL decoder passes (caption groups, every mlm group) as one row-batched stack -- every GEMM /
         LayerNorm of a BertLayer (bert.py:440-496) runs once on the concatenated rows; self- and cross-attention run per
-        pass on row segments. passes = [(tag, txt_input, txt_labels, groups, prompt_cpu, casual)]. Returns {tag: [loss]}."""
+        pass on row segments. passes = [(tag, txt_input, txt_labels, groups, prompt_cpu, casual)]. Returns {tag: [loss]}.
+        row_weights: fp32 device [all labelled rows, in pass order]: the reward-weighted loss per pass (SCST) instead of the mean CE."""
         P, H, E = self.P, self.spec.heads, self.spec.hidden
-        p = self.p_drop if self.training else 0.0
+        p = self._dec_p()
         xs, ssegs, xsegs, idxs, labs, seg_rows, r0 = [], [], [], [], [], [], 0
         dev_passes = []             # token_masker='device': (slot in idxs, labels, G, Ttot, r0) -- valor_masked_rows writes those slices
         for (tag, txt_input, txt_labels, groups, prompt_cpu, casual) in passes:
@@ -1181,7 +1204,7 @@ class VALOR(nn.Module):
                 seg = self._graph_segs["decoder"] = graphs.GraphedSegment("decoder", self._decoder_stack)
             self._dec_meta = ([(r0_, Bp_, Tt_) for (r0_, Bp_, Tt_, _m) in ssegs], [(r0_, Bp_, Tt_, b_) for (r0_, Bp_, Tt_, _k, b_) in xsegs])
             X = seg(X, kv_layers.va, *[m for (_a, _b, _c, m) in ssegs], *[k for (_a, _b, _c, k, _d) in xsegs],
-                    key_extra=(tuple(self._dec_meta[0]), tuple(self._dec_meta[1])))
+                    key_extra=(tuple(self._dec_meta[0]), tuple(self._dec_meta[1])) + ((("p", p),) if p != (self.p_drop if self.training else 0.0) else ()))
         else:
             dkv = getattr(self, "_dkv_static", None)
             # bert.py:510-513: with `checkpointing` every BertLayer keeps its input rows (and the layer's projected K|V, which lives in a
@@ -1190,11 +1213,11 @@ class VALOR(nn.Module):
             for i in range(self.spec.layers):
                 kv = kv_layers[i] if kv_layers is not None else None
                 if not ckpt:
-                    X = self._decoder_layer(i, X, kv, ssegs, xsegs, dkv)
+                    X = self._decoder_layer(i, X, kv, ssegs, xsegs, dkv, p)
                 elif kv is None:
-                    X = ops.checkpoint(lambda X_, i=i: self._decoder_layer(i, X_, None, ssegs, xsegs, dkv), X)
+                    X = ops.checkpoint(lambda X_, i=i: self._decoder_layer(i, X_, None, ssegs, xsegs, dkv, p), X)
                 else:
-                    X = ops.checkpoint(lambda X_, kv_, i=i: self._decoder_layer(i, X_, kv_, ssegs, xsegs, dkv), X, kv)
+                    X = ops.checkpoint(lambda X_, kv_, i=i: self._decoder_layer(i, X_, kv_, ssegs, xsegs, dkv, p), X, kv)
         if dev_passes:
             # one index and one label buffer for all passes; each device-masked pass writes its slice in place, a host-labelled one (caption
             # type 'lm' beside a device-masked mlm) is uploaded into its slice
@@ -1214,8 +1237,11 @@ class VALOR(nn.Module):
         h = self.cls_transform(rows)
         if lab_all is None:
             lab_all = self._dev(torch.cat(labs))
-        losses = ops.decoder_xent_segments(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], P["cls.decoder.bias"],
-                                           lab_all, seg_rows, smoothing=self._smoothing)
+        if row_weights is not None:
+            losses = self._weighted_loss(h, lab_all, seg_rows, row_weights)
+        else:
+            losses = ops.decoder_xent_segments(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], P["cls.decoder.bias"],
+                                               lab_all, seg_rows, smoothing=self._smoothing)
         res = {}
         for (tag, *_), l in zip(passes, losses):
             res.setdefault(tag, []).append(l)
@@ -1261,6 +1287,8 @@ class VALOR(nn.Module):
         scst / full_masker -- the shipped settings). Loss: forward_cap_single :802-880 = the caption passes of forward_pt. Otherwise
         generate_cap :914-985 -> valor_amd.decode (greedy for beam_size 1, beam search above)."""
         groups = task.split("%")[1:]
+        if compute_loss and self.scst_finetuning:
+            return self.forward_cap_scst(batch, groups)
         if compute_loss:
             self._smoothing, self._full_attn = self.label_smoothing, self.full_masker      # pretrain.py:835-860: forward_cap_single passes full_masker
             try:
@@ -1322,6 +1350,149 @@ class VALOR(nn.Module):
             return {"qa_loss": L.mean()}                            # mean over samples, mean over groups (:1290,1338-1343)
         return {"qa_loss": ((L * self._dev(weights)).sum(dim=1) / b).mean()}      # weighted rows summed over the QUESTION count (:1288-1289)
 
+    def _step_prologue(self):
+        """the top of a training / evaluation forward: staging ring, main stream, dropout windows"""
+        self.stage.begin_step()
+        if self.device.type == "cuda":
+            streams.set_main(self.device)
+            if torch.is_grad_enabled():
+                ops.K.ReduceQueue.discard_stale()    # leftovers of a backward pass that died half way (kernels.ReduceQueue)
+            if self._use_graphs():
+                # the graphed segments key their captures on the by-value dropout offset at their entry, which only repeats if the step's
+                # driver restarts it (TrainEngine.train_step does): a custom loop that never calls begin_step() gets it from here
+                if not ops.DropoutState.begun:
+                    ops.DropoutState.begin_step()
+                ops.DropoutState.begun = False
+
+    # ------------------------------------------------------------------ self-critical sequence training (SCST)
+    def forward_cap_scst(self, batch, groups):
+        """VALOR.forward_cap_scst, model/pretrain.py:741-791, as the code intends (its own sample pass is greedy and has no gradient; see
+        DESIGN 1). Per query group g of 'cap%..':
+          1. baseline: greedy decoding (whatever beam_size says) with the encoders in eval mode, no grad;
+          2. sample: the encoders ONCE in train mode with autograd; from their K|V (detached) one draw per clip through the cached decoding
+             session (valor_amd.decode.decode_sample_cached), no grad;
+          3. reward r = scorer(ids, sample) - scorer(ids, greedy) (alpha_type 0: alpha = 1, :1461-1507), hypotheses cut at the first [SEP];
+          4. loss: ONE teacher-forced decoder pass over the sampled sequences on the same encoder outputs, with grad, decoder dropout off:
+             caption_loss_<g> = reward_loss (:166-173) = mean over the positions up to and including the first [SEP] of -r_i logP."""
+        if self.scorer is None:
+            raise ValueError("scst_finetuning needs a reward scorer: attach one as model.scorer (valor_amd.scst.CaptionScorer, train.py:63-68)")
+        if "ids" not in batch:
+            raise ValueError("scst_finetuning: the batch carries no clip 'ids' for the reward scorer")
+        from .. import scst
+        groups = [g for g in ("tva", "tv", "ta") if g in groups]
+        ids = list(batch["ids"])
+        greedy = self.scst_baseline(batch, groups)
+        video_output, audio_output = self.scst_encode(batch, groups)
+        samples = self.scst_sample(video_output, audio_output, groups)
+        rewards = {}
+        for g in groups:
+            r_s = self.scorer(ids, scst.hypotheses(samples[g][0].cpu(), self.eos_token))
+            r_g = self.scorer(ids, scst.hypotheses(greedy[g], self.eos_token))
+            rewards[g] = r_s - r_g
+        if self.collect is not None:
+            self.collect.update(scst_greedy=greedy, scst_samples=samples, scst_rewards=rewards)
+        return self.scst_loss(video_output, audio_output, {g: samples[g][0] for g in groups}, rewards)
+
+    def scst_baseline(self, batch, groups):
+        """the self-critical baseline: greedy captions, encoders in eval mode, no grad -> {group: host int64 [b, L]}. The eval switch is
+        local (nn.Module.train, not VALOR.train: the training step's static K|V buffers and graphs stay)."""
+        from .. import decode
+        was = self.training
+        nn.Module.train(self, False)
+        try:
+            with torch.no_grad():
+                b, kv_layers, ranges = decode.encode_for_generation(self, batch, groups)
+                res = decode._decode_groups(self, groups, b, kv_layers, ranges, "caption", 1, self.max_generation_len)
+                return {g: seq.cpu() for g, (seq, _lp) in res.items()}
+        finally:
+            nn.Module.train(self, was)
+
+    def scst_encode(self, batch, groups):
+        """the encoders of the SCST step, once, in the model's mode and with autograd (the sample pass backpropagates into them)"""
+        self._step_prologue()
+        alltasks = "".join(groups)
+        video_output = self.forward_video_encoder(batch["video_pixels"]) if "v" in alltasks else None
+        audio_output = self.forward_audio_encoder(batch["audio_spectrograms"]) if "a" in alltasks else None
+        return video_output, audio_output
+
+    def scst_sample(self, video_output, audio_output, groups, seed=None):
+        """one sampled caption per clip and group from the encoder outputs (detached), decoder dropout off, no grad ->
+        {group: (sents int64 [b, L], logprobs fp32 [b, L]) on the device}. seed: None = the model's SampleStream"""
+        from .. import decode
+        stream = decode._sample_stream(self, seed)
+        det = lambda t: None if t is None else t.detach()
+        with torch.no_grad(), self._decoder_dropout_off():
+            kv_layers, ranges = self.cross_inputs(det(video_output), det(audio_output))
+            b = (video_output if video_output is not None else audio_output).shape[0]
+            return decode._decode_groups(self, groups, b, kv_layers, ranges, "caption", 1, self.max_generation_len, stream)
+
+    def scst_inputs(self, seq):
+        """the teacher-forced decoder input of sampled sequences seq (host int64 [b, L]) -> (tokens, labels) host [b, T]:
+        'unimlm' = the two-stream full-masker layout [CLS, w_0 .. w_{L-1} | L + 1 x [MASK]] (bert.py:197-201,872-878): [MASK] j sits at
+        position j + 1 and sees [CLS, w_0 .. w_{j-1}] and itself -- what decoding step j saw -- and predicts w_j; 'lm' = [CLS, w_0 ..
+        w_{L-1}], position j predicts w_j. Labels: every position up to and including the first [SEP] (reward_loss's mask, :167-168),
+        a sampled id 0 included."""
+        seq = seq.long()
+        b, L = seq.shape
+        keep = torch.ones((b, L), dtype=torch.bool)
+        keep[:, 1:] = seq[:, :-1] != self.eos_token
+        lab = torch.where(keep, seq, torch.full_like(seq, -1))
+        txt = torch.cat((torch.full((b, 1), self.bos_token, dtype=torch.long), seq), dim=1)
+        if self.caption_type == "unimlm":
+            tokens = torch.cat((txt, torch.full_like(txt, self.text_mask_token)), dim=1)
+            labels = torch.full_like(tokens, -1)
+            labels[:, L + 1:2 * L + 1] = lab
+        else:
+            tokens = txt
+            labels = torch.full_like(tokens, -1)
+            labels[:, :L] = lab
+        return tokens, labels
+
+    def scst_loss(self, video_output, audio_output, seqs, rewards):
+        """the SCST loss pass: seqs {group: int64 [b, L] (device or host)}, rewards {group: [b] (numpy / tensor)} -> {'caption_loss_<g>':
+        reward_loss}. One teacher-forced pass per group on the shared encoder outputs, row-batched into one decoder stack, with grad;
+        decoder dropout off; the two-stream layout whatever full_masker says."""
+        groups = [g for g in ("tva", "tv", "ta") if g in seqs]
+        b = (video_output if video_output is not None else audio_output).shape[0]
+        kv_layers, ranges = self.cross_inputs(video_output, audio_output, defer_kv=True)
+        prompt = self.get_task_prompt(PROMPTS["caption"], b) if self.use_task_prompt else None
+        passes, weights = [], []
+        for g in groups:
+            tokens, labels = self.scst_inputs(seqs[g].cpu())
+            passes.append(("caption_" + g, tokens, labels, [g], prompt, True))
+            r = torch.as_tensor(np.asarray(rewards[g], dtype=np.float32))
+            weights.append(r[(labels != -1).nonzero(as_tuple=True)[0]])       # one weight per labelled row, in nonzero() order
+        w_all = self._dev(torch.cat(weights))
+        saved = self._smoothing, self._full_attn
+        self._smoothing, self._full_attn = 0.0, self.caption_type == "unimlm"
+        try:
+            with self._decoder_dropout_off():
+                if isinstance(kv_layers, _BlockKV):
+                    out, r0 = {}, 0
+                    for (tag, tin, tlab, gs, pr, casual), w in zip(passes, weights):
+                        n = w.numel()
+                        out[tag] = [self._decoder_groups(tin, tlab, gs, pr, casual, kv_layers, ranges, b, True, tag, {}, row_weights=w_all[r0:r0 + n])]
+                        r0 += n
+                    res = out
+                else:
+                    res = self._decoder_fused(passes, kv_layers, ranges, b, row_weights=w_all)
+        finally:
+            self._smoothing, self._full_attn = saved
+        return {"caption_loss_" + g: res["caption_" + g][0] for g in groups}
+
+    def _decoder_dropout_off(self):
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            saved = self._dec_nodrop
+            self._dec_nodrop = True
+            try:
+                yield
+            finally:
+                self._dec_nodrop = saved
+        return ctx()
+
     def forward_pt(self, batch, task, compute_loss=True):
         """VALOR.forward_pt, model/pretrain.py:214-541."""
         mlm_task, caption_task, contra_task = [], [], []
@@ -1362,17 +1533,7 @@ class VALOR(nn.Module):
     def _forward_groups(self, batch, mlm_task, caption_task, contra_task, compute_loss, contra_ratio=1.0):
         """The body of VALOR.forward_pt (model/pretrain.py:226-541) on parsed group lists; forward_ret / forward_cap run it with one branch."""
         P, sp = self.P, self.spec
-        self.stage.begin_step()
-        if self.device.type == "cuda":
-            streams.set_main(self.device)
-            if torch.is_grad_enabled():
-                ops.K.ReduceQueue.discard_stale()    # leftovers of a backward pass that died half way (kernels.ReduceQueue)
-            if self._use_graphs():
-                # the graphed segments key their captures on the by-value dropout offset at their entry, which only repeats if the step's
-                # driver restarts it (TrainEngine.train_step does): a custom loop that never calls begin_step() gets it from here
-                if not ops.DropoutState.begun:
-                    ops.DropoutState.begin_step()
-                ops.DropoutState.begun = False
+        self._step_prologue()
         out = {}
         col = self.collect
         txt_tokens = batch.get("txt_tokens")

@@ -754,6 +754,71 @@ def decoder_xent_segments(h, w_emb, dec_bias, labels, seg_rows, smoothing=0.0):
     return DecoderXentSegFn.apply(h, w_emb, dec_bias, labels, seg_rows, smoothing)
 
 
+class DecoderXentWeightedSegFn(Function):
+    """DecoderXentSegFn with a weight per row: segment i's loss is sum_r w_rows[r] * CE_r / n_i over its rows -- SCST's reward_loss
+    (pretrain.py:166-173: mean over the labelled positions of -reward * logP, the reward of the row's sequence). Forward
+    valor_weighted_mean_f32, backward valor_xent_weighted_bwd: dlogits = (softmax - onehot) * w_r * g / n_i. No label smoothing (the
+    reference's reward loss has none). w_rows: fp32 [n] on the device (no gradient). Outputs: the segment losses, then the per-row CE
+    (fp32 [n] = -logP of each label, non-differentiable)."""
+
+    @staticmethod
+    def forward(ctx, h, w_emb, dec_bias, labels, seg_rows, w_rows):
+        n, V = h.shape[0], w_emb.shape[0]
+        Vpad = (V + 31) // 32 * 32
+        buf = _rows_with_slack(n, Vpad, h.dtype, h.device)
+        K.gemm(h, w_emb, bias=dec_bias, out=buf[:, :V])
+        loss_rows = torch.empty(n, dtype=torch.float32, device=h.device)
+        lse = torch.empty(n, dtype=torch.float32, device=h.device)
+        lib.call("valor_xent_fwd", _st(), _dt(h), _p(buf), _p(labels), _p(loss_rows), _p(lse), n, V, Vpad)
+        losses, r0 = [], 0
+        for nr in seg_rows:
+            l = torch.empty((), dtype=torch.float32, device=h.device)
+            lib.call("valor_weighted_mean_f32", _st(), _p(loss_rows[r0:r0 + nr]), _p(w_rows[r0:r0 + nr]), nr, _p(l))
+            losses.append(l); r0 += nr
+        ctx.save_for_backward(h, w_emb, labels, lse, buf, w_rows)
+        ctx.V, ctx.seg_rows = V, tuple(seg_rows)
+        ctx.params = (w_emb, dec_bias)
+        ctx.mark_non_differentiable(loss_rows)
+        return tuple(losses) + (loss_rows,)
+
+    @staticmethod
+    def backward(ctx, *dlosses):
+        h, w_emb, labels, lse, buf, w_rows = ctx.saved_tensors
+        V, Vpad = ctx.V, buf.shape[1]
+        r0 = 0
+        for nr, dl in zip(ctx.seg_rows, dlosses[:len(ctx.seg_rows)]):        # (the last output, the per-row CE, has no gradient)
+            g = dl.to(torch.float32).contiguous() if dl is not None else torch.zeros((), dtype=torch.float32, device=h.device)
+            lib.call("valor_xent_weighted_bwd", _st(), _dt(h), _p(buf[r0:r0 + nr]), _p(labels[r0:r0 + nr]), _p(lse[r0:r0 + nr]),
+                     _p(w_rows[r0:r0 + nr]), _p(g), 1.0 / nr, nr, V, Vpad)
+            r0 += nr
+        dlog = buf[:, :V]
+        dh = K.gemm(dlog, w_emb, trans_b=True)
+        pw, pb = ctx.params
+        sw, sb = _sink(pw), _sink(pb)
+        dw = db = None
+        if not ctx.needs_input_grad[1]:
+            pass
+        elif sw is not None:
+            K.gemm(dlog, h, trans_a=True, trans_b=True, out=sw, accumulate=True, defer_done=lambda: _sunk(pw))
+        else:
+            dw = K.gemm(dlog, h, trans_a=True, trans_b=True)
+        if not ctx.needs_input_grad[2]:
+            pass
+        elif sb is not None:
+            K.colsum(dlog, out=sb, accumulate=True); _sunk(pb)
+        else:
+            db = K.colsum(dlog)
+        return dh, dw, db, None, None, None
+
+
+def decoder_xent_weighted_segments(h, w_emb, dec_bias, labels, seg_rows, w_rows, loss_rows_out=None):
+    """per-segment reward-weighted CE (DecoderXentWeightedSegFn); loss_rows_out: a list that receives the per-row -logP tensor"""
+    *losses, rows = DecoderXentWeightedSegFn.apply(h, w_emb, dec_bias, labels, seg_rows, w_rows)
+    if loss_rows_out is not None:
+        loss_rows_out.append(rows)
+    return tuple(losses)
+
+
 # ------------------------------------------------------------------------------------------------
 class DecoderXentFn(Function):
     """loss = mean CE(h W_emb^T + b, labels): tied-decoder GEMM (modeling.py:253, weight = word embeddings
