@@ -374,6 +374,32 @@ int valor_fine_weight_grad(void* stream, const float* dscore, const float* A2B, 
                            int Nv);
 int valor_fine_set_fused(int v);
 
+/* ---- retrieval evaluation: the rank of every ground truth in a score matrix, without a sort (csrc/retrieval.hip). Replaces
+ * compute_dualsoftmax_forward / _backward and the sort + tolist + list.index of compute_metric_ret (test.py:685-775).
+ *   score fp32 [Nt, ld] (ld >= Nv): rows = texts (the A side), columns = clips (the B side). gt_col int32 [Nt]: the column of each
+ *   text's clip. col_ptr int32 [Nv + 1], col_rows int32 [nnz]: the texts of every clip as a CSR list (col_rows[col_ptr[j] ..
+ *   col_ptr[j + 1]) = the rows i whose clip is column j; nnz = Nt unless two columns carry the same clip id and share their texts,
+ *   test.py:746-748); read only when rank_b is given, entries outside [0, nnz) / [0, Nt) are skipped.
+ *   dual != 0 (the reference's dual_softmax): lse_col[j] = logsumexp_i(score[i,j] * inv_temp) and lse_row[i] = logsumexp_j(...) are
+ *   computed (and WRITTEN to lse_col fp32 [Nv] / lse_row fp32 [Nt], natural log, where the pointer is not NULL) and
+ *     x[i,j] = score[i,j] * exp(score[i,j] * inv_temp - lse_col[j]) * Nt     (test.py:694, softmax over dim 0 times len(score))
+ *     y[i,j] = score[i,j] * exp(score[i,j] * inv_temp - lse_row[i]) * Nv     (test.py:710)
+ *   otherwise x = y = score and inv_temp / lse_* are ignored.
+ *   rank_f int32 [Nt]: rank_f[i] = #{j : x[i,j] > x[i,g]} + #{j < g : x[i,j] == x[i,g]}, g = gt_col[i]; -1 if g is outside [0, Nv).
+ *   rank_b int32 [Nv] (NULL = forward only): with m_j = max{y[i,j] : gt_col[i] == j} and i* the lowest such i that reaches it,
+ *   rank_b[j] = #{i : y[i,j] > m_j} + #{i < i* : y[i,j] == m_j} = the minimum over the clip's texts of their position in the column
+ *   (test.py:743-750); -1 for a clip without a text.
+ *   TIE RULE: equal values rank in index order, i.e. the position in a STABLE descending sort. torch.sort(descending=True) without
+ *   stable=True, which the reference calls, leaves the order of equal values undefined; this is the one deterministic choice.
+ *   A NaN compares as not greater (a NaN ground truth therefore gets rank 0): no rank leaves [0, Nv) / [0, Nt).
+ *   workspace: valor_retrieval_workspace_bytes() bytes, 16-byte aligned (column partials of the reductions; no [Nt, Nv] temporary, no
+ *   float atomics). Passes over the matrix: 1 without dual, 2 with it. 16-byte loads when ld % 4 == 0 and score is 16-byte aligned.
+ *   Nt == 0 or Nv == 0: no-op. VALOR_ERR_ARG on a null / misaligned pointer, ld < Nv, a short workspace, dual with inv_temp <= 0. */
+int valor_retrieval_workspace_bytes(int Nt, int Nv, int64_t* bytes);
+int valor_retrieval_ranks(void* stream, const float* score, int64_t ld, const int* gt_col, const int* col_ptr, const int* col_rows,
+                          int nnz, float inv_temp, int dual, float* lse_row, float* lse_col, int* rank_f, int* rank_b, void* workspace,
+                          int64_t workspace_bytes, int Nt, int Nv);
+
 /* ---- fused multi-tensor AdamW + global-norm clip over flat arenas.  Replaces optim/adamw.py:40-103, optim/misc.py:66-77
  * (10 param groups), torch clip_grad_norm_ (train_utils.py:358-360) and apex-amp's master<->model copies
  * (apex/apex/amp/_process_optimizer.py:14-22). n % valor_adamw_chunk() == 0; chunk_group: int8 [n/chunk], -1 = skip. */

@@ -154,3 +154,217 @@ def validate_pt(model, loader, task):
         if "ta" in contra_task:
             val_log["t2a_recall"] = compute_metric_ret(compute_fine_matrix(ft, fa, maskA, ones(fa), wt, _fine_weights(model, "audio", fa)).cpu(), ids, ids_txt)["forward_recall"]
     return val_log
+
+
+# ------------------------------------------------------------------ retrieval evaluation (test.py:249-411 validate_ret, :685-775)
+def _gt_columns(ids, ids_txt, text_direction):
+    """gt_col[i] = ids.index(ids_txt[i]) (the first occurrence of a clip id wins) and, for the text direction, the texts of every clip
+    as a CSR list. ValueError where the reference raises: a text whose clip is absent (ids.index), a clip without a text (min([]))."""
+    first = {}
+    for j, clip in enumerate(ids):
+        first.setdefault(clip, j)
+    gt_col = []
+    for i, clip in enumerate(ids_txt):
+        if clip not in first:
+            raise ValueError(f"text {i}: clip id {clip!r} is not in ids")
+        gt_col.append(first[clip])
+    col_ptr = col_rows = None
+    if text_direction:
+        # test.py:746-748 compares ids_txt against ids[i] for EVERY column, so a duplicated clip id shares its texts with its copies
+        by_clip = {}
+        for i, clip in enumerate(ids_txt):
+            by_clip.setdefault(clip, []).append(i)
+        col_ptr, col_rows = [0], []
+        for j, clip in enumerate(ids):
+            rows = by_clip.get(clip)
+            if not rows:
+                raise ValueError(f"clip {j} ({clip!r}) has no text: the text-retrieval direction is undefined for it")
+            col_rows += rows
+            col_ptr.append(len(col_rows))
+    return gt_col, col_ptr, col_rows
+
+
+def _metrics_from_ranks(rank, prefix):
+    """test.py:731-737, 760-774: fp32 ranks -> recall string, ravg, medianR (torch.median: the LOWER middle element), meanR"""
+    n = rank.numel()
+    rank = rank.to(torch.float32)
+    r1, r5, r10 = [(rank < k).sum().item() / n for k in (1, 5, 10)]
+    return {f"{prefix}_recall": f"{round(r1 * 100, 1)}/{round(r5 * 100, 1)}/{round(r10 * 100, 1)}",
+            f"{prefix}_ravg": round((r1 + r5 + r10) / 3 * 100, 1),
+            f"{prefix}_medianR": torch.median(rank).item() + 1,
+            f"{prefix}_meanR": torch.mean(rank).item() + 1}
+
+
+@torch.no_grad()
+def retrieval_ranks(score, gt_col, col_ptr=None, col_rows=None, *, dual_softmax=False, temp=None):
+    """valor_retrieval_ranks on a device fp32 matrix [Nt, Nv] (unit column stride): (rank_f int32 [Nt], rank_b int32 [Nv] or None) on
+    the device; rank_b when the CSR lists are given. No [Nt, Nv] temporary: the workspace holds column partials of 1 / 16 of the matrix."""
+    if score.dtype != torch.float32 or score.dim() != 2:
+        raise ValueError("score: an fp32 [texts, clips] matrix")
+    if score.stride(1) != 1 or score.stride(0) < score.shape[1]:
+        score = score.contiguous()
+    Nt, Nv = score.shape
+    dev = score.device
+    bwd = col_ptr is not None
+    i32 = dict(dtype=torch.int32, device=dev)
+    rank_f = torch.empty((Nt,), **i32)
+    rank_b = torch.empty((Nv,), **i32) if bwd else None
+    if Nt == 0 or Nv == 0:
+        return rank_f, rank_b
+    if dual_softmax and not (temp is not None and temp > 0):
+        raise ValueError("dual_softmax needs the contrastive temperature")
+    to_dev = lambda x: torch.as_tensor(x, dtype=torch.int32).to(dev)
+    gt_col = to_dev(gt_col)
+    if bwd:
+        col_ptr, col_rows = to_dev(col_ptr), to_dev(col_rows)
+    import ctypes
+    nbytes = ctypes.c_int64()
+    lib.call("valor_retrieval_workspace_bytes", Nt, Nv, ctypes.byref(nbytes))
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+    p = lambda t: t.data_ptr() if t is not None else None
+    lib.call("valor_retrieval_ranks", K._stream(), p(score), score.stride(0), p(gt_col), p(col_ptr) if bwd else None, p(col_rows) if bwd else None, int(col_rows.numel()) if bwd else 0,
+             1.0 / temp if dual_softmax else 0.0, int(bool(dual_softmax)), None, None, p(rank_f), p(rank_b), p(ws), nbytes.value, Nt, Nv)
+    return rank_f, rank_b
+
+
+@torch.no_grad()
+def retrieval_metrics(score, ids, ids_txt, *, dual_softmax=False, temp=None, text_direction=False):
+    """compute_metric_ret of test.py:714-775 with its two options (dual_softmax, evaluate_ret_text) on a DEVICE score matrix
+    [len(ids_txt), len(ids)]: the ranks are counted on the device (valor_retrieval_ranks; ties in index order, the stable sort the
+    reference leaves undefined), and only the two int32 rank vectors come back. Returns the reference's eval_log: forward_recall /
+    _ravg / _medianR / _meanR and, with text_direction, the four backward_* keys."""
+    if tuple(score.shape) != (len(ids_txt), len(ids)):
+        raise ValueError(f"score matrix {tuple(score.shape)} against {len(ids_txt)} texts x {len(ids)} clips (test.py:720)")
+    gt_col, col_ptr, col_rows = _gt_columns(ids, ids_txt, text_direction)
+    rank_f, rank_b = retrieval_ranks(score, gt_col, col_ptr, col_rows, dual_softmax=dual_softmax, temp=temp)
+    log = _metrics_from_ranks(rank_f.cpu(), "forward")
+    if text_direction:
+        log.update(_metrics_from_ranks(rank_b.cpu(), "backward"))
+    return log
+
+
+_FUSED_BYTES = 0x7f000000          # valor_fine_fused_fwd addresses each feature tensor with 32-bit byte offsets below this
+
+
+@torch.no_grad()
+def fine_score_matrix(featA, featB, maskA, maskB, weightA, weightB):
+    """The [NA, NB] fine-grained score matrix of an evaluation. bf16 features: valor_fine_fused_fwd in its scores-only mode (the token
+    similarities stay in registers: no fp32 [NA * T, NB * Nv] buffer), in chunks of A rows / B items where a tensor would pass the
+    kernel's byte limit. fp32 features (parity mode): compute_fine_matrix. maskX [N, tokens], weightX raw token weights (softmaxed here)."""
+    if featA.dtype != torch.bfloat16:
+        return compute_fine_matrix(featA, featB, maskA, maskB, weightA, weightB)
+    NA, T, D = featA.shape
+    NB, Nv = featB.shape[:2]
+    if T > 64 or Nv > 64 or D % 64:
+        return compute_fine_matrix(featA, featB, maskA, maskB, weightA, weightB)
+    dev = featA.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    featA, featB = featA.contiguous(), featB.to(torch.bfloat16).contiguous()
+    maskA, maskB = maskA.float().contiguous(), maskB.float().contiguous()
+    st = K._stream()
+    wA, wB = torch.empty((NA, T), **f32), torch.empty((NB, Nv), **f32)
+    lib.call("valor_fine_weight_softmax", st, weightA.float().contiguous().data_ptr(), maskA.data_ptr(), wA.data_ptr(), NA, T)
+    lib.call("valor_fine_weight_softmax", st, weightB.float().contiguous().data_ptr(), maskB.data_ptr(), wB.data_ptr(), NB, Nv)
+    ra = max(1, min(NA, (_FUSED_BYTES - 1) // (T * D * 2)))
+    rb = max(1, min(NB, (_FUSED_BYTES - 1) // (Nv * D * 2)))
+    cols = []
+    for b0 in range(0, NB, rb):
+        nb = min(rb, NB - b0)
+        part = torch.empty((NA, nb), **f32)
+        for a0 in range(0, NA, ra):
+            na = min(ra, NA - a0)
+            lib.call("valor_fine_fused_fwd", st, featA[a0:a0 + na].data_ptr(), featB[b0:b0 + nb].data_ptr(), maskA[a0:a0 + na].data_ptr(),
+                     maskB[b0:b0 + nb].data_ptr(), wA[a0:a0 + na].data_ptr(), wB[b0:b0 + nb].data_ptr(), part[a0:a0 + na].data_ptr(),
+                     None, None, None, None, na, nb, T, Nv, D)
+        cols.append(part)
+    return cols[0] if len(cols) == 1 else torch.cat(cols, dim=1)
+
+
+def retrieval_temperature(model):
+    """test.py:688-691: 1 / exp(logit_scale) for a CLIP video encoder, else contra_temp"""
+    if model.spec.video_encoder == "clip":
+        return float(1.0 / model.P["clip_model.logit_scale"].detach().float().exp())
+    return float(model.P["contra_temp"].detach().float())
+
+
+@torch.no_grad()
+def validate_ret(model, loader, task):
+    """test.py::validate_ret (:249-411): `loader` yields THIS RANK's batches of valor_collate (+ 'ids_txt': several captions per clip);
+    `task` is 'ret%tva%tv...'. Returns the reference's nested val_log: val_log['t_v'] = {video_recall, video_ravg, video_medianR,
+    video_meanR [, txt_*]}, 't_va', 't_a' (audio_* / txt_*), and for contra_type 'fine' also 'v_a', 'v_ta', 'a_tv'. dual_softmax and
+    evaluate_ret_text come from the model's options. The features are gathered across ranks as in validate_pt, and as there every
+    rank returns the full log (the reference fills it on rank 0 only). The score matrices stay on the device; the ranks are counted
+    there (retrieval_metrics). The reference casts the gathered features to fp16 (:281-287); here they keep the model's dtype."""
+    from . import dist as vdist
+    from .model.valor import _opt
+    model.eval()
+    groups = task.split("%")[1:]
+    feats = {"feat_t": [], "feat_v": [], "feat_a": [], "txt_tokens": []}
+    ids, ids_txt = [], []
+    for batch in loader:
+        ev = model(batch, task=task, compute_loss=False)
+        for k in feats:
+            feats[k].append(ev[k])
+        ids += list(batch["ids"])
+        ids_txt += list(batch["ids_txt"] if batch.get("ids_txt") is not None else batch["ids"])
+    if vdist.is_dist():
+        ids = [j for part in vdist.all_gather_list(ids) for j in part]               # test.py:275-276
+        ids_txt = [j for part in vdist.all_gather_list(ids_txt) for j in part]
+        for k in feats:                                                              # test.py:279-290
+            if feats[k] and feats[k][0] is not None:
+                feats[k] = [vdist.ddp_allgather(torch.cat([t.to(model.device) for t in feats[k]], dim=0))]
+    cat = lambda k: torch.cat([t.to(model.device) for t in feats[k]], dim=0).contiguous() if feats[k] and feats[k][0] is not None else None
+    ft, fv, fa, tok = cat("feat_t"), cat("feat_v"), cat("feat_a"), cat("txt_tokens")
+    kw = dict(dual_softmax=bool(_opt(model.opts, "dual_softmax", False)), temp=retrieval_temperature(model),
+              text_direction=bool(_opt(model.opts, "evaluate_ret_text", False)))
+
+    def metric(score, fwd, bwd):
+        log = retrieval_metrics(score, ids, ids_txt, **kw)
+        return {k.replace("forward", fwd).replace("backward", bwd): v for k, v in log.items()}
+
+    val_log = {}
+    if model.spec.contra_type == "coarse":                                           # test.py:383-406
+        sim = lambda a, b: K.gemm(a, b, out_dtype=torch.float32)
+        if "tv" in groups:
+            val_log["t_v"] = metric(sim(ft, fv), "video", "txt")
+        if "tva" in groups:
+            if model.spec.late_fusion:
+                sm = sim(ft, fv) + sim(ft, fa)
+            else:
+                fva = ops.l2_normalize(ops.linear(torch.cat((fv, fa), dim=-1), model.P["va_fusion.weight"], model.P["va_fusion.bias"]))
+                sm = sim(ft, fva)
+            val_log["t_va"] = metric(sm, "video", "txt")
+        if "ta" in groups:
+            val_log["t_a"] = metric(sim(ft, fa), "audio", "txt")
+        return val_log
+    ones = lambda f: torch.ones(f.shape[:2], dtype=torch.float32, device=model.device)
+    mt = (tok != 0).float() if tok is not None else None
+    fw = {}
+
+    def weight(name, f):
+        if name not in fw:
+            fw[name] = _fine_weights(model, name, f)
+        return fw[name]
+
+    if "tv" in groups:                                                               # :296-305
+        val_log["t_v"] = metric(fine_score_matrix(ft, fv, mt, ones(fv), weight("text", ft), weight("video", fv)), "video", "txt")
+    if "tva" in groups:                                                              # :307-334
+        if model.spec.late_fusion:
+            sm = fine_score_matrix(ft, fv, mt, ones(fv), ones(ft), ones(fv)) + fine_score_matrix(ft, fa, mt, ones(fa), ones(ft), ones(fa))
+        else:
+            fva = torch.cat((fv, fa), dim=1)
+            sm = fine_score_matrix(ft, fva, mt, ones(fva), weight("text", ft), torch.cat((weight("video", fv), weight("audio", fa)), dim=1))
+        val_log["t_va"] = metric(sm, "video", "txt")
+    if "ta" in groups:                                                               # :338-346
+        val_log["t_a"] = metric(fine_score_matrix(ft, fa, mt, ones(fa), weight("text", ft), weight("audio", fa)), "audio", "txt")
+    if "va" in groups:                                                               # :350-358
+        val_log["v_a"] = metric(fine_score_matrix(fv, fa, ones(fv), ones(fa), weight("video", fv), weight("audio", fa)), "audio", "video")
+    if "vta" in groups:                                                              # :361-370
+        sm = fine_score_matrix(fv, torch.cat((ft, fa), dim=1), ones(fv), torch.cat((mt, ones(fa)), dim=1), weight("video", fv),
+                               torch.cat((weight("text", ft), weight("audio", fa)), dim=1))
+        val_log["v_ta"] = metric(sm, "ta", "video")
+    if "atv" in groups:                                                              # :372-381
+        sm = fine_score_matrix(fa, torch.cat((ft, fv), dim=1), ones(fa), torch.cat((mt, ones(fv)), dim=1), weight("audio", fa),
+                               torch.cat((weight("text", ft), weight("video", fv)), dim=1))
+        val_log["a_tv"] = metric(sm, "tv", "audio")
+    return val_log
