@@ -496,6 +496,39 @@ int valor_beam_select(void* stream, const float* logits, int64_t ld, int64_t row
  * The caller advances offset by R * ceil(V / 4) per step. One workgroup per row, no atomics: deterministic. */
 int valor_sample_tokens(void* stream, const float* logits, int64_t ld, int R, int V, uint64_t seed, uint64_t offset, int64_t eos,
                         uint8_t* unfinished, int64_t* tok, int64_t* sents, int64_t sents_ld, float* logprobs, int64_t lp_ld);
+/* ---- the SCST caption reward on the device: CIDEr-D + BLEU-4 per hypothesis row (csrc/reward.hip; the rules are those of
+ * valor_amd/scst.py: scorer/cider_scorer.py:119-200 with n = 1..4 and sigma 6, scorer/bleu_scorer.py:202-250 option 'closest').
+ *   KEY of the n-gram (t_0 .. t_{n-1}): (t_i + 1) in bits [16 i, 16 i + 16) of a uint64, unused fields 0 -- exact, n = the number of
+ *   non-zero fields. Valid token ids are 0 .. 65533; code 65535 stands for "unknown" and appears in no table.
+ *   valor_reward_tables (device pointers; built once per scorer by valor_amd.scst.reward_tables):
+ *     g_keys uint64 [n_global] sorted unique, g_idf fp64 [n_global]: every n-gram with a document frequency and its
+ *       idf = ref_len - log(max(1, df)), evaluated on the host; an n-gram not in the table has idf = ref_len.
+ *     clip_ref_ptr int32 [n_clips + 1]: the references of clip c are clip_ref_ptr[c] .. clip_ref_ptr[c + 1].
+ *     ref_key_ptr int32 [#references + 1]; ref_keys uint64 / ref_vals fp64: per reference its sorted unique keys and their tf * idf.
+ *     ref_norm fp64 [#references, 4] (the norm per n), ref_bigrams int32 (the count of 2-grams: CIDEr-D's "length"), ref_tokens int32.
+ *     clip_bleu_ptr int32 [n_clips + 1]; bleu_keys uint64 sorted unique per clip, bleu_cnt int32: the maximum count over the clip's
+ *       references. The lists are trusted (offsets ascending and inside their arrays).
+ *   seq int64 [R, L] with row pitch ld >= L (unit column stride), as the sampler and the decoders leave it; clip_idx int32 [R].
+ *   Per row: cut at the first eos (tokens behind it never count); a token outside [0, vocab) becomes the unknown code and matches nothing;
+ *   hypothesis tf-idf and norms; CIDEr-D = 10 * mean over n and references of the clipped dot product (min(x, y) * y) / both norms (when
+ *   neither is 0) * exp(-delta^2 / 72); BLEU-4 = (prod_k (correct_k + 1e-15) / (guess_k + 1e-9))^(1/4), times exp(1 - 1 / ratio) when
+ *   ratio = (len + 1e-15) / (closest reference length + 1e-9) < 1 (ties to the shorter reference).
+ *   reward fp64 [R] = CIDEr-D + BLEU-4; cider / bleu fp64 [R] receive the two parts where not NULL. A row whose clip_idx is outside
+ *   [0, n_clips) or whose clip has no reference gets NaN.
+ *   All sums, exp, sqrt and pow are fp64, every reduction has a fixed order and nothing is a floating-point atomic: the same input gives
+ *   the same bits. One launch (one workgroup per row) scores any number of rows; nothing is read back. No workspace.
+ *   L <= 128: four times the largest max_generation_len any shipped configuration uses. R == 0: no-op. VALOR_ERR_ARG for R < 0, L < 1,
+ *   L > 128, ld < L, vocab < 1 or > 65534, eos outside [0, vocab), a null seq / clip_idx / tables / reward or table pointer. */
+typedef struct valor_reward_tables {
+    const uint64_t* g_keys; const double* g_idf;
+    const int32_t* clip_ref_ptr; const int32_t* ref_key_ptr; const uint64_t* ref_keys; const double* ref_vals;
+    const double* ref_norm; const int32_t* ref_bigrams; const int32_t* ref_tokens;
+    const int32_t* clip_bleu_ptr; const uint64_t* bleu_keys; const int32_t* bleu_cnt;
+    double ref_len;
+    int32_t n_global, n_clips;
+} valor_reward_tables;
+int valor_caption_reward(void* stream, const int64_t* seq, int64_t ld, int R, int L, int64_t eos, int vocab, const int32_t* clip_idx,
+                         const valor_reward_tables* tables, double* reward, double* cider, double* bleu);
 /* backward of a fused activation when no GEMM can absorb it: modeling.py:249-252 */
 int valor_dact_mul(void* stream, int dtype, const void* dh, const void* u, void* du, int64_t n, int act);
 /* Linear(E -> 1) of the fine-weight heads: pretrain.py:104-112 */

@@ -4,8 +4,10 @@ the full length). Prints where the time goes: the encoders + K|V projections (on
 each step like the reference with VALOR_KV_CACHE=0; two rows per sequence against the K|V cache otherwise, decode.py).
 Mode 'sample' is the sampled decode of SCST (decode.decode_sample_cached); mode 'scst' times one self-critical training step at the
 caption-msrvtt shape (task cap%tva%tv, a CaptionScorer of 20 synthetic references per clip) split into greedy baseline, encoders +
-sampled decoding, scoring and the loss pass (forward + backward), and one scorer call of B hypotheses.
-usage: [GEN_MODES=greedy,beam3,sample,scst] python tools/gen_bench.py out.json [batch] [max_len]"""
+sampled decoding, scoring and the loss pass (forward + backward), and one scorer call of B hypotheses. GEN_SCORER=host (default) scores
+with scst.CaptionScorer on the host, GEN_SCORER=device with scst.DeviceCaptionScorer (valor_caption_reward: one launch for the sample and
+greedy rows of both groups, timed up to a device synchronisation); score_ms / scorer_ms_per_call are those of the scorer in use.
+usage: [GEN_MODES=greedy,beam3,sample,scst] [GEN_SCORER=host|device] python tools/gen_bench.py out.json [batch] [max_len]"""
 import json
 import os
 import sys
@@ -57,6 +59,13 @@ if "scst" in MODES:
     batch["ids"] = [f"clip{i}" for i in range(B)]
     model.scorer = scst.CaptionScorer({i: [rng.integers(1000, 3000, size=int(rng.integers(6, 15))).tolist() for _ in range(20)]
                                        for i in batch["ids"]})
+    SCORER = os.environ.get("GEN_SCORER", "host")
+    if SCORER not in ("host", "device"):
+        raise SystemExit(f"GEN_SCORER={SCORER}: host or device")
+    on_device = SCORER == "device"
+    if on_device:
+        model.scorer = model.scorer.to_device(dev, vocab=spec.vocab)
+    res["scorer"] = SCORER
     model.max_generation_len = L
     groups = ["tva", "tv"]
 
@@ -64,13 +73,18 @@ if "scst" in MODES:
         t = {}
         sync = torch.cuda.synchronize
         sync(); t0 = time.perf_counter()
-        greedy = model.scst_baseline(batch, groups)
+        greedy = model.scst_baseline(batch, groups, device=on_device)
         sync(); t["greedy_ms"] = time.perf_counter() - t0; t0 = time.perf_counter()
         vo, ao = model.scst_encode(batch, groups)
         samples = model.scst_sample(vo, ao, groups)
         sync(); t["encode_and_sample_ms"] = time.perf_counter() - t0; t0 = time.perf_counter()
-        rewards = {g: model.scorer(batch["ids"], scst.hypotheses(samples[g][0].cpu(), model.eos_token))
-                   - model.scorer(batch["ids"], scst.hypotheses(greedy[g], model.eos_token)) for g in groups}
+        if on_device:
+            rewards = dict(zip(groups, model.scorer.advantages(batch["ids"], [samples[g][0] for g in groups], [greedy[g] for g in groups],
+                                                               model.eos_token, vocab=spec.vocab)))
+            sync()
+        else:
+            rewards = {g: model.scorer(batch["ids"], scst.hypotheses(samples[g][0].cpu(), model.eos_token))
+                       - model.scorer(batch["ids"], scst.hypotheses(greedy[g], model.eos_token)) for g in groups}
         t["score_ms"] = time.perf_counter() - t0; t0 = time.perf_counter()
         out = model.scst_loss(vo, ao, {g: samples[g][0] for g in groups}, rewards)
         sum(out.values()).backward()
@@ -81,11 +95,19 @@ if "scst" in MODES:
     model.train()
     split()
     runs = [split() for _ in range(3)]
-    res["scst_step"] = {k: round(1e3 * sum(r[k] for r in runs) / len(runs), 1) for k in runs[0]}
+    res["scst_step"] = {k: round(1e3 * sum(r[k] for r in runs) / len(runs), 3 if k == "score_ms" else 1) for k in runs[0]}
     hyps = [rng.integers(1000, 3000, size=L).tolist() for _ in range(B)]
+    if on_device:
+        hyps = torch.tensor(hyps, dtype=torch.int64, device=dev)
+        call = lambda: model.scorer.score(batch["ids"], hyps, model.eos_token)
+        call()
+    else:
+        call = lambda: model.scorer(batch["ids"], hyps)
+    torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(5):
-        model.scorer(batch["ids"], hyps)
-    res["scorer_ms_per_call"] = round((time.perf_counter() - t0) / 5 * 1e3, 2)
+        call()
+    torch.cuda.synchronize()
+    res["scorer_ms_per_call"] = round((time.perf_counter() - t0) / 5 * 1e3, 3 if on_device else 2)
 print(json.dumps(res, indent=1))
 json.dump(res, open(sys.argv[1], "w"), indent=1)

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvalor_hip.so")
 OBJDIR = os.path.join(CSRC, "_obj")
+PUBLIC_HEADER = os.path.join(os.path.dirname(HERE), "include", "valor_hip.h")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -38,6 +39,8 @@ def _headers_digest():
         if f.endswith(".h"):
             with open(os.path.join(CSRC, f), "rb") as fh:
                 h.update(fh.read())
+    with open(PUBLIC_HEADER, "rb") as fh:          # reward.hip takes valor_reward_tables from the public header
+        h.update(fh.read())
     return h.hexdigest()
 
 

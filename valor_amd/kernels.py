@@ -543,6 +543,21 @@ def masked_rows(labels, row_off, n, G=1, Ttot=None, r0=0, idx=None, lab_out=None
     return idx, lab_out
 
 
+def caption_reward(seq, eos, vocab, clip_idx, tables, reward, cider=None, bleu=None):
+    """CIDEr-D + BLEU-4 of every row of seq int64 [R, L] (row pitch = stride(0), L <= 128) against the references of clip clip_idx[r]
+    (valor_caption_reward): tables = a lib.RewardTables of device pointers (scst.DeviceCaptionScorer keeps the tensors alive), reward /
+    cider / bleu fp64 [R] (the two parts optional). One launch, nothing read back."""
+    import ctypes
+    _check_gpu(seq, clip_idx, reward, cider, bleu)
+    assert seq.dtype == torch.int64 and seq.dim() == 2 and (seq.stride(1) == 1 or seq.shape[1] == 1)
+    R, L = seq.shape
+    assert clip_idx.dtype == torch.int32 and clip_idx.is_contiguous() and clip_idx.numel() == R
+    for t in (reward, cider, bleu):
+        assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.numel() == R)
+    lib.call("valor_caption_reward", _stream(), _ptr(seq), seq.stride(0) if R > 1 else L, R, L, int(eos), int(vocab), _ptr(clip_idx),
+             ctypes.addressof(tables), _ptr(reward), _ptr(cider), _ptr(bleu))
+
+
 def sample_tokens(logits, seed, offset, eos, unfinished, tok, sents, logprobs):
     """one step of the sampled decode (valor_sample_tokens): logits fp32 [R, V] (row pitch = stride(0)), unfinished bool [R] (updated in
     place), tok int64 [R] (written: the next input token), sents int64 / logprobs fp32 column views [R] (e.g. sents[:, t]). The caller

@@ -46,6 +46,13 @@ class XattnSeg(_c.Structure):
                 ("B", _i), ("Sq", _i), ("seed", _u64), ("offset", _u64)]
 
 
+class RewardTables(_c.Structure):
+    """valor_reward_tables of include/valor_hip.h"""
+    POINTERS = ("g_keys", "g_idf", "clip_ref_ptr", "ref_key_ptr", "ref_keys", "ref_vals", "ref_norm", "ref_bigrams", "ref_tokens",
+                "clip_bleu_ptr", "bleu_keys", "bleu_cnt")
+    _fields_ = [(k, _vp) for k in POINTERS] + [("ref_len", _c.c_double), ("n_global", _c.c_int32), ("n_clips", _c.c_int32)]
+
+
 # name -> argtypes (restype is always int: 0 ok, <0 error)
 SIGNATURES = {
     "valor_gemm": [_vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _vp, _vp, _i64,
@@ -141,6 +148,7 @@ SIGNATURES = {
     "valor_xent_weighted_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _i64, _i, _i64],
     "valor_weighted_mean_f32": [_vp, _vp, _vp, _i64, _vp],
     "valor_sample_tokens": [_vp, _vp, _i64, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _i64, _vp, _i64],
+    "valor_caption_reward": [_vp, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp],
     "valor_rowdot_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i],
     "valor_rowdot_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i],
     "valor_colsum": [_vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _i, _i],

@@ -1381,21 +1381,34 @@ class VALOR(nn.Module):
         from .. import scst
         groups = [g for g in ("tva", "tv", "ta") if g in groups]
         ids = list(batch["ids"])
-        greedy = self.scst_baseline(batch, groups)
+        on_device = isinstance(self.scorer, scst.DeviceCaptionScorer)
+        if on_device:                                                          # a vocabulary the 16-bit keys cannot carry: say so before decoding
+            self.scorer.check(self.eos_token, self.spec.vocab, self.max_generation_len)
+        greedy = self.scst_baseline(batch, groups, device=on_device)
         video_output, audio_output = self.scst_encode(batch, groups)
         samples = self.scst_sample(video_output, audio_output, groups)
-        rewards = {}
-        for g in groups:
-            r_s = self.scorer(ids, scst.hypotheses(samples[g][0].cpu(), self.eos_token))
-            r_g = self.scorer(ids, scst.hypotheses(greedy[g], self.eos_token))
-            rewards[g] = r_s - r_g
+        if on_device:
+            # sample and greedy rows of every group in ONE valor_caption_reward launch, where the decoders left them; r_s - r_g in fp64 on
+            # the device, then fp32: the roundings of the host path, nothing read back for the scoring
+            adv = self.scorer.advantages(ids, [samples[g][0] for g in groups], [greedy[g] for g in groups], self.eos_token,
+                                         vocab=self.spec.vocab)
+            rewards = dict(zip(groups, adv))
+            if self.collect is not None:
+                greedy = {g: t.cpu() for g, t in greedy.items()}
+        else:
+            rewards = {}
+            for g in groups:
+                r_s = self.scorer(ids, scst.hypotheses(samples[g][0].cpu(), self.eos_token))
+                r_g = self.scorer(ids, scst.hypotheses(greedy[g], self.eos_token))
+                rewards[g] = r_s - r_g
         if self.collect is not None:
             self.collect.update(scst_greedy=greedy, scst_samples=samples, scst_rewards=rewards)
         return self.scst_loss(video_output, audio_output, {g: samples[g][0] for g in groups}, rewards)
 
-    def scst_baseline(self, batch, groups):
-        """the self-critical baseline: greedy captions, encoders in eval mode, no grad -> {group: host int64 [b, L]}. The eval switch is
-        local (nn.Module.train, not VALOR.train: the training step's static K|V buffers and graphs stay)."""
+    def scst_baseline(self, batch, groups, device=False):
+        """the self-critical baseline: greedy captions, encoders in eval mode, no grad -> {group: host int64 [b, L]} (device=True: the
+        decoder's device tensors, not copied: what the device scorer reads). The eval switch is local (nn.Module.train, not VALOR.train:
+        the training step's static K|V buffers and graphs stay)."""
         from .. import decode
         was = self.training
         nn.Module.train(self, False)
@@ -1403,7 +1416,7 @@ class VALOR(nn.Module):
             with torch.no_grad():
                 b, kv_layers, ranges = decode.encode_for_generation(self, batch, groups)
                 res = decode._decode_groups(self, groups, b, kv_layers, ranges, "caption", 1, self.max_generation_len)
-                return {g: seq.cpu() for g, (seq, _lp) in res.items()}
+                return {g: seq if device else seq.cpu() for g, (seq, _lp) in res.items()}
         finally:
             nn.Module.train(self, was)
 
@@ -1460,9 +1473,16 @@ class VALOR(nn.Module):
         for g in groups:
             tokens, labels = self.scst_inputs(seqs[g].cpu())
             passes.append(("caption_" + g, tokens, labels, [g], prompt, True))
-            r = torch.as_tensor(np.asarray(rewards[g], dtype=np.float32))
-            weights.append(r[(labels != -1).nonzero(as_tuple=True)[0]])       # one weight per labelled row, in nonzero() order
-        w_all = self._dev(torch.cat(weights))
+            rows = (labels != -1).nonzero(as_tuple=True)[0]                   # one weight per labelled row, in nonzero() order
+            r = rewards[g]
+            if torch.is_tensor(r) and r.device.type != "cpu":                 # device rewards (the device scorer): gathered where they are
+                weights.append(r.to(torch.float32)[self._dev(rows)])
+            else:
+                weights.append(torch.as_tensor(np.asarray(r, dtype=np.float32))[rows])
+        if any(w.device.type != "cpu" for w in weights):
+            w_all = torch.cat([self._dev(w) for w in weights])
+        else:
+            w_all = self._dev(torch.cat(weights))
         saved = self._smoothing, self._full_attn
         self._smoothing, self._full_attn = 0.0, self.caption_type == "unimlm"
         try:
