@@ -529,6 +529,43 @@ typedef struct valor_reward_tables {
 } valor_reward_tables;
 int valor_caption_reward(void* stream, const int64_t* seq, int64_t ld, int R, int L, int64_t eos, int vocab, const int32_t* clip_idx,
                          const valor_reward_tables* tables, double* reward, double* cider, double* bleu);
+/* ---- caption evaluation on the device: corpus BLEU-1..4, ROUGE-L and CIDEr of one hypothesis per clip (csrc/capeval.hip; the rules
+ * are those of valor_amd/capeval.py: cococaption/pycocoevalcap bleu/bleu_scorer.py:201-266 option 'closest', rouge/rouge.py:47-77,
+ * cider/cider_scorer.py:96-195). Symbols are small integers (interned words, or model token ids); keys as valor_caption_reward.
+ *   valor_capeval_tables (device pointers; built per evaluated clip set by valor_amd.capeval.capeval_tables): the fields of
+ *   valor_reward_tables with the same meaning -- the document frequency behind g_idf / ref_vals / ref_norm and ref_len = log(#clips)
+ *   are counted over exactly the clips of the table, i.e. the clips being evaluated (pycocoevalcap/eval.py:21) -- plus the references'
+ *   raw symbol sequences for the longest common subsequence: ref_sym_ptr int32 [#references + 1], ref_syms uint16 (reference q =
+ *   ref_syms[ref_sym_ptr[q] .. ref_sym_ptr[q + 1]), any length). The lists are trusted.
+ *   seq int64 [R, L], row pitch ld >= L, L <= 128; a row is cut at its first eos; a symbol outside [0, vocab) matches nothing.
+ *   Per row r (all required, they are the input of the corpus reduction; there is no other workspace):
+ *     cider fp64 [R]; rouge fp64 [R] = (1 + b^2) P R / (R + b^2 P), b = 1.2, P = max_q lcs_q / len, R = max_q lcs_q / len(ref_q), the two
+ *     maxima independent, 0 if either is 0 or the hypothesis is empty; bleu fp64 [R, 4] = the sentence Bleu_1..4 on the row's own integers;
+ *     counts int32 [R, 10] = correct[4], guess[4] (guess_k = max(0, len - k + 1)), testlen, the closest reference length (ties: shorter).
+ *   summary (a second, one-workgroup launch): value[6] = corpus Bleu_1..4 = (prod_{j<=k} (C_j + 1e-15) / (G_j + 1e-9))^(1/k), times
+ *     exp(1 - 1/ratio) when ratio = (T + 1e-15) / (Rl + 1e-9) < 1; the mean ROUGE_L; the mean CIDEr. total[10] = the sums of counts.
+ *   A row whose clip_idx is outside [0, n_clips) or whose clip has no reference: NaN in its fp64 outputs, -1 in its counts, all six
+ *   summary values NaN (the totals then cover the other rows).
+ *   All float arithmetic is fp64, idf and reference tf-idf are the host's bits (no log here), every reduction has a fixed order, the only
+ *   atomics are integer ones: the same input gives the same bits.
+ *   R == 0: nothing is launched; a non-null summary is set to all zero bytes (values 0.0, totals 0). VALOR_ERR_ARG for R < 0, L < 1,
+ *   L > 128, ld < L, vocab < 1 or > 65534, eos outside [0, vocab), a null seq / clip_idx / tables / output / summary or table pointer. */
+typedef struct valor_capeval_tables {
+    const uint64_t* g_keys; const double* g_idf;
+    const int32_t* clip_ref_ptr; const int32_t* ref_key_ptr; const uint64_t* ref_keys; const double* ref_vals;
+    const double* ref_norm; const int32_t* ref_bigrams; const int32_t* ref_tokens;
+    const int32_t* clip_bleu_ptr; const uint64_t* bleu_keys; const int32_t* bleu_cnt;
+    const int32_t* ref_sym_ptr; const uint16_t* ref_syms;
+    double ref_len;
+    int32_t n_global, n_clips;
+} valor_capeval_tables;
+typedef struct valor_capeval_summary {
+    double value[6];
+    int64_t total[10];
+} valor_capeval_summary;
+int valor_caption_metrics(void* stream, const int64_t* seq, int64_t ld, int R, int L, int64_t eos, int vocab, const int32_t* clip_idx,
+                          const valor_capeval_tables* tables, double* cider, double* rouge, double* bleu, int32_t* counts,
+                          valor_capeval_summary* summary);
 /* backward of a fused activation when no GEMM can absorb it: modeling.py:249-252 */
 int valor_dact_mul(void* stream, int dtype, const void* dh, const void* u, void* du, int64_t n, int act);
 /* Linear(E -> 1) of the fine-weight heads: pretrain.py:104-112 */

@@ -368,3 +368,214 @@ def validate_ret(model, loader, task):
                                torch.cat((weight("text", ft), weight("video", fv)), dim=1))
         val_log["a_tv"] = metric(sm, "tv", "audio")
     return val_log
+
+
+# ------------------------------------------------------------------ caption / QA evaluation (test.py:18-237, :781-788)
+_GROUP_KEY = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}
+
+
+def _rank():
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def _gathered(items):
+    """test.py:101, :203: [i for j in all_gather_list(items) for i in j] -- this rank's list, or every rank's in rank order"""
+    from . import dist as vdist
+    return [i for part in vdist.all_gather_list(items) for i in part] if vdist.is_dist() else list(items)
+
+
+def _unwrapped(model):
+    """the VALOR under a DistributedDataParallel-style wrapper (the reference's get_model_attr)"""
+    return getattr(model, "module", model)
+
+
+def _decoder(model, decode):
+    if decode is not None:
+        return decode
+    return _unwrapped(model).decode_sequence
+
+
+def caption_metrics_for(annotations, tokenize=None, scorer="device", device="cuda:0"):
+    """The scorer validate_cap uses, for a caller that keeps it across validation rounds (the device tables of the validation set are then
+    built and uploaded once): annotations = the reference's annfile path, {clip id: [word list or caption string, ...]}, or a
+    capeval.CaptionMetrics. scorer: 'device' (capeval.DeviceCaptionMetrics) or 'host' (capeval.CaptionMetrics)."""
+    from . import capeval
+    if scorer not in ("device", "host"):
+        raise ValueError(f"scorer {scorer!r}: 'device' or 'host'")
+    tok = tokenize if tokenize is not None else capeval.simple_tokenize
+    if isinstance(annotations, capeval.DeviceCaptionMetrics):
+        return annotations if scorer == "device" else annotations.host
+    if isinstance(annotations, capeval.CaptionMetrics):
+        host = annotations
+    elif isinstance(annotations, (str, bytes)) or hasattr(annotations, "__fspath__"):
+        host = capeval.CaptionMetrics.from_annotations(annotations, tokenize=tok)
+    else:
+        host = capeval.CaptionMetrics(annotations, tokenize=tok)
+    if host.tokenize is None:                                                  # the hypotheses arrive as strings: a copy that splits them
+        import copy                                                            # (shallow: the caller's scorer keeps refusing strings)
+        host = copy.copy(host)
+        host.tokenize = tok
+    return capeval.DeviceCaptionMetrics(host, device=device) if scorer == "device" else host
+
+
+def compute_metric_cap(results, metrics):
+    """test.py:781-788 on [{'video_id', 'caption'}, ...]: the corpus metrics * 100 rounded to two decimals (no METEOR: capeval's docstring).
+    The evaluated clips are the ids of the results (pycocoevalcap/eval.py:21); a clip with two results raises ValueError."""
+    from . import capeval
+    res = metrics.score([r["video_id"] for r in results], [r["caption"] for r in results])
+    return capeval.rounded(res.corpus)
+
+
+@torch.no_grad()
+def validate_cap(model, loader, task, annotations, *, tokenize=None, decode=None, scorer="device", output_dir=None, global_step=0, dset_name=""):
+    """test.py::validate_cap (:136-237): `loader` yields THIS RANK's batches; `task` is 'cap%tva%tv..'. Per batch the model's
+    compute_loss=False branch generates, the sequences are decoded (model.decode_sequence, or `decode`: int [N, T] -> N strings), the
+    result lists are gathered across ranks (all_gather_list) and every group is scored against `annotations` (caption_metrics_for) by
+    capeval: on the device (`scorer='device'`, valor_caption_metrics) or on the host. Returns {'tva': {Bleu_1..4, ROUGE_L, CIDEr}, 'tv':
+    .., 'ta': ..}, every value * 100 rounded to two decimals: the reference's val_log without METEOR (and with `tokenize`, default
+    capeval.simple_tokenize, in the place of the PTB tokenizer; see capeval).
+    With output_dir, rank 0 writes the reference's results_test_{dset_name}/step_{global_step}_{group}.json. coco_submit / nocaps_submit
+    (group tv) and vatex_submit (group tva) from the model's options write submission.json in the reference's formats, and that group
+    gets no metrics. Every rank returns the full log (as validate_pt / validate_ret; the reference fills 'ta' on rank 0 only): every
+    rank scores the whole gathered set, so with raw annotations every rank also builds (host n-gram statistics and flat tables in
+    Python: seconds at MSRVTT size) and uploads its own device tables on every call. Pass a scorer from
+    caption_metrics_for and keep it across validation rounds: the tables are then built and uploaded once per rank."""
+    import json
+    import os
+    from .model.valor import _opt
+    core = _unwrapped(model)
+    opts = getattr(core, "opts", None)
+    coco, vatex, nocaps = (bool(_opt(opts, k, False)) for k in ("coco_submit", "vatex_submit", "nocaps_submit"))
+    groups = [g for g in ("tva", "tv", "ta") if g in task.split("%")[1:]]      # the reference's order of evaluation (:202-233)
+    dec = _decoder(model, decode)
+    model.eval()
+    results = {g: [] for g in groups}
+    for batch in loader:
+        ids = list(batch["ids"])
+        ev = model(batch, task=task, compute_loss=False)
+        for g in groups:
+            sents = dec(ev["generated_sequences_" + _GROUP_KEY[g]])
+            for i, s in zip(ids, sents):
+                if g == "tv" and coco:
+                    results[g].append({"image_id": int(str(i).split("_")[-1]), "caption": s})
+                elif g == "tv" and nocaps:
+                    results[g].append({"image_id": int(i), "caption": s})
+                elif g == "tva" and vatex:
+                    results[g].append({i: s})
+                else:
+                    results[g].append({"video_id": i, "caption": s})
+    folder = None
+    if output_dir is not None:
+        folder = os.path.join(output_dir, f"results_test_{dset_name}")
+        os.makedirs(folder, exist_ok=True)
+
+    def dump(obj, name):
+        if folder is not None and _rank() == 0:
+            with open(os.path.join(folder, name), "w") as fh:
+                json.dump(obj, fh)
+
+    metrics = None
+    val_log = {}
+    for g in groups:
+        res = _gathered(results[g])
+        if g == "tva" and vatex:
+            dump({k: v for r in res for k, v in r.items()}, "submission.json")
+        elif g == "tv" and (coco or nocaps):
+            dump(res, "submission.json")
+        else:
+            if metrics is None:
+                metrics = caption_metrics_for(annotations, tokenize, scorer, device=str(getattr(core, "device", "cuda:0")))
+            val_log[g] = compute_metric_cap(res, metrics)
+            dump(res, f"step_{global_step}_{g}.json")
+    return val_log
+
+
+def _answer_strings(batch, dec):
+    """the ground-truth answers of a QA batch as strings: batch['answers'], or the reference's eval schema (txt_tokens = the answer
+    strings, test.py:71), or the training schema (txt_tokens['bert_tokens'] = [CLS] answer [SEP] rows), decoded like the predictions"""
+    gt = batch.get("answers")
+    if gt is None:
+        gt = batch["txt_tokens"]
+    if isinstance(gt, dict):
+        return dec(gt["bert_tokens"][:, 1:])
+    return list(gt)
+
+
+@torch.no_grad()
+def validate_qa(model, loader, task, *, decode=None, output_dir=None, global_step=0, dset_name=""):
+    """test.py::validate_qa (:44-130): the generated answers of every group, decoded to strings, are compared with the ground truth
+    (exact string equality); answers and ground truth are gathered across ranks. Returns {'tv': {'accuracy': round(acc * 100, 2)}, ..}
+    on every rank. With output_dir, rank 0 writes predict_answers/step{global_step}_gt.json, step{..}_tv_pred.json and the question_ids
+    submission list step{..}_tv_pred_submited_{dset_name}.json (batch['question_ids'], group tv only: :79-81, :112-114)."""
+    import json
+    import os
+    groups = task.split("%")[1:]
+    dec = _decoder(model, decode)
+    model.eval()
+    gt, submit = [], []
+    answers = {g: [] for g in ("tv", "tva", "ta") if g in groups}
+    for batch in loader:
+        gt += _answer_strings(batch, dec)
+        ev = model(batch, task=task, compute_loss=False)
+        for g in answers:
+            a = dec(ev["generated_answers_" + _GROUP_KEY[g]])
+            answers[g] += a
+            if g == "tv" and batch.get("question_ids") is not None:
+                submit += [{"question_id": q, "answer": s} for q, s in zip(batch["question_ids"], a)]
+    folder = None
+    if output_dir is not None:
+        folder = os.path.join(output_dir, "predict_answers")
+        os.makedirs(folder, exist_ok=True)
+
+    def dump(obj, name):
+        if folder is not None and _rank() == 0:
+            with open(os.path.join(folder, name), "w") as fh:
+                json.dump(obj, fh)
+
+    gt = _gathered(gt)
+    dump(gt, f"step{global_step}_gt.json")
+    val_log = {}
+    for g in answers:
+        pred = _gathered(answers[g])
+        if len(pred) != len(gt):
+            raise ValueError(f"validate_qa: {len(pred)} answers of group {g} for {len(gt)} ground-truth answers")
+        if g == "tv":
+            dump(pred, f"step{global_step}_tv_pred.json")
+            dump(_gathered(submit), f"step{global_step}_tv_pred_submited_{dset_name}.json")
+        acc = sum(p == t for p, t in zip(pred, gt)) / len(gt)
+        val_log[g] = {"accuracy": round(acc * 100, 2)}
+    return val_log
+
+
+def validate_single(model, loader, task, *, annotations=None, dset_name="", output_dir=None, global_step=0, **kw):
+    """test.py::validate_single (:30-40): route a task string to validate_pt / validate_ret / validate_cap / validate_qa. annotations: the
+    caption references of a 'cap' task (default: loader.dataset.annfile, where the reference finds them, test.py:143)."""
+    if task.startswith("pt"):
+        return validate_pt(model, loader, task)
+    if task.startswith("ret"):
+        return validate_ret(model, loader, task)
+    if task.startswith("cap"):
+        if annotations is None:
+            annotations = getattr(getattr(loader, "dataset", None), "annfile", None)
+        if annotations is None:
+            raise ValueError(f"task {task!r}: caption evaluation needs annotations (or loader.dataset.annfile)")
+        return validate_cap(model, loader, task, annotations, output_dir=output_dir, global_step=global_step, dset_name=dset_name, **kw)
+    if task.startswith("qa"):
+        return validate_qa(model, loader, task, decode=kw.get("decode"), output_dir=output_dir, global_step=global_step, dset_name=dset_name)
+    raise NotImplementedError(f"task {task!r}: 'pt', 'ret', 'cap' and 'qa' are the reference's evaluation families (test.py:33-40)")
+
+
+def validate(model, val_loaders, *, annotations=None, output_dir=None, global_step=0, **kw):
+    """test.py::validate (:18-27): val_loaders = {'task--dset': loader}; returns {key: val_log} and puts the model back into train mode.
+    annotations: {key or dset name: caption references} for the 'cap' tasks (validate_single's default otherwise)."""
+    eval_log = {}
+    model.eval()
+    try:
+        for key, loader in val_loaders.items():
+            task, _, dset = key.partition("--")
+            ann = None if annotations is None else annotations.get(key, annotations.get(dset))
+            eval_log[key] = validate_single(model, loader, task, annotations=ann, dset_name=dset, output_dir=output_dir, global_step=global_step, **kw)
+    finally:
+        model.train()
+    return eval_log

@@ -558,6 +558,24 @@ def caption_reward(seq, eos, vocab, clip_idx, tables, reward, cider=None, bleu=N
              ctypes.addressof(tables), _ptr(reward), _ptr(cider), _ptr(bleu))
 
 
+def caption_metrics(seq, eos, vocab, clip_idx, tables, cider, rouge, bleu, counts, summary):
+    """Per-row CIDEr / ROUGE-L / sentence BLEU-1..4 and their integers of seq int64 [R, L] (row pitch = stride(0), L <= 128) against the
+    references of clip clip_idx[r], and the corpus values of the R rows (valor_caption_metrics): tables = a lib.CapevalTables of device
+    pointers (capeval.DeviceCaptionMetrics keeps the tensors alive), cider / rouge fp64 [R], bleu fp64 [R, 4], counts int32 [R, 10],
+    summary int64 [16] (valor_capeval_summary: six fp64 values, ten int64 totals). Two launches, nothing read back."""
+    import ctypes
+    _check_gpu(seq, clip_idx, cider, rouge, bleu, counts, summary)
+    assert seq.dtype == torch.int64 and seq.dim() == 2 and (seq.stride(1) == 1 or seq.shape[1] == 1)
+    R, L = seq.shape
+    assert clip_idx.dtype == torch.int32 and clip_idx.is_contiguous() and clip_idx.numel() == R
+    for t, n in ((cider, R), (rouge, R), (bleu, 4 * R)):
+        assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == 10 * R
+    assert summary.dtype == torch.int64 and summary.is_contiguous() and summary.numel() == 16
+    lib.call("valor_caption_metrics", _stream(), _ptr(seq), seq.stride(0) if R > 1 else L, R, L, int(eos), int(vocab), _ptr(clip_idx),
+             ctypes.addressof(tables), _ptr(cider), _ptr(rouge), _ptr(bleu), _ptr(counts), _ptr(summary))
+
+
 def sample_tokens(logits, seed, offset, eos, unfinished, tok, sents, logprobs):
     """one step of the sampled decode (valor_sample_tokens): logits fp32 [R, V] (row pitch = stride(0)), unfinished bool [R] (updated in
     place), tok int64 [R] (written: the next input token), sents int64 / logprobs fp32 column views [R] (e.g. sents[:, t]). The caller

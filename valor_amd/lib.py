@@ -53,6 +53,17 @@ class RewardTables(_c.Structure):
     _fields_ = [(k, _vp) for k in POINTERS] + [("ref_len", _c.c_double), ("n_global", _c.c_int32), ("n_clips", _c.c_int32)]
 
 
+class CapevalTables(_c.Structure):
+    """valor_capeval_tables of include/valor_hip.h"""
+    POINTERS = RewardTables.POINTERS + ("ref_sym_ptr", "ref_syms")
+    _fields_ = [(k, _vp) for k in POINTERS] + [("ref_len", _c.c_double), ("n_global", _c.c_int32), ("n_clips", _c.c_int32)]
+
+
+class CapevalSummary(_c.Structure):
+    """valor_capeval_summary of include/valor_hip.h"""
+    _fields_ = [("value", _c.c_double * 6), ("total", _c.c_int64 * 10)]
+
+
 # name -> argtypes (restype is always int: 0 ok, <0 error)
 SIGNATURES = {
     "valor_gemm": [_vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i, _vp, _vp, _i64,
@@ -149,6 +160,7 @@ SIGNATURES = {
     "valor_weighted_mean_f32": [_vp, _vp, _vp, _i64, _vp],
     "valor_sample_tokens": [_vp, _vp, _i64, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _i64, _vp, _i64],
     "valor_caption_reward": [_vp, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp],
+    "valor_caption_metrics": [_vp, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "valor_rowdot_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i],
     "valor_rowdot_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i],
     "valor_colsum": [_vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _i, _i],

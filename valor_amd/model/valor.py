@@ -293,6 +293,7 @@ class VALOR(nn.Module):
         self.vocab_tokens = vocab_tokens if vocab_tokens is not None else synthetic_vocab(self.spec.vocab)
         self.vocab = {t: i for i, t in enumerate(self.vocab_tokens)}
         self.bos_token, self.eos_token, self.text_mask_token = self.vocab["[CLS]"], self.vocab["[SEP]"], self.vocab["[MASK]"]
+        self.tokenizer_type = "bert"                                           # modeling.py:668: the decoder's tokenizer (decode_sequence)
         self.text_masker = TokenMasker(self.text_mask_token, 106, self.spec.vocab)     # modeling.py:673
         self.token_masker = token_masker_mode(opts)
         self.device_masker = (DeviceTokenMasker(self.text_mask_token, 106, self.spec.vocab, self._dev, seed=int(_opt(opts, "seed", 42)))
@@ -1297,6 +1298,19 @@ class VALOR(nn.Module):
                 self._smoothing, self._full_attn = 0.0, False
         from .. import decode
         return decode.generate_cap(self, batch, groups)
+
+    def decode_sequence(self, seq):
+        """VALOR.decode_sequence, model/pretrain.py:146-163 (BERT branch): int [N, T] generated ids -> N strings: every row cut at its
+        first [SEP], the WordPiece tokens joined by spaces, ' ##' removed. The CLIP tokenizer's byte-pair decoder (:161-162) is not part
+        of this project: such a model raises, and validate_cap / validate_qa take a `decode` callable instead."""
+        if self.tokenizer_type != "bert":
+            raise NotImplementedError(f"decode_sequence: tokenizer_type {self.tokenizer_type!r}; pass decode= to validate_cap / validate_qa")
+        rows = seq.tolist() if hasattr(seq, "tolist") else [list(r) for r in seq]
+        sents = []
+        for row in rows:
+            cut = row.index(self.eos_token) if self.eos_token in row else len(row)
+            sents.append(" ".join(self.vocab_tokens[int(t)] for t in row[:cut]).replace(" ##", ""))
+        return sents
 
     def qa_prompt(self, question_cpu):
         """the prompt rows of the QA passes are the QUESTION (prompt-type embeddings), 'answer the question' spliced in behind its [CLS]
