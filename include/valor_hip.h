@@ -573,6 +573,33 @@ int valor_rowdot_fwd(void* stream, int dtype, const void* x, const void* w, cons
 int valor_rowdot_bwd(void* stream, int dtype, const void* dy, const void* x, const void* w, void* dx, void* dw, void* db,
                      int64_t rows, int cols);
 
+/* ---- input preparation on the device (csrc/preproc.hip; the tensor work of AudioMapper / VideoMapper, data/data.py:135-323) ----
+ * valor_fbank: kaldi.fbank(htk_compat=True, use_energy=False, window_type='hanning', dither=0) of the selected T-frame slices of B
+ * mono clips, padded, normalised and transposed as AudioMapper.__getitem__ returns them: out fp32 [B, A, melbins, T].
+ *   wave: the clips packed back to back, n_samples values: fp32 in [-1, 1], or int16 PCM (is_pcm16: the kernel multiplies by 1/32768);
+ *   offsets int64 [B + 1] (device): clip b is samples offsets[b] .. offsets[b + 1]; a range that leaves [0, n_samples] makes the clip absent;
+ *   slice_idx int32 [B, A] (device): out[b, a] is frames slice_idx*T .. slice_idx*T + T - 1 of the clip's fbank; -1 = no audio: 0.0;
+ *   frame f < m = 1 + (N - win) / shift (0 if N < win) is samples f*shift .. f*shift + win - 1: mean removed, pre-emphasis 0.97 with
+ *   x[-1] := x[0], times window[win], zero-padded to P (the next power of two >= win, one of 256 / 512 / 1024 / 2048), |FFT|^2, mel sums,
+ *   log(max(e, 1.1920929e-07)); frames f >= m are the zero rows of the reference's padding; every value then becomes
+ *   (v - mean) / (2 * std);
+ *   tables (device, built in fp64 by the caller, valor_amd/preprocess.py fbank_tables): window fp64 [win]; twiddle fp64 [P/2, 2] =
+ *   (cos, -sin)(2 pi k / P); filter j sums mel_w[mel_ptr[j] .. mel_ptr[j + 1]) times the power of bins mel_start[j], mel_start[j] + 1, ...
+ *   (mel_start int32 [melbins], mel_ptr int32 [melbins + 1], mel_w fp32 [mel_nnz]; bins >= P/2 are never read). melbins <= 256.
+ * Only the A * T selected frames of a clip are computed, in fp64 up to the mel energy (fp32 from the log on). Deterministic (no atomics). */
+int valor_fbank(void* stream, const void* wave, int is_pcm16, int64_t n_samples, const int64_t* offsets, const int32_t* slice_idx,
+                int B, int A, int win, int shift, int P, int melbins, int T, const double* window, const double* twiddle,
+                const int32_t* mel_start, const int32_t* mel_ptr, const float* mel_w, int mel_nnz, float mean, float std, float* out);
+/* valor_frames_prepare: F uint8 RGB frames, HWC, packed in pixels[n_bytes] at offsets int64 [F] (device) -> out fp32 [F, 3, R, R].
+ * geom int32 [F, 11] (device) per frame: H, W (stored size), top, left, h, w (source box), Hv, Wv (size of the virtual resized image of
+ * the box), oy, ox (where the R x R output window sits in it), flip. Output pixel (y, x) is the bilinear sample (align_corners=False;
+ * antialias != 0: the triangle filter of support max(scale, 1), as torch.nn.functional.interpolate(antialias=True)) of the box at
+ * virtual position (y + oy, x + ox), scales h / Hv and w / Wv, taps clamped inside the box; / 255, (v - mean[c]) / std[c], column
+ * mirrored if flip. mean / std: HOST pointers to 3 floats. Frames of different stored sizes share one launch; a geometry row or an
+ * offset that leaves the buffer reads nothing and makes that frame NaN. Weights and sums are fp64: one rounding, at the store. */
+int valor_frames_prepare(void* stream, const uint8_t* pixels, int64_t n_bytes, const int64_t* offsets, const int32_t* geom, int F,
+                         int R, int antialias, const float* mean, const float* std, float* out);
+
 #ifdef __cplusplus
 }
 #endif

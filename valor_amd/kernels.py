@@ -588,3 +588,40 @@ def sample_tokens(logits, seed, offset, eos, unfinished, tok, sents, logprobs):
     assert unfinished.numel() == tok.numel() == sents.numel() == logprobs.numel() == R
     lib.call("valor_sample_tokens", _stream(), _ptr(logits), logits.stride(0), R, V, int(seed), int(offset), int(eos), _ptr(unfinished), _ptr(tok),
              _ptr(sents), sents.stride(0), _ptr(logprobs), logprobs.stride(0))
+
+
+def fbank(wave, offsets, slice_idx, tables, melbins, T, mean, std, out=None):
+    """log-mel filterbank of the selected slices in the model's layout (valor_fbank): wave = the clips packed back to back, fp32 or int16
+    PCM [n]; offsets int64 [B + 1]; slice_idx int32 [B, A] (-1: no audio); tables = preprocess.fbank_tables(...).to_device() (window,
+    twiddle, mel_start, mel_ptr, mel_w device tensors + win / shift / P). Returns fp32 [B, A, melbins, T]."""
+    _check_gpu(wave, offsets, slice_idx, out, tables.window, tables.twiddle, tables.mel_start, tables.mel_ptr, tables.mel_w)
+    assert wave.dtype in (torch.float32, torch.int16) and wave.dim() == 1 and wave.is_contiguous()
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and slice_idx.dtype == torch.int32 and slice_idx.is_contiguous()
+    B, A = slice_idx.shape
+    assert offsets.numel() == B + 1 and tables.melbins == melbins
+    assert tables.window.dtype == tables.twiddle.dtype == torch.float64 and tables.mel_w.dtype == torch.float32
+    assert tables.mel_start.dtype == tables.mel_ptr.dtype == torch.int32 and tables.mel_ptr.numel() == melbins + 1
+    if out is None:
+        out = torch.empty((B, A, melbins, T), dtype=torch.float32, device=slice_idx.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * A * melbins * T
+    lib.call("valor_fbank", _stream(), _ptr(wave), int(wave.dtype == torch.int16), wave.numel(), _ptr(offsets), _ptr(slice_idx), B, A,
+             tables.win, tables.shift, tables.P, melbins, T, _ptr(tables.window), _ptr(tables.twiddle), _ptr(tables.mel_start),
+             _ptr(tables.mel_ptr), _ptr(tables.mel_w), tables.mel_w.numel(), float(mean), float(std), _ptr(out))
+    return out
+
+
+def frames_prepare(pixels, offsets, geom, R, mean, std, antialias=False, out=None):
+    """uint8 HWC frames -> normalised fp32 [F, 3, R, R] (valor_frames_prepare): pixels uint8 [n] (the frames packed back to back), offsets
+    int64 [F], geom int32 [F, 11] = H, W, top, left, h, w, Hv, Wv, oy, ox, flip per frame; mean / std: 3 host floats each."""
+    import ctypes
+    _check_gpu(pixels, offsets, geom, out)
+    assert pixels.dtype == torch.uint8 and pixels.dim() == 1 and pixels.is_contiguous()
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and geom.dtype == torch.int32 and geom.is_contiguous()
+    F = offsets.numel()
+    assert geom.shape == (F, 11) and len(mean) == 3 and len(std) == 3
+    if out is None:
+        out = torch.empty((F, 3, R, R), dtype=torch.float32, device=geom.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == F * 3 * R * R
+    lib.call("valor_frames_prepare", _stream(), _ptr(pixels), pixels.numel(), _ptr(offsets), _ptr(geom), F, int(R), int(bool(antialias)),
+             (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), _ptr(out))
+    return out

@@ -164,6 +164,8 @@ SIGNATURES = {
     "valor_rowdot_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i],
     "valor_rowdot_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i],
     "valor_colsum": [_vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _i, _i],
+    "valor_fbank": [_vp, _vp, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp],
+    "valor_frames_prepare": [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _vp],
 }
 
 _lib = None
