@@ -400,6 +400,25 @@ int valor_retrieval_ranks(void* stream, const float* score, int64_t ld, const in
                           int nnz, float inv_temp, int dual, float* lse_row, float* lse_col, int* rank_f, int* rank_b, void* workspace,
                           int64_t workspace_bytes, int Nt, int Nv);
 
+/* ---- retrieval search: the k best columns of every row of a score matrix, streaming over column chunks (csrc/search.hip; the
+ * selection under valor_amd/search.py RetrievalIndex).
+ *   score fp32 [R, ld] (ld >= C). The candidates of row r are the pairs (score[r, c], col_base + c), c < C, and, with merge != 0, the
+ *   entries already in top_val[r, :] / top_idx[r, :] whose index is >= 0. top_val fp32 [R, k] and top_idx int64 [R, k] receive the k
+ *   best candidates, best first, under ONE total order: value descending, then index ascending. A NaN ranks below every number, -inf
+ *   included (NaNs among themselves by index): the opposite of torch.topk, and the rule of valor_retrieval_ranks, where a NaN compares
+ *   as not greater. -0 equals +0. With fewer than k candidates the remaining slots hold -inf / -1: every index written is a
+ *   candidate's or -1, never a sentinel a later gather could dereference.
+ *   The result does not depend on how the work is split (integer keys, no float atomics), so folding the chunks of a bank one by one
+ *   (merge = 1, col_base = the chunk's first clip) equals one pass over the whole row. 1 <= k <= 256; 0 <= col_base and col_base + C
+ *   < 2^63 - 1 (indices beyond 2^31 are fine). 16-byte loads when ld % 4 == 0 and score is 16-byte aligned, 4-byte loads otherwise.
+ *   workspace: valor_topk_workspace_bytes(R, C, k) bytes, 16-byte aligned, caller-owned (the k best keys of every column segment of
+ *   every row; at most one segment per 4096 columns, each a multiple of 1024 columns). Two launches: rows x segments workgroups, then one workgroup per row.
+ *   R == 0: no-op. VALOR_ERR_ARG before anything is launched on a null / misaligned pointer, ld < C, k outside [1, 256], a negative or
+ *   overflowing col_base, a short or misaligned workspace. */
+int valor_topk_workspace_bytes(int R, int C, int k, int64_t* bytes);
+int valor_topk_rows(void* stream, const float* score, int64_t ld, int R, int C, int64_t col_base, int k, int merge, float* top_val,
+                    int64_t* top_idx, void* workspace, int64_t workspace_bytes);
+
 /* ---- fused multi-tensor AdamW + global-norm clip over flat arenas.  Replaces optim/adamw.py:40-103, optim/misc.py:66-77
  * (10 param groups), torch clip_grad_norm_ (train_utils.py:358-360) and apex-amp's master<->model copies
  * (apex/apex/amp/_process_optimizer.py:14-22). n % valor_adamw_chunk() == 0; chunk_group: int8 [n/chunk], -1 = skip. */

@@ -1,0 +1,131 @@
+"""Time RetrievalIndex.search on synthetic bf16 banks at the pretraining token geometry (T = 32 text tokens, Nv = 10 clip tokens, D = 512)
+against what the parent commit offers for the same question: evaluate.fine_score_matrix over the whole bank followed by torch.topk.
+
+Per (NB, NQ, k): device events around `--iters` warmed calls of
+  search     RetrievalIndex.search (chunked fused scoring + valor_topk_rows per chunk)
+  topk       the valor_topk_rows calls of that search alone, on a score buffer of the chunk's shape: its share of the search
+  baseline   fine_score_matrix(whole bank) + torch.topk, wherever the [NQ, NB] fp32 matrix fits beside the bank
+and the rate at which the search reads the bank (features + token weights, the bytes the algorithm must read once per query batch) against
+the HBM rates of the MI355X (8.0 TB/s peak, about 6.3 TB/s achievable). The score path is compute-bound for many queries (NQ * T * Nv * D
+multiply-adds per clip), so the bank rate is an end-to-end figure of the search, not a kernel's share of peak.
+Also reports valor_topk_rows alone on [NQ, NB] fp32 scores (4 bytes per pair): the kernel's own bound is that read.
+
+Writes one JSON document to --out (default profiles/search_bench.json) and prints one line per case. No pass / fail bar: a measurement."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from valor_amd import evaluate as E                # noqa: E402
+from valor_amd import search as S                  # noqa: E402
+
+T, NV, D = 32, 10, 512
+HBM_PEAK, HBM_ACHIEVABLE = 8.0e12, 6.3e12
+
+
+def unit_bf16(n, tokens, dev, seed):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    out = torch.empty((n, tokens, D), dtype=torch.bfloat16, device=dev)
+    step = 1 << 16
+    for i in range(0, n, step):
+        m = min(step, n - i)
+        out[i:i + m] = torch.nn.functional.normalize(torch.randn((m, tokens, D), generator=g, device=dev), dim=-1).bfloat16()
+    return out
+
+
+def timed(fn, iters, warmup=2):
+    for _ in range(warmup):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nb", type=int, nargs="+", default=[10 ** 4, 10 ** 5, 10 ** 6])
+    ap.add_argument("--nq", type=int, nargs="+", default=[1, 16, 64])
+    ap.add_argument("--k", type=int, nargs="+", default=[10, 100])
+    ap.add_argument("--iters", type=int, default=200, help="most calls per timed window (large cases take fewer)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "search_bench.json"))
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "search_bench.py measures on the GPU"
+    dev = torch.device("cuda:0")
+    free = torch.cuda.mem_get_info()[0]
+    cases = []
+    for NB in a.nb:
+        bank_bytes = NB * NV * (D * 2 + 4)
+        if bank_bytes * 1.2 > free:
+            print(f"NB={NB}: a bank of {bank_bytes / 1e9:.1f} GB does not fit", flush=True)
+            continue
+        g = torch.Generator(device=dev).manual_seed(1)
+        fb = unit_bf16(NB, NV, dev, 2)
+        wb_raw = torch.randn((NB, NV), generator=g, device=dev)
+        index = S.RetrievalIndex.from_features(fb, wb_raw, group="tva")
+        ones_b = torch.ones((NB, NV), device=dev)
+        for NQ in a.nq:
+            fa = unit_bf16(NQ, T, dev, 3)
+            wa_raw = torch.randn((NQ, T), generator=g, device=dev)
+            mask = (torch.arange(T, device=dev)[None] < torch.randint(8, T + 1, (NQ, 1), generator=g, device=dev)).float()
+            q = {"feat_t": fa, "mask": mask, "weight": wa_raw}
+            chunk = index.default_chunk(NQ, T)
+            iters = max(3, min(a.iters, int(2e8 / (NB * NQ))))                        # about the same work per timed window
+            full = index.scores(None, q) if NB * NQ * 4 * 3 < free else None
+            for k in a.k:
+                search_ms = timed(lambda: index.search(None, q, k), iters)
+                bufs = [torch.randn((NQ, min(chunk, NB - c0)), device=dev) for c0 in range(0, NB, chunk)][:2]
+                state = (torch.full((NQ, k), float("-inf"), device=dev), torch.full((NQ, k), -1, dtype=torch.int64, device=dev))
+                ws = torch.empty((max(S.topk_workspace_bytes(NQ, b.shape[1], k) for b in bufs),), dtype=torch.uint8, device=dev)
+
+                def topk_only():
+                    for c0 in range(0, NB, chunk):
+                        b = bufs[0] if NB - c0 >= chunk else bufs[-1]
+                        S.topk_rows(b, k, col_base=c0, state=state, workspace=ws)
+
+                topk_ms = timed(topk_only, iters)
+                res = {"NB": NB, "NQ": NQ, "k": k, "chunk": chunk, "iters": iters, "search_ms": round(search_ms, 4), "topk_ms": round(topk_ms, 4),
+                       "topk_share": round(topk_ms / search_ms, 4), "bank_GB": round(bank_bytes / 1e9, 3),
+                       "bank_GBps": round(bank_bytes / search_ms / 1e6, 1), "bank_rate_of_hbm_peak": round(bank_bytes / (search_ms * 1e-3) / HBM_PEAK, 4),
+                       "bank_rate_of_hbm_achievable": round(bank_bytes / (search_ms * 1e-3) / HBM_ACHIEVABLE, 4),
+                       "score_GFLOPs": round(2.0 * NQ * T * NB * NV * D / 1e9, 2),
+                       "score_TFLOPps": round(2.0 * NQ * T * NB * NV * D / (search_ms * 1e-3) / 1e12, 2)}
+                if full is not None:
+                    def baseline():
+                        m = E.fine_score_matrix(fa, fb, mask, ones_b, wa_raw, wb_raw)
+                        return torch.topk(m, min(k, NB), dim=1)
+
+                    res["baseline_ms"] = round(timed(baseline, iters), 4)
+                    res["baseline_over_search"] = round(res["baseline_ms"] / search_ms, 3)
+                    topk_full_ms = timed(lambda: S.topk_rows(full, k), iters)
+                    torch_topk_ms = timed(lambda: torch.topk(full, min(k, NB), dim=1), iters)
+                    res.update(topk_rows_full_matrix_ms=round(topk_full_ms, 4), torch_topk_full_matrix_ms=round(torch_topk_ms, 4),
+                               topk_rows_full_matrix_GBps=round(NQ * NB * 4 / topk_full_ms / 1e6, 1))
+                    # the two agree wherever the k-th and (k+1)-th scores differ (torch.topk leaves the order of equal values open)
+                    got = index.search(None, q, k)
+                    want = torch.topk(full, min(k, NB), dim=1)
+                    res["indices_equal_torch_topk"] = bool(torch.equal(got.indices[:, :min(k, NB)], want.indices))
+                else:
+                    res["baseline_ms"] = None
+                print(json.dumps(res), flush=True)
+                cases.append(res)
+        del index, fb, wb_raw, ones_b
+        torch.cuda.empty_cache()
+    doc = {"bench": "search", "geometry": {"T": T, "Nv": NV, "D": D, "dtype": "bfloat16"}, "device": torch.cuda.get_device_name(0),
+           "hbm_peak_TBps": HBM_PEAK / 1e12, "hbm_achievable_TBps": HBM_ACHIEVABLE / 1e12, "timing": "device events over warmed calls", "cases": cases}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -20,23 +20,31 @@ def _fine_weights(model, name, feat):
     return ops.rowdot(h, P[f"{name}_fine_weight.2.weight"], P[f"{name}_fine_weight.2.bias"]).float().squeeze(-1).contiguous()
 
 
-def _fine_matrix_slice(featA, featB, maskA, maskB, wA_raw, wB_raw):
+def _scores_gemm(featA, featB, maskA, maskB, wA, wB, out=None):
+    """[NA, NB] fine scores through the token-similarity GEMM + valor_fine_scores; wA / wB are the SOFTMAXED token weights (contiguous
+    fp32, like the masks). `out`: a dense fp32 [NA, NB] tensor to fill. Shared by compute_fine_matrix and search.RetrievalIndex."""
     NA, T, D = featA.shape
     NB, Nv = featB.shape[:2]
-    dev = featA.device
-    f32 = dict(dtype=torch.float32, device=dev)
+    f32 = dict(dtype=torch.float32, device=featA.device)
     fa, fb = featA.contiguous().view(NA * T, D), featB.contiguous().view(NB * Nv, D)
     ldS = (NB * Nv + 7) // 8 * 8
     S = torch.empty((NA * T, ldS), **f32)
     K.gemm(fa, fb, out=S[:, :NB * Nv], out_dtype=torch.float32, splitk=False)
+    score = torch.empty((NA, NB), **f32) if out is None else out
+    lib.call("valor_fine_scores", K._stream(), S.data_ptr(), ldS, maskA.data_ptr(), maskB.data_ptr(), wA.data_ptr(), wB.data_ptr(), score.data_ptr(),
+             NA, NB, T, Nv)
+    return score
+
+
+def _fine_matrix_slice(featA, featB, maskA, maskB, wA_raw, wB_raw):
+    NA, T = featA.shape[:2]
+    NB, Nv = featB.shape[:2]
+    f32 = dict(dtype=torch.float32, device=featA.device)
     wA, wB = torch.empty((NA, T), **f32), torch.empty((NB, Nv), **f32)
     st = K._stream()
     lib.call("valor_fine_weight_softmax", st, wA_raw.data_ptr(), maskA.data_ptr(), wA.data_ptr(), NA, T)
     lib.call("valor_fine_weight_softmax", st, wB_raw.data_ptr(), maskB.data_ptr(), wB.data_ptr(), NB, Nv)
-    score = torch.empty((NA, NB), **f32)
-    lib.call("valor_fine_scores", st, S.data_ptr(), ldS, maskA.data_ptr(), maskB.data_ptr(), wA.data_ptr(), wB.data_ptr(), score.data_ptr(),
-             NA, NB, T, Nv)
-    return score
+    return _scores_gemm(featA, featB, maskA, maskB, wA, wB)
 
 
 @torch.no_grad()
@@ -265,19 +273,31 @@ def fine_score_matrix(featA, featB, maskA, maskB, weightA, weightB):
     wA, wB = torch.empty((NA, T), **f32), torch.empty((NB, Nv), **f32)
     lib.call("valor_fine_weight_softmax", st, weightA.float().contiguous().data_ptr(), maskA.data_ptr(), wA.data_ptr(), NA, T)
     lib.call("valor_fine_weight_softmax", st, weightB.float().contiguous().data_ptr(), maskB.data_ptr(), wB.data_ptr(), NB, Nv)
-    ra = max(1, min(NA, (_FUSED_BYTES - 1) // (T * D * 2)))
     rb = max(1, min(NB, (_FUSED_BYTES - 1) // (Nv * D * 2)))
-    cols = []
-    for b0 in range(0, NB, rb):
-        nb = min(rb, NB - b0)
-        part = torch.empty((NA, nb), **f32)
-        for a0 in range(0, NA, ra):
-            na = min(ra, NA - a0)
-            lib.call("valor_fine_fused_fwd", st, featA[a0:a0 + na].data_ptr(), featB[b0:b0 + nb].data_ptr(), maskA[a0:a0 + na].data_ptr(),
-                     maskB[b0:b0 + nb].data_ptr(), wA[a0:a0 + na].data_ptr(), wB[b0:b0 + nb].data_ptr(), part[a0:a0 + na].data_ptr(),
-                     None, None, None, None, na, nb, T, Nv, D)
-        cols.append(part)
+    cols = [_scores_fused(featA, featB[b0:b0 + rb], maskA, maskB[b0:b0 + rb], wA, wB[b0:b0 + rb]) for b0 in range(0, NB, rb)]
     return cols[0] if len(cols) == 1 else torch.cat(cols, dim=1)
+
+
+def fused_scores_ok(featA, featB):
+    """bf16 token features of a geometry valor_fine_fused_fwd takes (what fine_score_matrix asks before it chooses the kernel)"""
+    return featA.dtype == torch.bfloat16 and featB.dtype == torch.bfloat16 and featA.shape[1] <= 64 and featB.shape[1] <= 64 and featA.shape[2] % 64 == 0
+
+
+def _scores_fused(featA, featB, maskA, maskB, wA, wB, out=None):
+    """[NA, nb] fine scores of contiguous bf16 features by valor_fine_fused_fwd in its scores-only mode, the A rows in pieces under the
+    kernel's byte limit; featB (a slice of leading rows) must be under it already. wA / wB are the SOFTMAXED token weights (contiguous
+    fp32, like the masks). `out`: a dense fp32 [NA, nb] tensor to fill. Shared by fine_score_matrix and search.RetrievalIndex."""
+    NA, T, D = featA.shape
+    nb, Nv = featB.shape[:2]
+    st = K._stream()
+    part = torch.empty((NA, nb), dtype=torch.float32, device=featA.device) if out is None else out
+    ra = max(1, min(NA, (_FUSED_BYTES - 1) // (T * D * 2)))
+    for a0 in range(0, NA, ra):
+        na = min(ra, NA - a0)
+        lib.call("valor_fine_fused_fwd", st, featA[a0:a0 + na].data_ptr(), featB.data_ptr(), maskA[a0:a0 + na].data_ptr(),
+                 maskB.data_ptr(), wA[a0:a0 + na].data_ptr(), wB.data_ptr(), part[a0:a0 + na].data_ptr(),
+                 None, None, None, None, na, nb, T, Nv, D)
+    return part
 
 
 def retrieval_temperature(model):
