@@ -234,6 +234,26 @@ def test_capeval_structs_are_one_layout_in_header_binding_and_kernel():
     assert set(lib.CapevalTables.POINTERS) <= set(T) and T["clips"] == ["b", "a"] and T["ref_syms"].tolist() == [2, 3, 1, 2, 3]
 
 
+def test_reward_and_metrics_kernels_share_one_ngram_core():
+    """csrc/ngram.h is the one definition of the n-gram passes: both kernels include it, no helper is defined in two of the three files,
+    and for the same references the two table builders give the same twelve shared arrays"""
+    import itertools
+    from valor_amd import lib
+    src = {f: open(os.path.join(ROOT, "valor_amd", "csrc", f)).read() for f in ("reward.hip", "capeval.hip", "ngram.h")}
+    assert '#include "ngram.h"' in src["reward.hip"] and '#include "ngram.h"' in src["capeval.hip"]
+    names = {f: set(re.findall(r"DEVINL\s+[\w:<> ]+\s+(\w+)\(", text)) for f, text in src.items()}
+    assert {"ng_find", "ng_wave_sum", "ng_bleu", "ng_load_row", "ng_score_slots", "ng_norms", "ng_cider", "ng_cider_total", "ng_correct"} <= names["ngram.h"]
+    for a, b in itertools.combinations(names, 2):
+        assert not names[a] & names[b], (a, b, names[a] & names[b])
+    assert not re.search(r"#define\s+(RW|CE)_(THREADS|WAVES|MAXL|SLOTS|STAGE|UNKNOWN)\b", src["reward.hip"] + src["capeval.hip"])
+    rng = np.random.default_rng(4)
+    refs = {f"c{i}": [rng.integers(0, 50, size=int(rng.integers(1, 12))).tolist() for _ in range(int(rng.integers(1, 5)))] for i in range(9)}
+    ce, rw = capeval.capeval_tables(capeval.CaptionMetrics(refs), list(refs)), scst.reward_tables(scst.CaptionScorer(refs))
+    assert len(lib.RewardTables.POINTERS) == 12 and ce["clips"] == rw["clips"] and ce["ref_len"] == rw["ref_len"]
+    for k in lib.RewardTables.POINTERS:
+        assert ce[k].dtype == rw[k].dtype and np.array_equal(ce[k], rw[k]) and ce[k].size, k
+
+
 class _StubModel:
     """what validate / validate_qa / validate_cap touch of a model: eval / train, the compute_loss=False call, decode_sequence, opts"""
 

@@ -215,6 +215,49 @@ def test_nan_rows_and_refused_arguments(dev):
     assert keep
 
 
+def one_scorer_case(L):
+    """the corpus and the rows of test_the_two_entry_points_are_one_scorer -> (references, int64 [31, L] rows, int32 [31] clip indices).
+    Five clips with 3 references of 3..12 tokens and one with 40 references of 14; per clip an empty row, one token, an exact reference,
+    a row with an id outside the vocabulary (2000) and one repeated token over the full width without an end mark; last, a row of clip -1."""
+    rng = np.random.default_rng(11)
+    word = lambda n: rng.integers(1000, 1200, size=int(n)).tolist()
+    refs = {f"c{i}": [word(rng.integers(3, 13)) for _ in range(3)] for i in range(5)}
+    refs["big"] = [word(14) for _ in range(40)]
+    hyps, clip = [], []
+    for c, r in enumerate(refs.values()):
+        hyps += [[], r[0][:1], r[0], r[1][:2] + [5000] + r[1][2:], r[2][:1] * L]
+        clip += [c] * 5
+    hyps.append(r[0])
+    clip.append(-1)
+    return refs, _pad(hyps, L, rng, lo=1000, hi=1200), np.array(clip, dtype=np.int32)
+
+
+@pytest.mark.parametrize("L", [30, 128])
+def test_the_two_entry_points_are_one_scorer(dev, L):
+    """valor_caption_metrics and valor_caption_reward run one n-gram core (csrc/ngram.h): on the same rows and the same references their
+    CIDEr values, and Bleu_4 / BLEU-4, are the same bits -- through the LDS stage (the small clips) and past it (the clip of ~2000 keys)"""
+    from valor_amd import capeval, kernels as K, scst
+    refs, rows, clip = one_scorer_case(L)
+    T = capeval.capeval_tables(capeval.CaptionMetrics(refs), list(refs))
+    big = list(refs).index("big")
+    assert T["ref_key_ptr"][T["clip_ref_ptr"][big + 1]] - T["ref_key_ptr"][T["clip_ref_ptr"][big]] > 1536
+    keep, st = capeval.upload_tables(T, torch.device(dev))
+    seq, R = torch.from_numpy(rows).to(dev), len(clip)
+    assert (seq[4::5, :] != EOS).all() and seq.shape == (31, L)
+    f64 = torch.zeros((6, R), dtype=torch.float64, device=dev)
+    counts = torch.zeros((R, 10), dtype=torch.int32, device=dev)
+    summary = torch.zeros(16, dtype=torch.int64, device=dev)
+    K.caption_metrics(seq, EOS, 2000, torch.from_numpy(clip).to(dev), st, f64[0], f64[1], f64[2:].view(-1), counts, summary)
+    _, cider, bleu4 = scst.DeviceCaptionScorer(refs, device=dev, vocab=2000).score(clip, seq, EOS, parts=True)
+    bits = lambda t: t.contiguous().view(torch.int64).cpu()
+    print(f"[capeval one scorer L={L}] CIDEr {f64[0, :5].tolist()} .. BLEU-4 {bleu4[:5].tolist()}")
+    assert torch.equal(bits(f64[0]), bits(cider))
+    assert torch.equal(bits(f64[2:].view(R, 4)[:, 3]), bits(bleu4))
+    assert torch.isnan(f64[0, -1]) and torch.isnan(cider[-1]) and torch.isnan(f64[2:].view(R, 4)[-1]).all() and torch.isnan(bleu4[-1])
+    assert torch.isfinite(f64[0, :-1]).all() and (f64[0, 2::5] > 0).all() and (counts[:-1:5, 8] == 0).all() and (counts[4::5, 8] == L).all()
+    assert keep
+
+
 # ------------------------------------------------------------------ end to end: validate_cap / validate_qa on the small synthetic model
 OPTS = {"dropout": 0.0, "drop_path_rate": 0.0, "beam_size": 1, "max_generation_len": 8}
 

@@ -29,7 +29,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import scst
-from .scst import N, _SMALL, _TINY, ngram_counts
+from .scst import N, bleu_values, ngram_counts  # noqa: F401  (bleu_values: importable from here as before)
 
 END = 0
 BETA = 1.2
@@ -75,19 +75,6 @@ def rouge_l(hyp, refs):
     if prec != 0 and rec != 0:
         return ((1 + BETA ** 2) * prec * rec) / float(rec + BETA ** 2 * prec)
     return 0.0
-
-
-def bleu_values(correct, guess, testlen, reflen):
-    """bleu_scorer.py:234-242 / :250-259: Bleu_1..4 from one set of integers (a clip's, or the corpus totals)"""
-    out = []
-    b = 1.0
-    for k in range(N):
-        b *= (float(correct[k]) + _TINY) / (float(guess[k]) + _SMALL)
-        out.append(b ** (1.0 / (k + 1)))
-    ratio = (testlen + _TINY) / (reflen + _SMALL)
-    if ratio < 1:
-        out = [v * np.exp(1 - 1 / ratio) for v in out]
-    return [float(v) for v in out]
 
 
 def _assemble(cider, rouge, correct, guess, testlen, reflen, per_clip=True):
@@ -217,13 +204,10 @@ class CaptionMetrics:
             cider.append(st.cider(cid, h))
             rouge.append(rouge_l(h, self.refs[cid]))
             reflens, maxc = st._bleu_refs[cid]
-            c = [0] * N
-            for g, n in ngram_counts(h).items():
-                c[len(g) - 1] += min(maxc.get(g, 0), n)
-            correct.append(c)
-            guess.append([max(0, len(h) - k) for k in range(N)])
+            correct.append(scst.clipped_counts((len(g) - 1, n, maxc.get(g, 0)) for g, n in ngram_counts(h).items()))
+            guess.append(scst.guesses(len(h)))
             testlen.append(len(h))
-            reflen.append(min((abs(l - len(h)), l) for l in reflens)[1])
+            reflen.append(scst.closest_length(reflens, len(h)))
         return _assemble(cider, rouge, correct, guess, testlen, reflen)
 
     def to_device(self, device="cuda:0", eos=None, vocab=None):
@@ -269,28 +253,12 @@ def metrics_from_tables(tables, clip_idx, seqs, eos, vocab=scst.MAX_VOCAB, per_c
     CapEval. A row is cut at its first `eos`; a symbol outside [0, vocab) matches nothing; a row of a clip without references has NaN
     values and -1 integers, and makes every corpus value NaN."""
     T = tables
-    rows = seqs.tolist() if hasattr(seqs, "tolist") else [list(r) for r in seqs]
-    _, cider, _ = scst.reward_from_tables(T, clip_idx, rows, eos, vocab, parts=True)          # the CIDEr walk is the reward's
-    rouge, correct, guess, testlen, reflen = [], [], [], [], []
-    for r, row in enumerate(rows):
-        row = [int(x) for x in row]
-        hyp = row[:row.index(eos)] if eos in row else row
-        c = int(clip_idx[r])
-        ref0, ref1 = (int(T["clip_ref_ptr"][c]), int(T["clip_ref_ptr"][c + 1])) if 0 <= c < len(T["clip_ref_ptr"]) - 1 else (0, 0)
-        if ref1 <= ref0:
-            rouge.append(np.nan), correct.append([-1] * N), guess.append([-1] * N), testlen.append(-1), reflen.append(-1)
+    cider, rouge, correct, guess, testlen, reflen = [], [], [], [], [], []
+    for hyp, (ref0, ref1), cid, cc, rl in scst.walk_rows(T, clip_idx, seqs, eos, vocab):          # CIDEr and BLEU's integers are the reward's
+        if cc is None:
+            cider.append(np.nan), rouge.append(np.nan), correct.append([-1] * N), guess.append([-1] * N), testlen.append(-1), reflen.append(-1)
             continue
-        b0, b1 = int(T["clip_bleu_ptr"][c]), int(T["clip_bleu_ptr"][c + 1])
-        cc = [0] * N
-        for gram, tf in ngram_counts(hyp).items():
-            if all(0 <= t < vocab for t in gram):
-                j = scst._find(T["bleu_keys"], b0, b1, scst.pack_key(gram))
-                if j >= 0:
-                    cc[len(gram) - 1] += min(int(T["bleu_cnt"][j]), tf)
-        correct.append(cc)
-        guess.append([max(0, len(hyp) - k) for k in range(N)])
-        testlen.append(len(hyp))
-        reflen.append(min((abs(int(l) - len(hyp)), int(l)) for l in T["ref_tokens"][ref0:ref1])[1])
+        cider.append(cid), correct.append(cc), guess.append(scst.guesses(len(hyp))), testlen.append(len(hyp)), reflen.append(rl)
         best, rec = 0, 0.0
         inside = [t if 0 <= t < vocab else None for t in hyp]
         for q in range(ref0, ref1):
@@ -305,26 +273,9 @@ def metrics_from_tables(tables, clip_idx, seqs, eos, vocab=scst.MAX_VOCAB, per_c
 
 
 def upload_tables(T, dev):
-    """the numpy tables of capeval_tables -> (device tensors by field, a lib.CapevalTables of their addresses); keep the tensors alive
-    as long as the struct is used"""
-    import torch
+    """scst.upload_tables for the tables of capeval_tables: (device tensors by field, a lib.CapevalTables of their addresses)"""
     from . import lib
-    if dev.type != "cuda":
-        raise lib.ValorHipError("DeviceCaptionMetrics scores on the GPU (no CPU fallback); CaptionMetrics is the host scorer")
-    st = lib.CapevalTables()
-    keep = {}
-    for k in lib.CapevalTables.POINTERS:
-        a = T[k]
-        if a.size == 0:                                   # an empty list still gets an address
-            a = np.zeros(1, dtype=a.dtype)
-        a = np.ascontiguousarray(a)
-        view = {np.dtype(np.uint64): np.int64, np.dtype(np.uint16): np.int16}.get(a.dtype)
-        keep[k] = torch.from_numpy(a.view(view) if view else a).to(dev)
-        setattr(st, k, keep[k].data_ptr())
-    st.ref_len = T["ref_len"]
-    st.n_global = int(T["g_keys"].size)
-    st.n_clips = len(T["clips"])
-    return keep, st
+    return scst.upload_tables(T, lib.CapevalTables, dev)
 
 
 class DeviceCaptionMetrics:

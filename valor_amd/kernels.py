@@ -543,19 +543,25 @@ def masked_rows(labels, row_off, n, G=1, Ttot=None, r0=0, idx=None, lab_out=None
     return idx, lab_out
 
 
+def _caption_rows(seq, clip_idx):
+    """what caption_reward and caption_metrics ask of their id matrix and clip indices -> (R, L, the row pitch)"""
+    assert seq.dtype == torch.int64 and seq.dim() == 2 and (seq.stride(1) == 1 or seq.shape[1] == 1)
+    R, L = seq.shape
+    assert clip_idx.dtype == torch.int32 and clip_idx.is_contiguous() and clip_idx.numel() == R
+    return R, L, seq.stride(0) if R > 1 else L
+
+
 def caption_reward(seq, eos, vocab, clip_idx, tables, reward, cider=None, bleu=None):
     """CIDEr-D + BLEU-4 of every row of seq int64 [R, L] (row pitch = stride(0), L <= 128) against the references of clip clip_idx[r]
     (valor_caption_reward): tables = a lib.RewardTables of device pointers (scst.DeviceCaptionScorer keeps the tensors alive), reward /
     cider / bleu fp64 [R] (the two parts optional). One launch, nothing read back."""
     import ctypes
     _check_gpu(seq, clip_idx, reward, cider, bleu)
-    assert seq.dtype == torch.int64 and seq.dim() == 2 and (seq.stride(1) == 1 or seq.shape[1] == 1)
-    R, L = seq.shape
-    assert clip_idx.dtype == torch.int32 and clip_idx.is_contiguous() and clip_idx.numel() == R
+    R, L, ld = _caption_rows(seq, clip_idx)
     for t in (reward, cider, bleu):
         assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.numel() == R)
-    lib.call("valor_caption_reward", _stream(), _ptr(seq), seq.stride(0) if R > 1 else L, R, L, int(eos), int(vocab), _ptr(clip_idx),
-             ctypes.addressof(tables), _ptr(reward), _ptr(cider), _ptr(bleu))
+    lib.call("valor_caption_reward", _stream(), _ptr(seq), ld, R, L, int(eos), int(vocab), _ptr(clip_idx), ctypes.addressof(tables),
+             _ptr(reward), _ptr(cider), _ptr(bleu))
 
 
 def caption_metrics(seq, eos, vocab, clip_idx, tables, cider, rouge, bleu, counts, summary):
@@ -565,15 +571,13 @@ def caption_metrics(seq, eos, vocab, clip_idx, tables, cider, rouge, bleu, count
     summary int64 [16] (valor_capeval_summary: six fp64 values, ten int64 totals). Two launches, nothing read back."""
     import ctypes
     _check_gpu(seq, clip_idx, cider, rouge, bleu, counts, summary)
-    assert seq.dtype == torch.int64 and seq.dim() == 2 and (seq.stride(1) == 1 or seq.shape[1] == 1)
-    R, L = seq.shape
-    assert clip_idx.dtype == torch.int32 and clip_idx.is_contiguous() and clip_idx.numel() == R
+    R, L, ld = _caption_rows(seq, clip_idx)
     for t, n in ((cider, R), (rouge, R), (bleu, 4 * R)):
         assert t.dtype == torch.float64 and t.is_contiguous() and t.numel() == n
     assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == 10 * R
     assert summary.dtype == torch.int64 and summary.is_contiguous() and summary.numel() == 16
-    lib.call("valor_caption_metrics", _stream(), _ptr(seq), seq.stride(0) if R > 1 else L, R, L, int(eos), int(vocab), _ptr(clip_idx),
-             ctypes.addressof(tables), _ptr(cider), _ptr(rouge), _ptr(bleu), _ptr(counts), _ptr(summary))
+    lib.call("valor_caption_metrics", _stream(), _ptr(seq), ld, R, L, int(eos), int(vocab), _ptr(clip_idx), ctypes.addressof(tables),
+             _ptr(cider), _ptr(rouge), _ptr(bleu), _ptr(counts), _ptr(summary))
 
 
 def sample_tokens(logits, seed, offset, eos, unfinished, tok, sents, logprobs):

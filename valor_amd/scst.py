@@ -3,7 +3,7 @@
 statistics (CIDEr-D tf-idf vectors and norms, BLEU maximum counts and lengths) are computed ONCE at construction, a call only cooks the
 hypotheses. Host-side numpy / Python: the scorer is the reference's host code too. DeviceCaptionScorer (below) is the same reward on the
 device: the statistics flattened into sorted n-gram key tables, scored by valor_caption_reward (csrc/reward.hip) on id matrices that stay
-there; reward_from_tables walks those tables in numpy.
+there; walk_rows / reward_from_tables walk those tables in numpy.
 
   * CIDEr-D (scorer/cider_scorer.py:119-200): n = 1..4, sigma = 6; idf = ref_len - log(max(1, df)) with df counted over the clips of
     `df_ids` and ref_len = log(#those clips) (precompute_df_reflen_for_cider, scorer/scorer.py:117-147); per n the clipped dot product
@@ -59,6 +59,50 @@ def hypotheses(seq, eos):
         cut = r.index(eos) if eos in r else len(r)
         out.append([int(x) for x in r[:cut]])
     return out
+
+
+def clipped_counts(grams):
+    """BLEU's correct_k, k = 1..4, from (n - 1, the hypothesis' count, the clip's maximum count in one reference) per distinct n-gram"""
+    correct = [0] * N
+    for n, c, m in grams:
+        correct[n] += min(m, c)
+    return correct
+
+
+def guesses(testlen):
+    """BLEU's guess_k = the number of k-grams of a hypothesis of `testlen` tokens"""
+    return [max(0, testlen - k) for k in range(N)]
+
+
+def closest_length(reflens, testlen):
+    """the reference length closest to testlen, ties to the shorter (bleu_scorer.py 'closest')"""
+    return min((abs(int(l) - testlen), int(l)) for l in reflens)[1]
+
+
+def bleu_values(correct, guess, testlen, reflen):
+    """bleu_scorer.py:234-242 / :250-259: Bleu_1..4 from one set of integers (a clip's, or the corpus totals)"""
+    out = []
+    b = 1.0
+    for k in range(N):
+        b *= (float(correct[k]) + _TINY) / (float(guess[k]) + _SMALL)
+        out.append(b ** (1.0 / (k + 1)))
+    ratio = (testlen + _TINY) / (reflen + _SMALL)
+    if ratio < 1:
+        out = [v * np.exp(1 - 1 / ratio) for v in out]
+    return [float(v) for v in out]
+
+
+def _bleu4(correct, testlen, reflen):
+    """the reward's sentence BLEU-4. bleu_values(..)[3] up to the last bit of its brevity penalty: math.exp here, np.exp there, and the
+    two differ by an ulp on some ratios, so the reward keeps its own"""
+    b = 1.0
+    for k in range(N):
+        b *= (float(correct[k]) + _TINY) / (float(max(0, testlen - k)) + _SMALL)
+    b = b ** (1.0 / N)
+    ratio = (testlen + _TINY) / (reflen + _SMALL)
+    if ratio < 1:
+        b *= math.exp(1 - 1 / ratio)
+    return b
 
 
 class CaptionScorer:
@@ -128,19 +172,8 @@ class CaptionScorer:
 
     def bleu4(self, cid, hyp):
         reflens, maxc = self._bleu_refs[cid]
-        testlen = len(hyp)
-        reflen = min((abs(l - testlen), l) for l in reflens)[1]
-        correct = [0] * N
-        for g, c in ngram_counts(hyp).items():
-            correct[len(g) - 1] += min(maxc.get(g, 0), c)
-        b = 1.0
-        for k in range(N):
-            b *= (float(correct[k]) + _TINY) / (float(max(0, testlen - k)) + _SMALL)
-        b = b ** (1.0 / N)
-        ratio = (testlen + _TINY) / (reflen + _SMALL)
-        if ratio < 1:
-            b *= math.exp(1 - 1 / ratio)
-        return b
+        correct = clipped_counts((len(g) - 1, c, maxc.get(g, 0)) for g, c in ngram_counts(hyp).items())
+        return _bleu4(correct, len(hyp), closest_length(reflens, len(hyp)))
 
     def __call__(self, ids, hyps):
         if len(ids) != len(hyps):
@@ -233,20 +266,20 @@ def _find(keys, lo, hi, key):
     return j if j < hi and int(keys[j]) == key else -1
 
 
-def reward_from_tables(tables, clip_idx, seqs, eos, vocab=MAX_VOCAB, parts=False):
-    """The walk valor_caption_reward does, in numpy on the flat tables (the table format checked without a GPU): seqs int [R, L] (or
-    rows of different lengths), clip_idx [R] -> fp64 reward [R] (parts: (reward, CIDEr-D, BLEU-4)). A row is cut at its first `eos`; a
-    token outside [0, vocab) takes the unknown code and matches nothing; a row of a clip without references gets NaN."""
+def walk_rows(tables, clip_idx, seqs, eos, vocab=MAX_VOCAB):
+    """The walk the device kernels do, in numpy on the flat tables (the table format checked without a GPU): seqs int [R, L] (or rows of
+    different lengths), clip_idx [R] -> per row (hyp, (ref0, ref1), CIDEr, correct[4], reflen). A row is cut at its first `eos`: hyp, of
+    len(hyp) tokens; a token outside [0, vocab) takes the unknown code and matches nothing; a row of a clip without references
+    (ref1 <= ref0) has None for its three values."""
     T = tables
     rows = seqs.tolist() if hasattr(seqs, "tolist") else [list(r) for r in seqs]
-    cider, bleu = np.zeros(len(rows)), np.zeros(len(rows))
     for r, row in enumerate(rows):
         row = [int(x) for x in row]
         hyp = row[:row.index(eos)] if eos in row else row
         c = int(clip_idx[r])
         ref0, ref1 = (int(T["clip_ref_ptr"][c]), int(T["clip_ref_ptr"][c + 1])) if 0 <= c < len(T["clip_ref_ptr"]) - 1 else (0, 0)
         if ref1 <= ref0:
-            cider[r] = bleu[r] = np.nan
+            yield hyp, (0, 0), None, None, None
             continue
         # (n, key, tf, x): counted on the raw tokens, so two different unknown tokens stay two n-grams
         grams = []
@@ -275,23 +308,43 @@ def reward_from_tables(tables, clip_idx, seqs, eos, vocab=MAX_VOCAB, parts=False
                 if norm[n] != 0 and T["ref_norm"][q, n] != 0:
                     val[n] /= norm[n] * T["ref_norm"][q, n]
             score += val * math.exp(-(delta * delta) / (2 * SIGMA ** 2))
-        cider[r] = score.sum() / N / (ref1 - ref0) * 10.0
         b0, b1 = int(T["clip_bleu_ptr"][c]), int(T["clip_bleu_ptr"][c + 1])
-        correct = [0] * N
-        for n, key, tf, _ in grams:
-            j = _find(T["bleu_keys"], b0, b1, key)
-            if j >= 0:
-                correct[n] += min(int(T["bleu_cnt"][j]), tf)
-        reflen = min((abs(int(l) - len(hyp)), int(l)) for l in T["ref_tokens"][ref0:ref1])[1]
-        b = 1.0
-        for k in range(N):
-            b *= (float(correct[k]) + _TINY) / (float(max(0, len(hyp) - k)) + _SMALL)
-        b = b ** (1.0 / N)
-        ratio = (len(hyp) + _TINY) / (reflen + _SMALL)
-        if ratio < 1:
-            b *= math.exp(1 - 1 / ratio)
-        bleu[r] = b
+        found = ((n, tf, _find(T["bleu_keys"], b0, b1, key)) for n, key, tf, _ in grams)
+        correct = clipped_counts((n, tf, int(T["bleu_cnt"][j]) if j >= 0 else 0) for n, tf, j in found)
+        yield hyp, (ref0, ref1), score.sum() / N / (ref1 - ref0) * 10.0, correct, closest_length(T["ref_tokens"][ref0:ref1], len(hyp))
+
+
+def reward_from_tables(tables, clip_idx, seqs, eos, vocab=MAX_VOCAB, parts=False):
+    """What valor_caption_reward returns, from walk_rows: fp64 reward [R] (parts: (reward, CIDEr-D, BLEU-4)); NaN for a row of a clip
+    without references."""
+    walk = list(walk_rows(tables, clip_idx, seqs, eos, vocab))
+    cider, bleu = np.zeros(len(walk)), np.zeros(len(walk))
+    for r, (hyp, _, cid, correct, reflen) in enumerate(walk):
+        cider[r], bleu[r] = (np.nan, np.nan) if correct is None else (cid, _bleu4(correct, len(hyp), reflen))
     return (cider + bleu, cider, bleu) if parts else cider + bleu
+
+
+def upload_tables(T, struct_cls, dev):
+    """the numpy tables of reward_tables / capeval.capeval_tables -> (device tensors by field, a struct_cls (lib.RewardTables,
+    lib.CapevalTables) of their addresses); keep the tensors alive as long as the struct is used"""
+    import torch
+    from . import lib
+    if dev.type != "cuda":
+        raise lib.ValorHipError("the device caption scorers score on the GPU (no CPU fallback); CaptionScorer / CaptionMetrics are the host scorers")
+    st = struct_cls()
+    keep = {}
+    for k in struct_cls.POINTERS:
+        a = T[k]
+        if a.size == 0:                                   # an empty list still gets an address
+            a = np.zeros(1, dtype=a.dtype)
+        a = np.ascontiguousarray(a)
+        view = {np.dtype(np.uint64): np.int64, np.dtype(np.uint16): np.int16}.get(a.dtype)          # torch has no unsigned of these widths
+        keep[k] = torch.from_numpy(a.view(view) if view else a).to(dev)
+        setattr(st, k, keep[k].data_ptr())
+    st.ref_len = T["ref_len"]
+    st.n_global = int(T["g_keys"].size)
+    st.n_clips = len(T["clips"])
+    return keep, st
 
 
 class DeviceCaptionScorer:
@@ -343,21 +396,7 @@ class DeviceCaptionScorer:
         import torch
         from . import lib
         dev = torch.device(self.device)
-        if dev.type != "cuda":
-            raise lib.ValorHipError("DeviceCaptionScorer scores on the GPU (no CPU fallback); CaptionScorer is the host scorer")
-        st = lib.RewardTables()
-        keep = {}
-        for k in lib.RewardTables.POINTERS:
-            a = self.tables[k]
-            if a.size == 0:                               # an empty list still gets an address
-                a = np.zeros(1, dtype=a.dtype)
-            a = np.ascontiguousarray(a)
-            keep[k] = torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(dev)
-            setattr(st, k, keep[k].data_ptr())
-        st.ref_len = self.tables["ref_len"]
-        st.n_global = int(self.tables["g_keys"].size)
-        st.n_clips = len(self.tables["clips"])
-        self._dev = (dev, keep, st)
+        self._dev = (dev,) + upload_tables(self.tables, lib.RewardTables, dev)
         return self._dev
 
     def score(self, ids, seq, eos, vocab=None, parts=False):
