@@ -140,6 +140,58 @@ def _sunk(p):
         GradSink.listener(p._arena_name)
 
 
+def _colsum_grad(x2, p, want):
+    """Gradient of a bias-like parameter p = column sums of x2: added into its arena slot and reported (-> None), else returned."""
+    if not want or p is None:
+        return None
+    s = _sink(p)
+    if s is None:
+        return K.colsum(x2)
+    K.colsum(x2, out=s.view(-1), accumulate=True); _sunk(p)
+    return None
+
+
+def _wgrad_bgrad(dy2, x2, pw, pb, want_w, want_b, *, w_is_kn=False, fuse=True):
+    """(dw, db) of y = x W^T + b (w_is_kn: y = x W + b) from dy2 [rows, N] and x2 [rows, K]; None for whatever was written in place.
+    dW = dY^T.X is one split-K GEMM; accumulated into the arena slot, its reduction joins the layer's group (K.ReduceQueue) and the
+    write is reported when that reduction is enqueued. db rides the same GEMM as fused row sums where the kernel offers it (`fuse`,
+    never for w_is_kn) and is a column sum otherwise. A frozen parameter (want_* false) gets no launch at all."""
+    want_b = want_b and pb is not None
+    dw, fused = None, False
+    if want_w:
+        sw, sb = _sink(pw), (_sink(pb) if want_b else None)
+        kw = {}
+        if fuse and not w_is_kn and sb is not None and K.gemm_fuses_rowsum(dy2, x2, True, True):      # db on the matrix pipe beside dW
+            kw.update(rowsum_out=sb, rowsum_accumulate=True); fused = True
+        if sw is not None:
+            kw.update(out=sw, accumulate=True, defer_done=(lambda: (_sunk(pw), _sunk(pb))) if fused else (lambda: _sunk(pw)))
+        a, b = (x2, dy2) if w_is_kn else (dy2, x2)
+        dw = K.gemm(a, b, trans_a=True, trans_b=True, **kw)
+        if sw is not None:
+            dw = None
+        elif fused:
+            _sunk(pb)
+    return dw, (None if fused else _colsum_grad(dy2, pb, want_b))
+
+
+def _slot_grad(slot, shape, produce):
+    """Gradient of an activation whose consumers share `slot` (GradSlot, or None). produce(out, accumulate) is the dgrad launch: into
+    the buffer a sibling already produced (`C +=`, nothing is returned), else into a fresh one that is parked in the slot and returned."""
+    if slot is not None and slot.buf is not None:
+        produce(_2d(slot.buf), True)
+        return None
+    dx = produce(None, False).view(shape)
+    if slot is not None:
+        slot.buf = dx
+    return dx
+
+
+def _inference():
+    """no autograd graph is being built (torch.no_grad: evaluation, generation) and this is not the first run of a checkpointed layer, which
+    must run the kernels its second, differentiated run will (bit-identical activations)"""
+    return not torch.is_grad_enabled() and not CheckpointFn.first_pass
+
+
 # ------------------------------------------------------------------------------------------------
 class CheckpointFn(Function):
     """Activation checkpointing of one layer (the reference's `checkpointing` option: torch.utils.checkpoint around every resblock /
@@ -201,7 +253,7 @@ class LinearFn(Function):
             res = K.gemm(x2, w, bias=b, act=act, want_preact=want_pre, **kw)
         y, pre = res if want_pre else (res, None)
         ctx.save_for_backward(x2, w, pre)
-        ctx.act, ctx.w_is_kn, ctx.has_b, ctx.xshape = act, w_is_kn, b is not None, x.shape
+        ctx.act, ctx.w_is_kn, ctx.xshape = act, w_is_kn, x.shape
         ctx.params = (w, b)
         return y.view(*x.shape[:-1], y.shape[-1])
 
@@ -213,47 +265,15 @@ class LinearFn(Function):
             du = torch.empty_like(dy2)
             lib.call("valor_dact_mul", _st(), _dt(dy2), _p(dy2), _p(pre), _p(du), dy2.numel(), ctx.act)
             dy2 = du
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
-            slot = ctx.slot
-            if slot is not None and slot.buf is not None:          # a sibling already produced a gradient buffer: add into it
-                out2 = _2d(slot.buf)
-                K.gemm(dy2, w, out=out2, accumulate=True) if ctx.w_is_kn else K.gemm(dy2, w, trans_b=True, out=out2, accumulate=True)
-            else:
-                dx = (K.gemm(dy2, w) if ctx.w_is_kn else K.gemm(dy2, w, trans_b=True)).view(ctx.xshape)
-                if slot is not None:
-                    slot.buf = dx
-        pw, pb = ctx.params
-        sb = _sink(pb) if (ctx.has_b and ctx.needs_input_grad[2]) else None
-        fused_b = False
-        if ctx.needs_input_grad[1]:
-            sw = _sink(pw)
-            kw = dict(out=sw, accumulate=True) if sw is not None else {}
-            if ctx.w_is_kn:
-                if sw is not None:
-                    kw["defer_done"] = lambda: _sunk(pw)          # the split-K reduction joins the layer's group (K.ReduceQueue)
-                dw = K.gemm(x2, dy2, trans_a=True, trans_b=True, **kw)
-            else:
-                if sb is not None and K.gemm_fuses_rowsum(dy2, x2, True, True):      # bias gradient on the matrix pipe beside dW
-                    kw.update(rowsum_out=sb, rowsum_accumulate=True); fused_b = True
-                if sw is not None:
-                    kw["defer_done"] = (lambda: (_sunk(pw), _sunk(pb))) if fused_b else (lambda: _sunk(pw))
-                dw = K.gemm(dy2, x2, trans_a=True, trans_b=True, **kw)
-            if sw is not None:
-                dw = None
-        if ctx.has_b and ctx.needs_input_grad[2]:
-            if fused_b:
-                if sw is None:
-                    _sunk(pb)
-            elif sb is not None:
-                K.colsum(dy2, out=sb, accumulate=True); _sunk(pb)
-            else:
-                db = K.colsum(dy2)
+            dx = _slot_grad(ctx.slot, ctx.xshape, lambda out, acc: K.gemm(dy2, w, trans_b=not ctx.w_is_kn, out=out, accumulate=acc))
+        dw, db = _wgrad_bgrad(dy2, x2, *ctx.params, ctx.needs_input_grad[1], ctx.needs_input_grad[2], w_is_kn=ctx.w_is_kn)
         return dx, dw, db, None, None, None, None
 
 
 def linear(x, w, b=None, act=ACT_NONE, w_is_kn=False, grad_slot=None, out=None):
-    if not torch.is_grad_enabled() and not CheckpointFn.first_pass:      # _inference(): no pre-activation copy, few-row products on family 5
+    if _inference():       # no pre-activation copy, few-row products on family 5
         kw = {} if out is None else {"out": _2d(out)}
         y = K.gemm(_2d(x), w, trans_b=w_is_kn, bias=b, act=act, policy=K.infer_policy(), **kw)
         return y.view(*x.shape[:-1], y.shape[-1])
@@ -288,50 +308,13 @@ class MlpFn(Function):
         dy2 = _2d(dy.contiguous())
         du = K.gemm(dy2, w2, trans_b=True, act=ctx.act, dact_aux=u)
         pw1, pb1, pw2, pb2 = ctx.params
-
-        def wgrad_bgrad(dyy, xx, pw, pb):
-            """dW (+ db fused on the matrix pipe where the kernel offers it), accumulated straight into the arena"""
-            sw = _sink(pw)
-            sb = _sink(pb) if pb is not None else None
-            kw, fused = {}, False
-            if sb is not None and K.gemm_fuses_rowsum(dyy, xx, True, True):
-                kw.update(rowsum_out=sb, rowsum_accumulate=True); fused = True
-            if sw is None:
-                dw = K.gemm(dyy, xx, trans_a=True, trans_b=True, **kw)
-                if fused:
-                    _sunk(pb)
-            else:
-                # the split-K reduction of this product joins the layer's group (K.ReduceQueue); the writes are reported when it is enqueued
-                done = (lambda: (_sunk(pw), _sunk(pb))) if fused else (lambda: _sunk(pw))
-                K.gemm(dyy, xx, trans_a=True, trans_b=True, out=sw, accumulate=True, defer_done=done, **kw); dw = None
-            if pb is None:
-                return dw, None
-            if fused:
-                return dw, None
-            if sb is None:
-                return dw, K.colsum(dyy)
-            K.colsum(dyy, out=sb, accumulate=True); _sunk(pb)
-            return dw, None
-
-        # (a frozen weight -- VALOR's frozen_multimodal / frozen_vision -- needs no gradient GEMM at all)
-        dw2, db2 = wgrad_bgrad(dy2, h, pw2, pb2) if (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]) else (None, None)
+        need = ctx.needs_input_grad
+        dw2, db2 = _wgrad_bgrad(dy2, h, pw2, pb2, need[3], need[4])
         dx = None
-        if ctx.needs_input_grad[0]:
-            slot = ctx.slot
-            if slot is not None and slot.buf is not None:          # the residual path already produced x's gradient buffer: add into it
-                K.gemm(du, w1, trans_b=True, out=_2d(slot.buf), accumulate=True)
-            else:
-                dx = K.gemm(du, w1, trans_b=True).view(ctx.xshape)
-                if slot is not None:
-                    slot.buf = dx
-        dw1, db1 = wgrad_bgrad(du, x2, pw1, pb1) if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) else (None, None)
+        if need[0]:          # (with a slot: the residual path may already have produced x's gradient buffer)
+            dx = _slot_grad(ctx.slot, ctx.xshape, lambda out, acc: K.gemm(du, w1, trans_b=True, out=out, accumulate=acc))
+        dw1, db1 = _wgrad_bgrad(du, x2, pw1, pb1, need[1], need[2])
         return dx, dw1, db1, dw2, db2, None, None
-
-
-def _inference():
-    """no autograd graph is being built (torch.no_grad: evaluation, generation) and this is not the first run of a checkpointed layer, which
-    must run the kernels its second, differentiated run will (bit-identical activations)"""
-    return not torch.is_grad_enabled() and not CheckpointFn.first_pass
 
 
 def mlp(x, w1, b1, w2, b2, act, grad_slot=None):
@@ -696,138 +679,18 @@ def _rows_with_slack(n, cols, dtype, device):
     return torch.empty((rows, cols), dtype=dtype, device=device)[:n]
 
 
-class DecoderXentSegFn(Function):
-    """per-segment mean CE over ONE tied-decoder GEMM: rows of segment i are h[sum(n[:i]) : sum(n[:i+1])]; returns one
-    loss per segment (caption / mlm passes share the prediction head, modeling.py:245-254, pretrain.py:444,498)."""
-
-    @staticmethod
-    def forward(ctx, h, w_emb, dec_bias, labels, seg_rows, smoothing=0.0):
-        n, V = h.shape[0], w_emb.shape[0]
-        Vpad = (V + 31) // 32 * 32
-        buf = _rows_with_slack(n, Vpad, h.dtype, h.device)
-        K.gemm(h, w_emb, bias=dec_bias, out=buf[:, :V])
-        loss_rows = torch.empty(n, dtype=torch.float32, device=h.device)
-        lse = torch.empty(n, dtype=torch.float32, device=h.device)
-        ctx.smoothing = float(smoothing)          # LabelSmoothing (pretrain.py:46-61): the caption finetune loss with config.label_smoothing > 0
-        lib.call("valor_xent_smooth_fwd", _st(), _dt(h), _p(buf), _p(labels), _p(loss_rows), _p(lse), n, V, Vpad, ctx.smoothing)
-        losses, r0 = [], 0
-        for nr in seg_rows:
-            l = torch.empty((), dtype=torch.float32, device=h.device)
-            lib.call("valor_mean_f32", _st(), _p(loss_rows[r0:r0 + nr]), nr, _p(l))
-            losses.append(l); r0 += nr
-        ctx.save_for_backward(h, w_emb, labels, lse, buf)
-        ctx.V, ctx.seg_rows = V, tuple(seg_rows)
-        ctx.params = (w_emb, dec_bias)
-        return tuple(losses)
-
-    @staticmethod
-    def backward(ctx, *dlosses):
-        h, w_emb, labels, lse, buf = ctx.saved_tensors
-        V, Vpad = ctx.V, buf.shape[1]
-        r0 = 0
-        for nr, dl in zip(ctx.seg_rows, dlosses):
-            g = dl.to(torch.float32).contiguous() if dl is not None else torch.zeros((), dtype=torch.float32, device=h.device)
-            lib.call("valor_xent_smooth_bwd", _st(), _dt(h), _p(buf[r0:r0 + nr]), _p(labels[r0:r0 + nr]), _p(lse[r0:r0 + nr]), _p(g), 1.0 / nr,
-                     nr, V, Vpad, ctx.smoothing)
-            r0 += nr
-        dlog = buf[:, :V]
-        dh = K.gemm(dlog, w_emb, trans_b=True)
-        pw, pb = ctx.params
-        sw, sb = _sink(pw), _sink(pb)
-        dw = db = None
-        if not ctx.needs_input_grad[1]:            # frozen prediction head (VALOR.frozen_multimodal): no [vocab x hidden] wgrad
-            pass
-        elif sw is not None:
-            K.gemm(dlog, h, trans_a=True, trans_b=True, out=sw, accumulate=True, defer_done=lambda: _sunk(pw))
-        else:
-            dw = K.gemm(dlog, h, trans_a=True, trans_b=True)
-        if not ctx.needs_input_grad[2]:
-            pass
-        elif sb is not None:
-            K.colsum(dlog, out=sb, accumulate=True); _sunk(pb)
-        else:
-            db = K.colsum(dlog)
-        return dh, dw, db, None, None, None
-
-
-def decoder_xent_segments(h, w_emb, dec_bias, labels, seg_rows, smoothing=0.0):
-    return DecoderXentSegFn.apply(h, w_emb, dec_bias, labels, seg_rows, smoothing)
-
-
-class DecoderXentWeightedSegFn(Function):
-    """DecoderXentSegFn with a weight per row: segment i's loss is sum_r w_rows[r] * CE_r / n_i over its rows -- SCST's reward_loss
-    (pretrain.py:166-173: mean over the labelled positions of -reward * logP, the reward of the row's sequence). Forward
-    valor_weighted_mean_f32, backward valor_xent_weighted_bwd: dlogits = (softmax - onehot) * w_r * g / n_i. No label smoothing (the
-    reference's reward loss has none). w_rows: fp32 [n] on the device (no gradient). Outputs: the segment losses, then the per-row CE
-    (fp32 [n] = -logP of each label, non-differentiable)."""
-
-    @staticmethod
-    def forward(ctx, h, w_emb, dec_bias, labels, seg_rows, w_rows):
-        n, V = h.shape[0], w_emb.shape[0]
-        Vpad = (V + 31) // 32 * 32
-        buf = _rows_with_slack(n, Vpad, h.dtype, h.device)
-        K.gemm(h, w_emb, bias=dec_bias, out=buf[:, :V])
-        loss_rows = torch.empty(n, dtype=torch.float32, device=h.device)
-        lse = torch.empty(n, dtype=torch.float32, device=h.device)
-        lib.call("valor_xent_fwd", _st(), _dt(h), _p(buf), _p(labels), _p(loss_rows), _p(lse), n, V, Vpad)
-        losses, r0 = [], 0
-        for nr in seg_rows:
-            l = torch.empty((), dtype=torch.float32, device=h.device)
-            lib.call("valor_weighted_mean_f32", _st(), _p(loss_rows[r0:r0 + nr]), _p(w_rows[r0:r0 + nr]), nr, _p(l))
-            losses.append(l); r0 += nr
-        ctx.save_for_backward(h, w_emb, labels, lse, buf, w_rows)
-        ctx.V, ctx.seg_rows = V, tuple(seg_rows)
-        ctx.params = (w_emb, dec_bias)
-        ctx.mark_non_differentiable(loss_rows)
-        return tuple(losses) + (loss_rows,)
-
-    @staticmethod
-    def backward(ctx, *dlosses):
-        h, w_emb, labels, lse, buf, w_rows = ctx.saved_tensors
-        V, Vpad = ctx.V, buf.shape[1]
-        r0 = 0
-        for nr, dl in zip(ctx.seg_rows, dlosses[:len(ctx.seg_rows)]):        # (the last output, the per-row CE, has no gradient)
-            g = dl.to(torch.float32).contiguous() if dl is not None else torch.zeros((), dtype=torch.float32, device=h.device)
-            lib.call("valor_xent_weighted_bwd", _st(), _dt(h), _p(buf[r0:r0 + nr]), _p(labels[r0:r0 + nr]), _p(lse[r0:r0 + nr]),
-                     _p(w_rows[r0:r0 + nr]), _p(g), 1.0 / nr, nr, V, Vpad)
-            r0 += nr
-        dlog = buf[:, :V]
-        dh = K.gemm(dlog, w_emb, trans_b=True)
-        pw, pb = ctx.params
-        sw, sb = _sink(pw), _sink(pb)
-        dw = db = None
-        if not ctx.needs_input_grad[1]:
-            pass
-        elif sw is not None:
-            K.gemm(dlog, h, trans_a=True, trans_b=True, out=sw, accumulate=True, defer_done=lambda: _sunk(pw))
-        else:
-            dw = K.gemm(dlog, h, trans_a=True, trans_b=True)
-        if not ctx.needs_input_grad[2]:
-            pass
-        elif sb is not None:
-            K.colsum(dlog, out=sb, accumulate=True); _sunk(pb)
-        else:
-            db = K.colsum(dlog)
-        return dh, dw, db, None, None, None
-
-
-def decoder_xent_weighted_segments(h, w_emb, dec_bias, labels, seg_rows, w_rows, loss_rows_out=None):
-    """per-segment reward-weighted CE (DecoderXentWeightedSegFn); loss_rows_out: a list that receives the per-row -logP tensor"""
-    *losses, rows = DecoderXentWeightedSegFn.apply(h, w_emb, dec_bias, labels, seg_rows, w_rows)
-    if loss_rows_out is not None:
-        loss_rows_out.append(rows)
-    return tuple(losses)
-
-
-# ------------------------------------------------------------------------------------------------
 class DecoderXentFn(Function):
-    """loss = mean CE(h W_emb^T + b, labels): tied-decoder GEMM (modeling.py:253, weight = word embeddings
-    :241) + fused softmax cross-entropy (pretrain.py:444). Logits live in a zero-padded [n, Vpad] buffer that
-    backward overwrites in place with d(logits)."""
+    """Per-segment mean CE over ONE tied-decoder GEMM (modeling.py:245-254, weight = word embeddings :241; pretrain.py:444,498): rows of
+    segment i are h[sum(n[:i]) : sum(n[:i+1])], one loss per segment (the caption / mlm passes share the prediction head). The logits
+    live in a zero-padded [n, Vpad] buffer that backward overwrites in place with d(logits).
+    w_rows None: label-smoothed CE (LabelSmoothing, pretrain.py:46-61; smoothing 0 = plain CE). w_rows fp32 [n] on the device (no
+    gradient): segment i's loss is sum_r w_rows[r] * CE_r / n_i -- SCST's reward_loss (pretrain.py:166-173: mean over the labelled
+    positions of -reward * logP), dlogits = (softmax - onehot) * w_r * g / n_i, no smoothing (the reference's reward loss has none).
+    Outputs: the segment losses; then, non-differentiable, the per-row CE (fp32 [n] = -logP of each label) if w_rows is given and the
+    logits if want_logits."""
 
     @staticmethod
-    def forward(ctx, h, w_emb, dec_bias, labels, want_logits, smoothing=0.0):
-        ctx.smoothing = float(smoothing)
+    def forward(ctx, h, w_emb, dec_bias, labels, seg_rows, w_rows, smoothing, want_logits):
         n, V = h.shape[0], w_emb.shape[0]
         Vpad = (V + 31) // 32 * 32
         buf = _rows_with_slack(n, Vpad, h.dtype, h.device)
@@ -835,45 +698,65 @@ class DecoderXentFn(Function):
         K.gemm(h, w_emb, bias=dec_bias, out=logits)
         loss_rows = torch.empty(n, dtype=torch.float32, device=h.device)
         lse = torch.empty(n, dtype=torch.float32, device=h.device)
-        lib.call("valor_xent_smooth_fwd", _st(), _dt(h), _p(buf), _p(labels), _p(loss_rows), _p(lse), n, V, Vpad, ctx.smoothing)
-        loss = torch.empty((), dtype=torch.float32, device=h.device)
-        lib.call("valor_mean_f32", _st(), _p(loss_rows), n, _p(loss))
-        ctx.save_for_backward(h, w_emb, labels, lse, buf)
-        ctx.V = V
+        ctx.smoothing = float(smoothing)
+        if w_rows is None:
+            lib.call("valor_xent_smooth_fwd", _st(), _dt(h), _p(buf), _p(labels), _p(loss_rows), _p(lse), n, V, Vpad, ctx.smoothing)
+        else:
+            lib.call("valor_xent_fwd", _st(), _dt(h), _p(buf), _p(labels), _p(loss_rows), _p(lse), n, V, Vpad)
+        losses, r0 = [], 0
+        for nr in seg_rows:
+            l = torch.empty((), dtype=torch.float32, device=h.device)
+            if w_rows is None:
+                lib.call("valor_mean_f32", _st(), _p(loss_rows[r0:r0 + nr]), nr, _p(l))
+            else:
+                lib.call("valor_weighted_mean_f32", _st(), _p(loss_rows[r0:r0 + nr]), _p(w_rows[r0:r0 + nr]), nr, _p(l))
+            losses.append(l); r0 += nr
+        ctx.save_for_backward(h, w_emb, labels, lse, buf, w_rows)
+        ctx.V, ctx.seg_rows = V, tuple(seg_rows)
         ctx.params = (w_emb, dec_bias)
-        if want_logits:
-            ctx.mark_non_differentiable(logits)
-            return loss, logits
-        return loss
+        extra = ((loss_rows,) if w_rows is not None else ()) + ((logits,) if want_logits else ())
+        ctx.mark_non_differentiable(*extra)
+        return (*losses, *extra)
 
     @staticmethod
-    def backward(ctx, dloss, *_):
-        h, w_emb, labels, lse, buf = ctx.saved_tensors
-        n, V, Vpad = h.shape[0], ctx.V, buf.shape[1]
-        g = dloss.to(torch.float32).contiguous()
-        lib.call("valor_xent_smooth_bwd", _st(), _dt(h), _p(buf), _p(labels), _p(lse), _p(g), 1.0 / n, n, V, Vpad, ctx.smoothing)
+    def backward(ctx, *douts):
+        h, w_emb, labels, lse, buf, w_rows = ctx.saved_tensors
+        V, Vpad = ctx.V, buf.shape[1]
+        r0 = 0
+        for nr, dl in zip(ctx.seg_rows, douts):        # (the outputs behind the segment losses have no gradient; an unused loss: zero)
+            g = dl.to(torch.float32).contiguous() if dl is not None else torch.zeros((), dtype=torch.float32, device=h.device)
+            rows = slice(r0, r0 + nr)
+            if w_rows is None:
+                lib.call("valor_xent_smooth_bwd", _st(), _dt(h), _p(buf[rows]), _p(labels[rows]), _p(lse[rows]), _p(g), 1.0 / nr,
+                         nr, V, Vpad, ctx.smoothing)
+            else:
+                lib.call("valor_xent_weighted_bwd", _st(), _dt(h), _p(buf[rows]), _p(labels[rows]), _p(lse[rows]), _p(w_rows[rows]), _p(g),
+                         1.0 / nr, nr, V, Vpad)
+            r0 += nr
         dlog = buf[:, :V]
         dh = K.gemm(dlog, w_emb, trans_b=True)
-        pw, pb = ctx.params
-        sw, sb = _sink(pw), _sink(pb)
-        dw = db = None
-        if not ctx.needs_input_grad[1]:            # frozen prediction head (VALOR.frozen_multimodal): no [vocab x hidden] wgrad
-            pass
-        elif sw is not None:
-            K.gemm(dlog, h, trans_a=True, trans_b=True, out=sw, accumulate=True, defer_done=lambda: _sunk(pw))
-        else:
-            dw = K.gemm(dlog, h, trans_a=True, trans_b=True)
-        if not ctx.needs_input_grad[2]:
-            pass
-        elif sb is not None:
-            K.colsum(dlog, out=sb, accumulate=True); _sunk(pb)
-        else:
-            db = K.colsum(dlog)
-        return dh, dw, db, None, None, None
+        # (a frozen prediction head -- VALOR.frozen_multimodal -- gets no [vocab x hidden] wgrad)
+        dw, db = _wgrad_bgrad(dlog, h, *ctx.params, ctx.needs_input_grad[1], ctx.needs_input_grad[2], fuse=False)
+        return dh, dw, db, None, None, None, None, None
+
+
+def decoder_xent_segments(h, w_emb, dec_bias, labels, seg_rows, smoothing=0.0):
+    """one mean (label-smoothed) CE per row segment"""
+    return DecoderXentFn.apply(h, w_emb, dec_bias, labels, seg_rows, None, smoothing, False)
+
+
+def decoder_xent_weighted_segments(h, w_emb, dec_bias, labels, seg_rows, w_rows, loss_rows_out=None):
+    """per-segment reward-weighted CE; loss_rows_out: a list that receives the per-row -logP tensor"""
+    *losses, rows = DecoderXentFn.apply(h, w_emb, dec_bias, labels, seg_rows, w_rows, 0.0, False)
+    if loss_rows_out is not None:
+        loss_rows_out.append(rows)
+    return tuple(losses)
 
 
 def decoder_xent(h, w_emb, dec_bias, labels, want_logits=False, smoothing=0.0):
-    return DecoderXentFn.apply(h, w_emb, dec_bias, labels, want_logits, smoothing)
+    """loss = mean CE(h W_emb^T + b, labels) over all rows (pretrain.py:444), or (loss, logits)"""
+    out = DecoderXentFn.apply(h, w_emb, dec_bias, labels, [h.shape[0]], None, smoothing, want_logits)
+    return out if want_logits else out[0]
 
 
 def decoder_logits(h, w_emb, dec_bias):
@@ -1122,18 +1005,18 @@ class EmbedFn(Function):
         out = torch.empty((n, E), dtype=word.dtype, device=word.device)
         lib.call("valor_embed_fwd", _st(), _dt(word), _p(ids), _p(word), _p(pos), _p(typevec), _p(out), n, L, E)
         ctx.save_for_backward(ids)
-        ctx.cfg = (word.shape, pos.shape if pos is not None else None, typevec is not None, L)
+        ctx.cfg = (word.shape, pos.shape if pos is not None else None, L)
         ctx.params = (word, pos, typevec)
         return out.view(*ids.shape, E)
 
     @staticmethod
     def backward(ctx, dout):
         (ids,) = ctx.saved_tensors
-        wshape, pshape, has_type, L = ctx.cfg
+        wshape, pshape, L = ctx.cfg
         pw, pp, pt = ctx.params
         d2 = _2d(dout.contiguous())
         n, E = d2.shape
-        dword = dpos = dtype_vec = None
+        dword = dpos = None
         if ctx.needs_input_grad[1]:
             sw = _sink(pw)
             if sw is not None:
@@ -1148,13 +1031,7 @@ class EmbedFn(Function):
             else:
                 dpos = torch.zeros(pshape, dtype=d2.dtype, device=d2.device)
                 lib.call("valor_sum_over_batch", _st(), _dt(d2), _p(d2), _p(dpos), n // L, L, E, 0)
-        if has_type and ctx.needs_input_grad[3]:
-            st_ = _sink(pt)
-            if st_ is not None:
-                K.colsum(d2, out=st_.view(-1), accumulate=True); _sunk(pt)
-            else:
-                dtype_vec = K.colsum(d2)
-        return None, dword, dpos, dtype_vec, None
+        return None, dword, dpos, _colsum_grad(d2, pt, ctx.needs_input_grad[3]), None
 
 
 def embed(ids, word, pos, typevec, L):
@@ -1170,18 +1047,18 @@ class AssembleFn(Function):
         E = patches.shape[-1]
         out = torch.empty((N, Pn + 1, E), dtype=patches.dtype, device=patches.device)
         lib.call("valor_assemble_tokens_fwd", _st(), _dt(patches), _p(patches), _p(cls), _p(pos), _p(bias), _p(out), N, Pn, E)
-        ctx.cfg = (N, Pn, E, bias is not None, cls.shape, pos.shape)
+        ctx.cfg = (N, Pn, E, cls.shape, pos.shape)
         ctx.params = (cls, pos, bias)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        N, Pn, E, has_bias, cshape, pshape = ctx.cfg
+        N, Pn, E, cshape, pshape = ctx.cfg
         pc, pp, pb = ctx.params
         dout = dout.contiguous()
         dpatch = torch.empty((N * Pn, E), dtype=dout.dtype, device=dout.device)
         sc, sp = _sink(pc), _sink(pp)
-        dcls = dposr = dbias = None
+        dcls = dposr = None
         if sc is not None and sp is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
             lib.call("valor_assemble_tokens_bwd", _st(), _dt(dout), _p(dout), _p(dpatch), _p(sp), _p(sc), N, Pn, E, 1)
             _sunk(pc); _sunk(pp)
@@ -1189,13 +1066,7 @@ class AssembleFn(Function):
             dpos = torch.empty((Pn + 1, E), dtype=dout.dtype, device=dout.device)
             lib.call("valor_assemble_tokens_bwd", _st(), _dt(dout), _p(dout), _p(dpatch), _p(dpos), None, N, Pn, E, 0)
             dcls, dposr = dpos[0].clone().view(cshape), dpos.view(pshape)
-        if has_bias and ctx.needs_input_grad[3]:
-            sb = _sink(pb)
-            if sb is not None:
-                K.colsum(dpatch, out=sb, accumulate=True); _sunk(pb)
-            else:
-                dbias = K.colsum(dpatch)
-        return dpatch, dcls, dposr, dbias, None, None
+        return dpatch, dcls, dposr, _colsum_grad(dpatch, pb, ctx.needs_input_grad[3]), None, None
 
 
 def assemble_tokens(patches, cls, pos, bias, N, Pn):
