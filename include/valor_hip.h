@@ -320,7 +320,9 @@ int valor_reducer_destroy(void* reducer);
 
 /* ---- softmax cross-entropy over the vocabulary: F.cross_entropy on the masked rows (pretrain.py:444,457,469,498).
  * logits [rows, V] with leading dim ld; backward overwrites the logits (and zero-fills the ld padding) with
- * (softmax - onehot) * (*gscale_dev) * gmul. */
+ * (softmax - onehot) * (*gscale_dev) * gmul.
+ * A label outside [0, V) marks an ignored row: loss_rows = 0, lse is still written, and every backward entry point below writes exact
+ * zeros over that row (padding included). The other rows are not renormalised by the number of valid rows: gmul is the caller's. */
 int valor_xent_fwd(void* stream, int dtype, const void* logits, const int64_t* labels, float* loss_rows, float* lse,
                    int64_t rows, int V, int64_t ld);
 int valor_xent_bwd(void* stream, int dtype, void* logits_inout, const int64_t* labels, const float* lse,

@@ -413,7 +413,7 @@ extern "C" int valor_group_mean_bwd(void* stream, int dtype, const void* dout, v
 extern "C" int valor_assemble_tokens_fwd(void* stream, int dtype, const void* patches, const void* cls, const void* pos,
                                          const void* bias, void* out, int N, int Pn, int E) {
     if (N <= 0) return VALOR_OK;
-    if (E & 3) return VALOR_ERR_ARG;
+    if (!patches || !cls || !pos || !out || Pn < 0 || (E & 3)) return VALOR_ERR_ARG;   // bias is optional
     hipStream_t st = (hipStream_t)stream;
     const int64_t work = (int64_t)N * (Pn + 1) * E / 4;
     DISPATCH_T(dtype,
@@ -425,7 +425,7 @@ extern "C" int valor_assemble_tokens_fwd(void* stream, int dtype, const void* pa
 extern "C" int valor_assemble_tokens_bwd(void* stream, int dtype, const void* dout, void* dpatches, void* dpos, void* dcls, int N, int Pn, int E,
                                          int accumulate) {
     if (N <= 0) return VALOR_OK;
-    if (E & 3) return VALOR_ERR_ARG;
+    if (!dout || !dpatches || !dpos || Pn < 0 || (E & 3)) return VALOR_ERR_ARG;        // dcls is optional
     hipStream_t st = (hipStream_t)stream;
     const int64_t work = (int64_t)N * Pn * E / 4, work2 = (int64_t)(Pn + 1) * E / 4;
     DISPATCH_T(dtype,
@@ -438,7 +438,7 @@ extern "C" int valor_assemble_tokens_bwd(void* stream, int dtype, const void* do
 // dsum[Tn, E] (+)= sum over n of x[N, Tn, E]
 extern "C" int valor_sum_over_batch(void* stream, int dtype, const void* x, void* dsum, int N, int Tn, int E, int accumulate) {
     if (Tn <= 0) return VALOR_OK;
-    if (E & 3) return VALOR_ERR_ARG;
+    if (!x || !dsum || (E & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t work = (int64_t)Tn * E / 4;
     DISPATCH_T(dtype,
@@ -460,7 +460,7 @@ extern "C" int valor_embed_fwd(void* stream, int dtype, const int64_t* ids, cons
 // rows of occurring ids are written (dword [V, E] zero-initialised by the caller) or, with accumulate, added to
 extern "C" int valor_embed_bwd_word(void* stream, int dtype, const int64_t* ids, const void* dout, void* dword, int64_t n, int E, int accumulate) {
     if (n <= 0) return VALOR_OK;
-    if (E & 3) return VALOR_ERR_ARG;
+    if (!ids || !dout || !dword || (E & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((embed_bwd_word_kernel<bf16_t>), dim3((unsigned)n), dim3(256), 0, st, ids, (const bf16_t*)dout, (bf16_t*)dword, n, E, accumulate),
@@ -470,8 +470,8 @@ extern "C" int valor_embed_bwd_word(void* stream, int dtype, const int64_t* ids,
 
 extern "C" int valor_add_frame_type_fwd(void* stream, int dtype, const void* in, const void* frame_emb, const void* type_emb,
                                         void* out, int Bn, int F, int X, int E, int64_t out_bs, int64_t out_row_off) {
-    if (Bn <= 0) return VALOR_OK;
-    if (E & 3) return VALOR_ERR_ARG;
+    if (Bn <= 0 || F <= 0 || X <= 0) return VALOR_OK;
+    if (!in || !frame_emb || !type_emb || !out || (E & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t work = (int64_t)Bn * F * X * E / 4;
     DISPATCH_T(dtype,
@@ -482,8 +482,8 @@ extern "C" int valor_add_frame_type_fwd(void* stream, int dtype, const void* in,
 // din [Bn,F,X,E] = slice of dout ; dframe [F,E] = sum_{b,x} din
 extern "C" int valor_add_frame_type_bwd(void* stream, int dtype, const void* dout, void* din, void* dframe, float* part, int Bn, int F, int X,
                                         int E, int64_t out_bs, int64_t out_row_off) {
-    if (Bn <= 0) return VALOR_OK;
-    if (E & 3) return VALOR_ERR_ARG;
+    if (Bn <= 0 || F <= 0 || X <= 0) return VALOR_OK;
+    if (!dout || !din || !dframe || (E & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t work = (int64_t)Bn * F * X * E / 4;
     if (!part) return VALOR_ERR_ARG;   // fp32 scratch >= 64 * F * E floats
@@ -499,7 +499,7 @@ extern "C" int valor_add_frame_type_bwd(void* stream, int dtype, const void* dou
 
 extern "C" int valor_l2norm_fwd(void* stream, int dtype, const void* x, void* y, float* norm, int64_t rows, int cols) {
     if (rows <= 0) return VALOR_OK;
-    if (cols & 3) return VALOR_ERR_ARG;
+    if (!x || !y || !norm || (cols & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((l2norm_fwd_kernel<bf16_t>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, norm, rows, cols),
@@ -508,7 +508,7 @@ extern "C" int valor_l2norm_fwd(void* stream, int dtype, const void* x, void* y,
 }
 extern "C" int valor_l2norm_bwd(void* stream, int dtype, const void* y, const void* dy, const float* norm, void* dx, int64_t rows, int cols) {
     if (rows <= 0) return VALOR_OK;
-    if (cols & 3) return VALOR_ERR_ARG;
+    if (!y || !dy || !norm || !dx || (cols & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((l2norm_bwd_kernel<bf16_t>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, (const bf16_t*)y, (const bf16_t*)dy, norm, (bf16_t*)dx, rows, cols),
@@ -518,7 +518,7 @@ extern "C" int valor_l2norm_bwd(void* stream, int dtype, const void* y, const vo
 
 extern "C" int valor_gather_rows(void* stream, int dtype, const void* src, const int64_t* idx, void* out, int64_t n, int E, int64_t src_ld) {
     if (n <= 0) return VALOR_OK;
-    if ((E & 3) || (src_ld & 3)) return VALOR_ERR_ARG;
+    if (!src || !idx || !out || (E & 3) || (src_ld & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((gather_rows_kernel<bf16_t>), dim3(grid_for(n * E / 4)), dim3(256), 0, st, (const bf16_t*)src, idx, (bf16_t*)out, n, E, src_ld),
@@ -527,7 +527,7 @@ extern "C" int valor_gather_rows(void* stream, int dtype, const void* src, const
 }
 extern "C" int valor_scatter_rows(void* stream, int dtype, const void* src, const int64_t* idx, void* dst, int64_t n, int E, int64_t dst_ld) {
     if (n <= 0) return VALOR_OK;
-    if ((E & 3) || (dst_ld & 3)) return VALOR_ERR_ARG;
+    if (!src || !idx || !dst || (E & 3) || (dst_ld & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((scatter_rows_kernel<bf16_t>), dim3(grid_for(n * E / 4)), dim3(256), 0, st, (const bf16_t*)src, idx, (bf16_t*)dst, n, E, dst_ld),
@@ -536,7 +536,7 @@ extern "C" int valor_scatter_rows(void* stream, int dtype, const void* src, cons
 }
 extern "C" int valor_cast_from_f32(void* stream, int dtype, const float* in, void* out, int64_t n) {
     if (n <= 0) return VALOR_OK;
-    if (n & 3) return VALOR_ERR_ARG;
+    if (!in || !out || (n & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((cast_from_f32_kernel<bf16_t>), dim3(grid_for(n / 4)), dim3(256), 0, st, in, (bf16_t*)out, n / 4),
@@ -557,7 +557,7 @@ __global__ void dact_mul_kernel(const T* dh, const T* u, T* du, int64_t n4, int 
 }
 extern "C" int valor_dact_mul(void* stream, int dtype, const void* dh, const void* u, void* du, int64_t n, int act) {
     if (n <= 0) return VALOR_OK;
-    if (n & 3) return VALOR_ERR_ARG;
+    if (!dh || !u || !du || (n & 3)) return VALOR_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((dact_mul_kernel<bf16_t>), dim3(grid_for(n / 4)), dim3(256), 0, st, (const bf16_t*)dh, (const bf16_t*)u, (bf16_t*)du, n / 4, act),
@@ -639,7 +639,7 @@ __global__ __launch_bounds__(1024) void rowdot_bwd_dw_kernel(const T* dy, const 
 }
 extern "C" int valor_rowdot_fwd(void* stream, int dtype, const void* x, const void* w, const void* b, void* y, int64_t rows, int cols) {
     if (rows <= 0) return VALOR_OK;
-    if (cols & 3) return VALOR_ERR_ARG;
+    if (!x || !w || !y || (cols & 3)) return VALOR_ERR_ARG;                            // b is optional
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         hipLaunchKernelGGL((rowdot_fwd_kernel<bf16_t>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, rows, cols),
@@ -649,7 +649,7 @@ extern "C" int valor_rowdot_fwd(void* stream, int dtype, const void* x, const vo
 extern "C" int valor_rowdot_bwd(void* stream, int dtype, const void* dy, const void* x, const void* w, void* dx, void* dw, void* db,
                                 int64_t rows, int cols) {
     if (rows <= 0) return VALOR_OK;
-    if (cols & 3) return VALOR_ERR_ARG;
+    if (!dy || !x || !w || !dx || !dw || (cols & 3)) return VALOR_ERR_ARG;             // db is optional
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype,
         { hipLaunchKernelGGL((rowdot_bwd_dx_kernel<bf16_t>), dim3(grid_for(rows * cols / 4)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)w, (bf16_t*)dx, rows, cols);

@@ -5,6 +5,8 @@
 //   backward: dlogits[i, j] = (exp(logits[i,j] - lse[i]) - [j == label[i]]) * g,
 //             g = (*gscale_dev) * gmul     (upstream scalar grad stays on the device: no host sync)
 //             written IN PLACE over the logits (also zero-fills the ld padding).
+//   A label outside [0, V) marks an ignored row: loss[i] = 0 (lse[i] is still written) and dlogits[i, :ld] = 0 in every backward entry
+//   point. The other rows are not renormalised by the count of valid rows: that factor is the caller's (gmul).
 //   weighted backward (valor_xent_weighted_bwd): g_i = (*gscale_dev) * gmul * w_rows[i] -- the reward-weighted caption loss of SCST
 //             (pretrain.py:166-173, mean over labelled positions of -r_i logP): dlogits = (softmax - onehot) * r_i * g / N.
 // Label smoothing (LabelSmoothing of model/pretrain.py:46-61, the caption finetune loss when config.label_smoothing > 0, :839-840): the
@@ -62,6 +64,10 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(T* logits, const int64_t*
     const int64_t lab = labels[row];
     float g = (gscale_dev ? *gscale_dev : 1.0f) * gmul;
     if (w_rows) g *= w_rows[row];
+    if (lab < 0 || lab >= V) {                  // an ignored row (the forward gave it loss 0): no gradient, exact zeros whatever g and the logits hold
+        for (int j = threadIdx.x; j < (int)ld; j += 256) x[j] = from_f32<T>(0.f);
+        return;
+    }
     const float t_other = eps > 0.f ? eps / (float)(V - 1) : 0.f, t_label = 1.0f - eps;
     for (int j = threadIdx.x; j < (int)ld; j += 256) {
         float d = 0.f;
