@@ -10,8 +10,14 @@
     :520-528), CLIP (:560-573 + clip.py:470-515), VideoSwin (:591-600) and BERT + prediction head (:613-660) key mappings into
     VALOR state-dict keys -- load_pretrained_components() merges them into ONE dict for VALOR.from_pretrained(opts, dict).
 The optimizer side (`optimizer_step_N.pt`, --resume) is FusedAdamW.load_reference_state_dict / reference_state_dict.
+
+  * save_run / latest_step / resume_run: exact-resume checkpoints of a training run in the reference's layout (utils/save.py:38-64,
+    train_utils.py:174-192) plus one engine file per rank -- see the section at the end of this file.
 """
 import os
+import re
+import threading
+import time
 
 import torch
 import torch.nn.functional as F
@@ -160,3 +166,234 @@ def load_pretrained_components(opts, root="./pretrained_weights", load=None, jit
     if get("initial_multimodal", True):
         sd.update(bert_to_valor(load(os.path.join(root, PRETRAINED_FILES[get("multimodal_encoder_type", "bert_base_uncased")]))))
     return sd
+
+
+# ------------------------------------------------------------------------------------------ exact-resume checkpoints of a run
+# output_dir/ckpt/model_step_N.pt            model.state_dict(), the reference's keys (utils/save.py:45-49; VALOR.from_pretrained loads it)
+#                 optimizer_step_N.pt        the NATIVE optimizer.state_dict(): per-tensor {step, exp_avg, exp_avg_sq} + the fp32 masters
+#                 engine_step_N.rank{r}.pt   TrainEngine.state_dict(): step counters and every RNG stream, one file per rank
+# Rank 0 writes the first two. Every file is written under a temporary name (`tmp.<pid>.<name>`: neither latest_step nor the reference's
+# `startswith('model')` / `startswith('optimizer')` listings see it) and renamed, so a killed process leaves no half-written step behind.
+# Not restored: the position of the data loader (the caller's), and -- for a checkpoint without an engine file, e.g. one the reference
+# wrote -- the RNG streams (resume_run(allow_inexact=True)).
+_STEP_FILE = {"model": re.compile(r"model_step_(\d+)\.pt"), "optimizer": re.compile(r"optimizer_step_(\d+)\.pt"),
+              "engine": re.compile(r"engine_step_(\d+)\.rank(\d+)\.pt")}
+
+
+def _rank():
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def run_files(output_dir, step, rank=None):
+    """the three files of step N for this rank: {'model' | 'optimizer' | 'engine': path}"""
+    d = os.path.join(output_dir, "ckpt")
+    rank = _rank() if rank is None else rank
+    return {"model": os.path.join(d, f"model_step_{step}.pt"), "optimizer": os.path.join(d, f"optimizer_step_{step}.pt"),
+            "engine": os.path.join(d, f"engine_step_{step}.rank{rank}.pt")}
+
+
+def latest_step(output_dir, rank=None, need_engine=True):
+    """load_from_resume's step discovery (train_utils.py:174-187) restated: the largest N for which model_step_N.pt, optimizer_step_N.pt
+    and this rank's engine file all exist (need_engine=False: the first two, a checkpoint the reference wrote), or None. Temporary files
+    of an interrupted save and steps with a file missing are ignored."""
+    d = os.path.join(output_dir, "ckpt")
+    if not os.path.isdir(d):
+        return None
+    rank = _rank() if rank is None else rank
+    seen = {k: set() for k in _STEP_FILE}
+    for name in os.listdir(d):
+        for kind, pat in _STEP_FILE.items():
+            m = pat.fullmatch(name)
+            if m and (kind != "engine" or int(m.group(2)) == rank):
+                seen[kind].add(int(m.group(1)))
+    steps = seen["model"] & seen["optimizer"]
+    if need_engine:
+        steps &= seen["engine"]
+    return max(steps) if steps else None
+
+
+def _write(obj, path):
+    tmp = os.path.join(os.path.dirname(path), f"tmp.{os.getpid()}.{os.path.basename(path)}")
+    torch.save(obj, tmp)
+    os.replace(tmp, path)
+
+
+def _remove_older(output_dir, step, rank, kinds):
+    """opts.remove_before_ckpt (utils/save.py:40-44,60-63) -- but AFTER the new step's files are complete, so there is always one whole
+    checkpoint on disk. Rank 0 owns the model / optimizer files, every rank its own engine files."""
+    d = os.path.join(output_dir, "ckpt")
+    for name in os.listdir(d):
+        for kind in kinds:
+            m = _STEP_FILE[kind].fullmatch(name)
+            if m and int(m.group(1)) != step and (kind != "engine" or int(m.group(2)) == rank):
+                os.remove(os.path.join(d, name))
+
+
+def _host_copy(sd):
+    """tensors of a (nested) state dict on the host, compact (a view of the arena becomes a tensor of its own size); keys that alias one
+    tensor (the tied decoder weight, txt_encoder.* of the shared BERT) keep sharing one copy"""
+    memo = {}
+
+    def go(x):
+        if isinstance(x, torch.Tensor):
+            key = (x.data_ptr(), tuple(x.shape), tuple(x.stride()), x.dtype, x.device)
+            if key not in memo:
+                memo[key] = x.detach().cpu().contiguous() if x.device.type != "cpu" else x.detach().clone()
+            return memo[key]
+        if isinstance(x, dict):
+            return {k: go(v) for k, v in x.items()}
+        if isinstance(x, (list, tuple)):
+            return type(x)(go(v) for v in x)
+        return x
+    return go(sd)
+
+
+class SaveHandle:
+    """what save_run returns: wait() blocks until the files are complete and re-raises what the writer raised"""
+
+    def __init__(self, step, files):
+        self.step, self.files, self._thread, self._error = step, files, None, None
+        self._t0 = time.perf_counter()
+        self.seconds = None               # wall time from the save_run call until the files were complete
+
+    def _finished(self):
+        self.seconds = time.perf_counter() - self._t0
+
+    def done(self):
+        return self._thread is None or not self._thread.is_alive()
+
+    def wait(self):
+        if self._thread is not None:
+            self._thread.join()
+            self._thread = None
+        if self._error is not None:
+            err, self._error = self._error, None
+            raise err
+        return self.step
+
+
+class _Snapshotter:
+    """the non-blocking save of one engine: device-side copies of the flat arenas taken in stream order at the step boundary, moved into
+    pinned host memory on a side stream, written by one background thread. Buffers are allocated at the first use and reused; one save
+    in flight (the next waits for it)."""
+
+    def __init__(self, engine):
+        model, opt = engine.model, engine.optimizer
+        self.src = dict(opt.flat_state(), flat=model.arena.flat)       # (fp32 mode: no separate master, the parameters are the masters)
+        self.dev = {k: torch.empty_like(t) for k, t in self.src.items()}
+        self.host = {k: torch.empty(t.shape, dtype=t.dtype, device="cpu", pin_memory=True) for k, t in self.src.items()}
+        self.stream = torch.cuda.Stream(device=model.arena.flat.device)
+        self.handle = None
+
+    def wait(self):
+        if self.handle is not None:
+            h, self.handle = self.handle, None
+            h.wait()
+
+    def start(self, engine, handle, engine_sd, after):
+        self.wait()
+        step, files = handle.step, handle.files
+        model, opt = engine.model, engine.optimizer
+        cur = torch.cuda.current_stream(model.arena.flat.device)
+        for k, t in self.src.items():               # behind step N's optimizer kernels, ahead of step N + 1's: the step's own stream
+            self.dev[k].copy_(t)
+        taken = torch.cuda.Event()
+        taken.record(cur)
+        done = torch.cuda.Event()
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(taken)
+            for k, t in self.dev.items():
+                self.host[k].copy_(t, non_blocking=True)
+            done.record(self.stream)
+        param_groups = [dict(g) for g in opt.param_groups]          # the LR schedule rewrites them at the next step
+
+        def write():
+            try:
+                done.synchronize()
+                if "model" in files:
+                    _write(model.state_dict(flat=self.host["flat"]), files["model"])
+                    osd = opt.state_dict(flat=self.host)
+                    osd["param_groups"] = param_groups
+                    _write(osd, files["optimizer"])
+                _write(engine_sd, files["engine"])
+                after()
+                handle._finished()
+            except BaseException as e:          # handed to wait()
+                handle._error = e
+        handle._thread = threading.Thread(target=write, name=f"valor-ckpt-{step}", daemon=False)
+        handle._thread.start()
+        self.handle = handle
+        return handle
+
+
+def save_run(engine, output_dir, step=None, blocking=True):
+    """Checkpoint a run at a step boundary (layout: the comment above). step: defaults to engine.global_step. Raises RuntimeError inside an
+    accumulation window (TrainEngine.state_dict). blocking=False: the call enqueues device-side copies and returns; the returned
+    handle's wait() (or the next save_run, or engine.close()) waits for the files. The engine state -- counters, host RNG -- is captured
+    at the call in both modes. opts.remove_before_ckpt (default True, utils/save.py:33): older steps' files are removed once the new
+    ones are complete."""
+    step = int(engine.global_step if step is None else step)
+    rank = _rank()
+    os.makedirs(os.path.join(output_dir, "ckpt"), exist_ok=True)
+    saver = getattr(engine, "_saver", None)
+    if saver is not None:
+        saver.wait()                                  # one save in flight
+    engine_sd = engine.state_dict()
+    files = run_files(output_dir, step, rank)
+    if rank != 0:
+        files = {"engine": files["engine"]}
+    opts = engine.opts
+    remove = bool(opts.get("remove_before_ckpt", True) if isinstance(opts, dict) else getattr(opts, "remove_before_ckpt", True))
+
+    def after():
+        if remove:
+            _remove_older(output_dir, step, rank, tuple(files))
+    handle = SaveHandle(step, files)
+    if not blocking and engine.model.arena.flat.is_cuda:
+        if saver is None:
+            saver = engine._saver = _Snapshotter(engine)
+        return saver.start(engine, handle, engine_sd, after)
+    if "model" in files:
+        _write(_host_copy(engine.model.state_dict()), files["model"])
+        _write(_host_copy(engine.optimizer.state_dict()), files["optimizer"])
+    _write(engine_sd, files["engine"])
+    after()
+    handle._finished()
+    return handle
+
+
+def resume_run(engine, output_dir, step=None, allow_inexact=False):
+    """Load step N (default: latest_step) into an already constructed model / optimizer / engine and return N: the next train_step
+    continues the saved run to the bit (same world size, graphs and token-masker mode; the data loader's position is the caller's).
+    A checkpoint without this rank's engine file -- one the reference wrote: its torch-Optimizer file goes through
+    FusedAdamW.load_reference_state_dict -- is refused unless allow_inexact=True: then weights, moments and the LR schedule's step
+    continue, the RNG streams (dropout masks, token masking, stochastic depth, sampling) start fresh, and the masters are re-derived
+    from the parameters."""
+    rank = _rank()
+    if getattr(engine, "_saver", None) is not None:
+        engine._saver.wait()                              # a save of this engine that is still being written
+    if step is None:
+        step = latest_step(output_dir, rank)
+        if step is None and allow_inexact:
+            step = latest_step(output_dir, rank, need_engine=False)
+        if step is None:
+            raise FileNotFoundError(f"resume_run: no complete checkpoint under {os.path.join(output_dir, 'ckpt')}"
+                                    + ("" if allow_inexact else " (a step without its engine file needs allow_inexact=True)"))
+    files = run_files(output_dir, int(step), rank)
+    exact = os.path.exists(files["engine"])
+    if not exact and not allow_inexact:
+        raise FileNotFoundError(f"resume_run: {files['engine']} is missing -- without it the RNG streams cannot be restored and the run "
+                                "does not continue bit-identically; pass allow_inexact=True to continue with fresh RNG state")
+    engine_sd = torch.load(files["engine"], map_location="cpu", weights_only=True) if exact else None
+    if engine_sd is not None:
+        engine.load_state_dict(engine_sd)                 # first: it refuses a mismatching run before anything is overwritten
+    engine.model.load_state_dict(torch.load(files["model"], map_location="cpu", weights_only=True), strict=True)
+    osd = torch.load(files["optimizer"], map_location="cpu", weights_only=True)
+    if "names" in osd:
+        engine.optimizer.load_state_dict(osd)
+    else:                                                 # torch-Optimizer layout: the reference's optimizer_step_N.pt
+        engine.optimizer.load_reference_state_dict(osd)
+    if engine_sd is None:
+        engine.global_step = int(step)
+    return int(step)

@@ -21,6 +21,8 @@ so that a row's cross-attention K|V is row % b -- the kv_bmod addressing the tra
 (pretrain.py:1133-1139 expands video_input / audio_input beam_size times).
 
 Everything here is inference: torch.no_grad, dropout off regardless of model.training (the reference calls it under model.eval())."""
+import contextlib
+import gc
 import os
 
 import torch
@@ -260,7 +262,7 @@ class DecodeSession:
         g = torch.cuda.CUDAGraph()
         mode = "thread_local" if (torch.distributed.is_available() and torch.distributed.is_initialized()) else "global"
         torch.cuda.current_stream(dev).synchronize()
-        with torch.cuda.graph(g, pool=self.pool, stream=ctx["stream"], capture_error_mode=mode):
+        with no_gc(), torch.cuda.graph(g, pool=self.pool, stream=ctx["stream"], capture_error_mode=mode):
             self.logits_of[cur] = self._body(cur)
         self.graphs[cur] = g
 
@@ -461,6 +463,21 @@ def decode_beam_cached(sess, b, beam, max_len):
     return outputs.contiguous()[:, 0]
 
 
+@contextlib.contextmanager
+def no_gc():
+    """Keep Python's cyclic collector out of a decoding step's capture. A dead cycle that still holds device resources -- an earlier model
+    with its decoding sessions: their hipGraphs, private pools, events -- is freed whenever the collector happens to run; inside a capture
+    (error mode "global") those frees are illegal calls that end the process from a destructor, and torch.cuda.graph no longer collects
+    before it begins a capture. The collector is switched off for the capture's duration; the cycle goes afterwards."""
+    on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if on:
+            gc.enable()
+
+
 class SampleStream:
     """the Philox stream of the sampled decode: plain ints (like DeviceTokenMasker). Each decode call draws under its own key, derived
     from (seed, data-parallel rank, call index): ranks draw different samples and a rerun with the same seed draws the same ones. Inside
@@ -472,14 +489,25 @@ class SampleStream:
         self.key = None
         self.offset = 0
 
-    def begin_call(self):
+    def _key_of(self, call):
         import numpy as np
         from .model.valor import _dp_rank
-        w = np.random.SeedSequence(self.seed, spawn_key=(_dp_rank(), 2, self.calls)).generate_state(2, np.uint32)
-        self.key = int(w[0]) | int(w[1]) << 32
+        w = np.random.SeedSequence(self.seed, spawn_key=(_dp_rank(), 2, call)).generate_state(2, np.uint32)
+        return int(w[0]) | int(w[1]) << 32
+
+    def begin_call(self):
+        self.key = self._key_of(self.calls)
         self.offset = 0
         self.calls += 1
         return self
+
+    def state(self):
+        """the ints the next draw depends on (a checkpoint entry); the key is a function of (seed, rank, calls) and is not stored"""
+        return {"seed": self.seed, "calls": self.calls, "offset": self.offset}
+
+    def set_state(self, st):
+        self.seed, self.calls, self.offset = int(st["seed"]), int(st["calls"]), int(st["offset"])
+        self.key = self._key_of(self.calls - 1) if self.calls > 0 else None       # the key of the call that was under way
 
     def take(self, R, V):
         off = self.offset
@@ -494,6 +522,20 @@ def sampler_of(model):
         from .model.valor import _opt
         s = model.__dict__["_sample_stream"] = SampleStream(int(_opt(model.opts, "seed", 42)))
     return s
+
+
+def sampler_state(model):
+    """state() of the model's SampleStream, or None while nothing has sampled yet (the stream is created at first use)"""
+    s = model.__dict__.get("_sample_stream")
+    return None if s is None else s.state()
+
+
+def set_sampler_state(model, st):
+    """restore sampler_state(): None = a model that had not sampled yet (the stream is dropped and re-created from opts.seed at first use)"""
+    if st is None:
+        model.__dict__.pop("_sample_stream", None)
+    else:
+        sampler_of(model).set_state(st)
 
 
 def decode_sample_cached(sess, b, max_len, stream):

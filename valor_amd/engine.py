@@ -3,13 +3,37 @@ forward -> sum of losses -> backward (+ overlapped gradient all-reduce) -> warmu
 clip -> fused AdamW. Losses stay on the device (the reference's per-step `.item()` syncs, :309, are gone;
 read them when you log)."""
 import gc
+import random
 import sys
 
+import numpy as np
 import torch
 
 from . import dist as vdist
 from .ops import DropoutState
 from .optim import FusedAdamW, get_lr_sched
+
+
+ENGINE_FORMAT = "valor_amd.engine/1"
+
+
+def host_rng_state():
+    """Python `random` (the host TokenMasker), numpy's global generator (VideoSwin stochastic depth) and torch's CPU generator as lists /
+    tensors / plain numbers: what torch.load(weights_only=True) reads back"""
+    version, words, gauss = random.getstate()
+    name, keys, pos, has_gauss, cached = np.random.get_state()
+    return {"python": {"version": int(version), "words": [int(w) for w in words], "has_gauss": int(gauss is not None),
+                       "gauss": float(gauss) if gauss is not None else 0.0},
+            "numpy": {"name": str(name), "keys": torch.from_numpy(keys.astype(np.int64)), "pos": int(pos), "has_gauss": int(has_gauss),
+                      "cached": float(cached)},
+            "torch": torch.get_rng_state()}
+
+
+def set_host_rng_state(st):
+    py, npy = st["python"], st["numpy"]
+    random.setstate((int(py["version"]), tuple(int(w) for w in py["words"]), float(py["gauss"]) if py["has_gauss"] else None))
+    np.random.set_state((npy["name"], npy["keys"].numpy().astype(np.uint32), int(npy["pos"]), int(npy["has_gauss"]), float(npy["cached"])))
+    torch.set_rng_state(st["torch"].cpu().to(torch.uint8))
 
 
 class TrainEngine:
@@ -71,6 +95,8 @@ class TrainEngine:
         self.grad_norm = grad_norm
         self._task = None
         self._micro = 0
+        self._window_open = False        # the last train_step returned without an optimizer step: partial gradient sums are in the arena
+        self._saver = None               # valor_amd.checkpoint's non-blocking writer, once save_run(blocking=False) was used
         # VALOR_DP_CHECK=1 (debug): every rank must have seen the same task sequence in an accumulation window -- the closing micro-step's
         # bucket order (dist.Reducer) is only the same on every rank if it did; checked with one small all-reduce per optimizer step
         self._check_window = _os.environ.get("VALOR_DP_CHECK", "0") == "1"
@@ -106,6 +132,7 @@ class TrainEngine:
             head = torch.cuda.Event(enable_timing=True)
             head.record()
         model.train()
+        DropoutState.check_restored()      # a restored device-mode state that never met its counter (graphs were on when it was saved)
         DropoutState.begin_step()          # device mode (model.enable_graphs): by-value offsets restart, the device counter advances
         micro = self._micro + 1             # committed only once forward + backward went through: an exception in between must not shift the
         last = (not accum) or micro % accum_steps == 0          # accumulation window's boundary for the next call
@@ -129,6 +156,7 @@ class TrainEngine:
         active = self.reducer.finish_backward(last=last)
         if tracing and self.world > 1:
             r1.record()
+        self._window_open = not last
         if not last:
             loss_dict["total_loss"] = loss.detach()
             return loss_dict
@@ -194,9 +222,62 @@ class TrainEngine:
                 del blocks
         return torch.cuda.memory_reserved(dev) - before
 
+    # ---- exact resume: everything outside model and optimizer that the next step's bits depend on (valor_amd.checkpoint.save_run /
+    # resume_run write and read it as engine_step_N.rank{r}.pt beside the reference's model_step_N.pt / optimizer_step_N.pt)
+    def state_dict(self):
+        """Tensors, ints, floats, strings, lists and dicts only (torch.load(weights_only=True) reads it). Reads the dropout counter back
+        from the device (one synchronisation). Not inside an accumulation window: the partial gradient sums are not part of a
+        checkpoint (in the reference neither: utils/save.py:38-64 saves model and optimizer)."""
+        if self._window_open:
+            raise RuntimeError("TrainEngine.state_dict: an accumulation window is open (the last train_step did not reach its optimizer "
+                               "step); save after the window's closing micro-step")
+        from . import decode
+        model = self.model
+        sd = {"format": ENGINE_FORMAT, "world_size": int(self.world), "rank": torch.distributed.get_rank() if vdist.is_dist() else 0,
+              "global_step": int(self.global_step), "micro": int(self._micro), "task": [] if self._task is None else [str(self._task)],
+              "dropout": DropoutState.state(), "token_masker": str(getattr(model, "token_masker", "host")), "host_rng": host_rng_state()}
+        masker = getattr(model, "device_masker", None)
+        if masker is not None:
+            sd["device_masker"] = masker.state()
+        sampler = decode.sampler_state(model)
+        if sampler is not None:
+            sd["sampler"] = sampler
+        return sd
+
+    def load_state_dict(self, sd):
+        """Restore state_dict(). Order-free: before or after model.enable_graphs() (a device-mode dropout state loaded in host mode waits
+        for the counter and is written INTO it -- ops.DropoutState.set_state), before or after the model's and the optimizer's own loads
+        (nothing here touches parameters or optimizer state). ValueError when the world size, the dropout mode (it follows graphs on /
+        off) or the token-masker mode differ from the saved run's: the draws would differ."""
+        from . import decode
+        if sd.get("format") != ENGINE_FORMAT:
+            raise ValueError(f"TrainEngine.load_state_dict: format {sd.get('format')!r}, expected {ENGINE_FORMAT!r}")
+        if int(sd["world_size"]) != self.world:
+            raise ValueError(f"TrainEngine.load_state_dict: saved with world size {sd['world_size']}, this run has {self.world} "
+                             "(per-rank RNG streams and the batch split would differ)")
+        model = self.model
+        mode = str(getattr(model, "token_masker", "host"))
+        if sd["token_masker"] != mode:
+            raise ValueError(f"TrainEngine.load_state_dict: saved with token_masker={sd['token_masker']!r}, the model has {mode!r}")
+        if self._window_open:
+            raise RuntimeError("TrainEngine.load_state_dict: an accumulation window is open")
+        DropoutState.set_state(sd["dropout"])               # refuses a host-mode state in device mode before anything else is changed
+        self.global_step, self._micro = int(sd["global_step"]), int(sd.get("micro", 0))
+        task = sd["task"][0] if sd["task"] else None
+        if task != self._task:
+            self.reducer.reset_task(task)
+            self._task = task
+        if mode == "device":
+            model.device_masker.set_state(sd["device_masker"])
+        decode.set_sampler_state(model, sd.get("sampler"))
+        set_host_rng_state(sd["host_rng"])
+
     def close(self):
         """release what the engine holds outside the Python heap: the native reducer's communicator / stream / events (dist.Reducer.close);
-        idempotent, also run when the engine is collected"""
+        waits for a non-blocking checkpoint that is still being written; idempotent, also run when the engine is collected"""
+        s = getattr(self, "_saver", None)
+        if s is not None:
+            s.wait()
         r = getattr(self, "reducer", None)
         if r is not None:
             r.close()

@@ -169,6 +169,14 @@ class DeviceTokenMasker:
             key = self._keys[rank] = int(w[0]) | int(w[1]) << 32
         return key
 
+    def state(self):
+        """the three ints the next draw depends on (a checkpoint entry)"""
+        return {"seed": self.seed, "calls": self.calls, "offset": self.offset}
+
+    def set_state(self, st):
+        self.seed, self.calls, self.offset = int(st["seed"]), int(st["calls"]), int(st["offset"])
+        self._keys = {}             # derived from the seed
+
     def __call__(self, tokens, mask_prob):
         src = tokens.cpu().long().contiguous()
         toks = src.numpy()
@@ -405,11 +413,16 @@ class VALOR(nn.Module):
         self.arena.grad.zero_()
         self.arena.rebind_grads()
 
-    def state_dict(self, *a, **k):
-        """Reference-keyed state dict (fp32 CPU-agnostic views of the arena parameters)."""
+    def state_dict(self, *a, flat=None, **k):
+        """Reference-keyed state dict (fp32 CPU-agnostic views of the arena parameters). flat: a copy of arena.flat to cut the views from
+        instead (valor_amd.checkpoint's snapshot of a step boundary)."""
         out = {}
         for name, shape, refs in self.table:
-            p = self.P[name].detach()
+            if flat is None:
+                p = self.P[name].detach()
+            else:
+                o, n, _ = self.arena.offsets[name]
+                p = flat[o:o + n].view(shape)
             if len(refs) == 1 or refs[1] == "cls.decoder.weight":
                 for r in refs:
                     out[r] = p

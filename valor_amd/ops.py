@@ -38,6 +38,7 @@ class DropoutState:
     @classmethod
     def reset(cls, seed, offset=0):
         cls.seed, cls.offset = int(seed), int(offset)
+        cls._pending = None
         if cls.base is not None:
             cls.base.zero_()
 
@@ -48,9 +49,47 @@ class DropoutState:
             cls.base = torch.zeros(1, dtype=torch.int64, device=device)
             K.RNG_BASE = cls.base.data_ptr()
         cls.offset = 0
+        if cls._pending is not None:             # a device-mode state restored while still in host mode (set_state): it lands now
+            st, cls._pending = cls._pending, None
+            cls.set_state(st)
         return cls.base
 
-    _retired = []                  # counters of earlier device-mode sessions: their ADDRESS may be baked into graphs that still exist
+    _pending = None                # a saved device-mode state waiting for enable_device_base (set_state ahead of VALOR.enable_graphs)
+
+    @classmethod
+    def state(cls):
+        """what decides the next draw, as plain ints / a string (a checkpoint entry): the mode, seed, the by-value offset and the VALUE of the
+        device counter (read back: synchronises with the device)"""
+        return {"mode": "device" if cls.base is not None else "host", "seed": int(cls.seed), "offset": int(cls.offset),
+                "base": int(cls.base.item()) if cls.base is not None else 0}
+
+    @classmethod
+    def set_state(cls, st):
+        """restore state(). The device counter is written INTO the live tensor (captured graphs have its address baked in). The mode is not
+        switched here -- it follows graphs on / off and changes the draws: a host-mode state is refused in device mode (ValueError); a
+        device-mode state restored in host mode is kept until enable_device_base() (VALOR.enable_graphs) and applied there, and
+        check_restored() refuses to go on while it is still waiting."""
+        if st["mode"] not in ("host", "device"):
+            raise ValueError(f"DropoutState.set_state: unknown mode {st['mode']!r}")
+        if st["mode"] == "device" and cls.base is None:
+            cls._pending = dict(st)
+            return
+        if st["mode"] == "host" and cls.base is not None:
+            raise ValueError("DropoutState.set_state: the state was saved in host mode (graphs off), this process draws in device mode "
+                             "(graphs on): the masks would differ")
+        cls._pending = None
+        cls.seed, cls.offset = int(st["seed"]), int(st["offset"])
+        if cls.base is not None:
+            cls.base.fill_(int(st["base"]))
+
+    @classmethod
+    def check_restored(cls):
+        """top of a step: a restored device-mode state must have met its counter by now"""
+        if cls._pending is not None:
+            raise ValueError("DropoutState: the restored state was saved in device mode (graphs on), this process draws in host mode "
+                             "(graphs off): the masks would differ")
+
+    _retired = []                # counters of earlier device-mode sessions: their ADDRESS may be baked into graphs that still exist
 
     @classmethod
     def disable_device_base(cls):

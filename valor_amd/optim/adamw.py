@@ -238,16 +238,28 @@ class FusedAdamW:
         self.sync_master()          # the reference's checkpoint carries no fp32 masters: re-derive them from the loaded parameters
 
     # ---- compact native layout (one entry per arena tensor)
-    def state_dict(self):
+    def flat_state(self):
+        """the flat tensors state_dict() is cut from: a consistent copy of them (valor_amd.checkpoint's device-side snapshot), moved to the
+        host, gives the same state dict through state_dict(flat=...)"""
+        out = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "count": self._count}
+        if self.separate_master:
+            out["master"] = self.master
+        return out
+
+    def state_dict(self, flat=None):
+        """flat: copies of flat_state()'s tensors to cut the entries from (they are referenced, not cloned); None = the live state, cloned"""
+        own = flat is None
+        flat = self.flat_state() if own else flat
+        keep = (lambda t: t.clone()) if own else (lambda t: t)
         state = {}
-        steps = self.steps
+        steps = dict(zip(self.arena.offsets, flat["count"].tolist()))
         for i, (name, (o, n, shape)) in enumerate(self.arena.offsets.items()):
             if steps[name] > 0:
-                state[i] = {"step": steps[name], "exp_avg": self.exp_avg[o:o + n].view(shape).clone(),
-                            "exp_avg_sq": self.exp_avg_sq[o:o + n].view(shape).clone()}
+                state[i] = {"step": steps[name], "exp_avg": keep(flat["exp_avg"][o:o + n].view(shape)),
+                            "exp_avg_sq": keep(flat["exp_avg_sq"][o:o + n].view(shape))}
         out = {"state": state, "param_groups": [dict(g) for g in self.param_groups], "names": list(self.arena.offsets)}
         if self.separate_master:
-            out["master"] = self.master.clone()         # bf16 mode: the fp32 weights the update really runs on
+            out["master"] = keep(flat["master"])         # bf16 mode: the fp32 weights the update really runs on
         return out
 
     def load_state_dict(self, sd):
