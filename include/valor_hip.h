@@ -26,6 +26,18 @@
  *     value). By-value arguments are baked into a captured hipGraph; with the device-resident term the caller bumps one counter
  *     per step (any kernel / memset node ahead of the step) and every replay of the graph draws fresh masks
  *     (train_utils.py:309: the reference advances torch's global generator once per dropout call).
+ *     That Philox law is the one of the LayerNorm-side kernels (valor_bdrln_*): element (row, c) of a [rows, cols] operand reads word
+ *     c % 4 of Philox4x32-10(seed, offset + (row * cols + c) / 4) and is KEPT iff word >= drop_threshold(p) = (uint32)((double)p * 2^32).
+ *     The attention kernels (valor_attn_fwd / valor_attn_bwd, valor_cross_attn_*_fused) draw one 32-bit hash per probability instead
+ *     (csrc/attn_common.h), with the same threshold and the same 64-bit offset = `offset` + *rng_base:
+ *         hk   = attn_drop_headkey(seed, offset, b * H + h)     b: the QUERY batch (also under kv_bmod), h: the head
+ *                = mix32(mix32(mix32(lo32(offset) + (b * H + h) * 0x9E3779B9) ^ hi32(offset) ^ lo32(seed)) + hi32(seed))
+ *         bits = attn_drop_bits(hk, q * Skv + j)                q: query row, j: key index LOCAL to the batch's kv_range (j = key - start),
+ *                                                               Skv: the launch's K / V rows per batch (the pitch, never the range length)
+ *                = x ^ (x >> 13),  x = mul24(y ^ (y >> 15), 0x85EBCB) + hk,  y = mul24(j' ^ hk, 0x9E3779) + (hk >> 7),  j' = q * Skv + j
+ *         (mix32: x ^= x >> 16, x *= 0x7FEB352D, x ^= x >> 15, x *= 0x846CA68B, x ^= x >> 16; mul24: low 24 bits of both operands, low 32 of
+ *         the product; all arithmetic modulo 2^32). P[q, j] is kept iff bits >= drop_threshold(p), kept values are scaled by 1 / (1 - p),
+ *         lse is of the undropped scores. Sq * Skv must stay below 2^24 (checked). tests/dropout_ref.py restates both laws on the host.
  */
 #ifndef VALOR_HIP_H
 #define VALOR_HIP_H

@@ -9,23 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+from dropout_ref import philox4x32_10
+
 pytestmark = pytest.mark.gpu
 TASK = "pt_contra%tva%tv%ta_caption%tva%tv%ta_mlm%tva"
 MASK, RS = 103, 106
 U32 = np.uint64(0xFFFFFFFF)
-
-
-def philox4x32_10(seed, ctr):
-    """Philox4x32-10 of valor_amd/csrc/common.h (counter words 2-3 fixed), vectorised over a uint64 counter array -> 4 x uint64 words"""
-    ctr = np.asarray(ctr, dtype=np.uint64)
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
-    c0, c1 = ctr & U32, ctr >> np.uint64(32)
-    c2, c3 = np.full_like(ctr, 0x9E3779B9), np.full_like(ctr, 0xBB67AE85)
-    for _ in range(10):
-        p0, p1 = c0 * np.uint64(0xD2511F53), c2 * np.uint64(0xCD9E8D57)
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & U32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & U32
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & U32, (k1 + np.uint64(0xBB67AE85)) & U32
-    return c0, c1, c2, c3
 
 
 def ref_mask_tokens(tokens, k, seed, offset, mask_token, rs, re):
