@@ -433,6 +433,23 @@ int valor_topk_workspace_bytes(int R, int C, int k, int64_t* bytes);
 int valor_topk_rows(void* stream, const float* score, int64_t ld, int R, int C, int64_t col_base, int k, int merge, float* top_val,
                     int64_t* top_idx, void* workspace, int64_t workspace_bytes);
 
+/* ---- retrieval search on an fp8 clip bank (csrc/search_fp8.hip; valor_amd/search.py RetrievalIndex with bank_dtype="fp8"). gfx950.
+ * valor_fp8_quantize_rows: every row of x (dtype VALOR_DT_BF16 / VALOR_DT_F32, [rows, ld], ld >= cols, cols % 16 == 0, rows 16-byte
+ *   aligned) becomes cols OCP e4m3fn codes (uint8 [rows, cols], dense, 16-byte aligned) and one fp32 scale. All in fp32,
+ *   round-to-nearest: amax = max |x|; amax < 2^-64: scale 0, every code 0x00; else scale = amax / 448, inv = 448 / amax,
+ *   code = e4m3fn(min(max(x * inv, -448), 448)), nearest-even, subnormals and sign kept. The caller keeps non-finite values out
+ *   (search.py reduces isfinite over the incoming rows first). rows == 0: no-op. VALOR_ERR_ARG before any launch on a null or
+ *   misaligned pointer, an unknown dtype, ld < cols, cols <= 0 or cols % 16 != 0.
+ * valor_fine_fused_fwd_fp8: the scores-only mode of valor_fine_fused_fwd on such rows: score[a, b] fp32 [NA, NB] of
+ *   compute_fine_matrix_slice (pretrain.py:191-211) on code * scale, i.e. sim[a,b,t,v] = scaleA[a,t] scaleB[b,v] sum_d codeA codeB.
+ *   codesA uint8 [NA, T, D], scaleA fp32 [NA, T], codesB [NB, Nv, D], scaleB [NB, Nv]; masks and SOFTMAXED token weights as in
+ *   valor_fine_fused_fwd. D % 128 == 0, 1 <= T, Nv <= 64, each code tensor below 0x7f000000 bytes and 16-byte aligned. No backward
+ *   pass exists for it. NA == 0 or NB == 0: no-op. VALOR_ERR_ARG before any launch otherwise. */
+int valor_fp8_quantize_rows(void* stream, int dtype, const void* x, int64_t ld, int64_t rows, int cols, uint8_t* codes, float* scales);
+int valor_fine_fused_fwd_fp8(void* stream, const uint8_t* codesA, const float* scaleA, const uint8_t* codesB, const float* scaleB,
+                             const float* maskA, const float* maskB, const float* wA, const float* wB, float* score, int NA, int NB,
+                             int T, int Nv, int D);
+
 /* ---- fused multi-tensor AdamW + global-norm clip over flat arenas.  Replaces optim/adamw.py:40-103, optim/misc.py:66-77
  * (10 param groups), torch clip_grad_norm_ (train_utils.py:358-360) and apex-amp's master<->model copies
  * (apex/apex/amp/_process_optimizer.py:14-22). n % valor_adamw_chunk() == 0; chunk_group: int8 [n/chunk], -1 = skip. */

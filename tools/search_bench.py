@@ -10,7 +10,14 @@ the HBM rates of the MI355X (8.0 TB/s peak, about 6.3 TB/s achievable). The scor
 multiply-adds per clip), so the bank rate is an end-to-end figure of the search, not a kernel's share of peak.
 Also reports valor_topk_rows alone on [NQ, NB] fp32 scores (4 bytes per pair): the kernel's own bound is that read.
 
-Writes one JSON document to --out (default profiles/search_bench.json) and prints one line per case. No pass / fail bar: a measurement."""
+Writes one JSON document to --out (default profiles/search_bench.json) and prints one line per case. No pass / fail bar: a measurement.
+
+--bank-dtype fp8 | both (default bf16: the run above, unchanged) times the fp8 bank (RetrievalIndex bank_dtype="fp8": e4m3 codes + row
+scales, valor_fine_fused_fwd_fp8) instead of / beside the bf16 bank, on the same shapes, features and queries in one process: `--rounds`
+timed windows per bank, alternating bf16, fp8, bf16, ... so that drift of the shared host hits both alike; the median window is reported
+with the spread. Per (NB, NQ, k): search ms, bank bytes (RetrievalIndex.bank_bytes) and bank read GB/s of each bank, the ratio, and the
+share of the bf16 bank's top-k clips that the fp8 bank returns too (the banks are random unit vectors: neighbouring scores lie closer
+than the quantisation error, so this is a lower bound for structured data). Default --out profiles/search_fp8_bench.json."""
 import argparse
 import json
 import os
@@ -50,16 +57,79 @@ def timed(fn, iters, warmup=2):
     return e0.elapsed_time(e1) / iters
 
 
+def compare_banks(a, dev):
+    """--bank-dtype fp8 / both"""
+    kinds = ("bf16", "fp8") if a.bank_dtype == "both" else ("fp8",)
+    free = torch.cuda.mem_get_info()[0]
+    cases = []
+    for NB in a.nb:
+        if NB * NV * (D * 3 + 12) * 1.2 > free:
+            print(f"NB={NB}: the two banks do not fit", flush=True)
+            continue
+        g = torch.Generator(device=dev).manual_seed(1)
+        fb = unit_bf16(NB, NV, dev, 2)
+        wb_raw = torch.randn((NB, NV), generator=g, device=dev)
+        banks = {"bf16": S.RetrievalIndex.from_features(fb, wb_raw, group="tva")}
+        banks["fp8"] = banks["bf16"].quantize()
+        if "bf16" not in kinds:
+            del banks["bf16"], fb
+        for NQ in a.nq:
+            fa = unit_bf16(NQ, T, dev, 3)
+            wa_raw = torch.randn((NQ, T), generator=g, device=dev)
+            mask = (torch.arange(T, device=dev)[None] < torch.randint(8, T + 1, (NQ, 1), generator=g, device=dev)).float()
+            q = {"feat_t": fa, "mask": mask, "weight": wa_raw}
+            iters = max(3, min(a.iters, int(2e8 / (NB * NQ))))
+            for k in a.k:
+                ms = {kind: [] for kind in kinds}
+                for _ in range(a.rounds):
+                    for kind in kinds:
+                        ms[kind].append(timed(lambda: banks[kind].search(None, q, k), iters))
+                res = {"NB": NB, "NQ": NQ, "k": k, "iters": iters, "rounds": a.rounds}
+                for kind in kinds:
+                    med = sorted(ms[kind])[len(ms[kind]) // 2]
+                    nbytes = banks[kind].bank_bytes()
+                    res.update({f"{kind}_search_ms": round(med, 4), f"{kind}_search_ms_min_max": [round(min(ms[kind]), 4), round(max(ms[kind]), 4)],
+                                f"{kind}_chunk": banks[kind].default_chunk(NQ, T), f"{kind}_bank_GB": round(nbytes / 1e9, 4),
+                                f"{kind}_bank_GBps": round(nbytes / med / 1e6, 1)})
+                if len(kinds) == 2:
+                    res["bf16_over_fp8"] = round(res["bf16_search_ms"] / res["fp8_search_ms"], 3)
+                    got, want = banks["fp8"].search(None, q, k).indices.cpu().tolist(), banks["bf16"].search(None, q, k).indices.cpu().tolist()
+                    res["topk_overlap"] = round(sum(len(set(g_) & set(w_)) for g_, w_ in zip(got, want)) / (min(k, NB) * NQ), 4)
+                    diff = (banks["fp8"].scores(None, q) - banks["bf16"].scores(None, q)).abs().max() if NB * NQ * 4 * 4 < free else None
+                    res["largest_score_difference"] = None if diff is None else round(float(diff), 6)
+                print(json.dumps(res), flush=True)
+                cases.append(res)
+        banks.clear()
+        fb = wb_raw = None
+        torch.cuda.empty_cache()
+    return {"bench": "search_fp8", "geometry": {"T": T, "Nv": NV, "D": D, "feature_dtype": "bfloat16", "banks": list(kinds)},
+            "device": torch.cuda.get_device_name(0), "hbm_peak_TBps": HBM_PEAK / 1e12, "hbm_achievable_TBps": HBM_ACHIEVABLE / 1e12,
+            "timing": "device events over warmed calls; the median of `rounds` windows per bank, the banks alternating", "cases": cases}
+
+
+def write(doc, out):
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nb", type=int, nargs="+", default=[10 ** 4, 10 ** 5, 10 ** 6])
     ap.add_argument("--nq", type=int, nargs="+", default=[1, 16, 64])
     ap.add_argument("--k", type=int, nargs="+", default=[10, 100])
     ap.add_argument("--iters", type=int, default=200, help="most calls per timed window (large cases take fewer)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "search_bench.json"))
+    ap.add_argument("--bank-dtype", choices=("bf16", "fp8", "both"), default="bf16", help="fp8 / both: the fp8 bank instead of / beside the bf16 bank")
+    ap.add_argument("--rounds", type=int, default=3, help="--bank-dtype fp8 / both: timed windows per bank")
+    ap.add_argument("--out", default=None, help="default profiles/search_bench.json (bf16) or profiles/search_fp8_bench.json (fp8, both)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "search_bench.py measures on the GPU"
     dev = torch.device("cuda:0")
+    if a.bank_dtype != "bf16":
+        write(compare_banks(a, dev), a.out or os.path.join(ROOT, "profiles", "search_fp8_bench.json"))
+        return
+    a.out = a.out or os.path.join(ROOT, "profiles", "search_bench.json")
     free = torch.cuda.mem_get_info()[0]
     cases = []
     for NB in a.nb:
@@ -121,10 +191,7 @@ def main():
         torch.cuda.empty_cache()
     doc = {"bench": "search", "geometry": {"T": T, "Nv": NV, "D": D, "dtype": "bfloat16"}, "device": torch.cuda.get_device_name(0),
            "hbm_peak_TBps": HBM_PEAK / 1e12, "hbm_achievable_TBps": HBM_ACHIEVABLE / 1e12, "timing": "device events over warmed calls", "cases": cases}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(doc, fh, indent=1)
-        fh.write("\n")
+    write(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -15,6 +15,7 @@
 // (valor_fine_ds_chunk below): no [B*T, B*Nv] tensor exists in either direction.
 // Roofline: MFMA (2 * B^2 * TP * VP * D flop per group, 137 GFLOP at B = 512, T = 32, Nv = 10 padded to 16, D = 512) beside
 // ~1100 VALU operations per 64 x 64 wave tile; traffic = the features (21 MB) + A2B / B2A / argmax bytes (54 MB).
+#include "dpp.h"
 #include "mma.h"
 #include <stdlib.h>
 
@@ -30,36 +31,6 @@ struct FineFusedArgs {
 };
 
 #define FF_OOB 0x7f000000        // a buffer offset past every operand: the range check returns zeros (padded token slots / tile tails)
-
-template <int CTRL>
-DEVINL float dpp_mov_f(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-}
-template <int CTRL>
-DEVINL int dpp_mov_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true); }
-// all-reduce over the 16 lanes of a DPP row (lanes sharing lane >> 4): xor 1, xor 2 as quad permutes; once quads are uniform the
-// half-row / row mirrors exchange the remaining halves
-DEVINL float row16_max(float x) {
-    x = fmaxf(x, dpp_mov_f<0xB1>(x));
-    x = fmaxf(x, dpp_mov_f<0x4E>(x));
-    x = fmaxf(x, dpp_mov_f<0x141>(x));
-    x = fmaxf(x, dpp_mov_f<0x140>(x));
-    return x;
-}
-DEVINL int row16_min(int x) {
-    x = min(x, dpp_mov_i<0xB1>(x));
-    x = min(x, dpp_mov_i<0x4E>(x));
-    x = min(x, dpp_mov_i<0x141>(x));
-    x = min(x, dpp_mov_i<0x140>(x));
-    return x;
-}
-DEVINL float row16_sum(float x) {
-    x += dpp_mov_f<0xB1>(x);
-    x += dpp_mov_f<0x4E>(x);
-    x += dpp_mov_f<0x141>(x);
-    x += dpp_mov_f<0x140>(x);
-    return x;
-}
 
 template <int TPB, int VPB>
 __global__ __launch_bounds__(256, 2) void fine_fused_fwd_kernel(FineFusedArgs p) {

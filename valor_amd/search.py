@@ -12,8 +12,15 @@ kernels evaluate.fine_score_matrix uses (valor_fine_fused_fwd for bf16 features,
 for coarse) and are folded into the running [NQ, k] result by valor_topk_rows(merge=1, col_base=chunk start) (csrc/search.hip). Nothing
 of size [NQ, NB] exists, and nothing comes back to the host before the caller reads `.ids`.
 
+bank_dtype="fp8" (fine banks only, opt-in; csrc/search_fp8.hip): the bank keeps OCP e4m3 codes [NB, Nv, D] (uint8) and one fp32 scale per
+token row [NB, Nv] instead of the features -- half the bytes of a bf16 bank, and no bf16 copy is kept. build / add / from_features /
+quantize() encode the incoming rows with valor_fp8_quantize_rows; search() quantises the query rows per call with the same kernel and
+scores a chunk with valor_fine_fused_fwd_fp8 (the e4m3 MFMA form of valor_fine_fused_fwd, scores only). The quantisation law and the
+score law are restated on the host below (quantize_rows_host, fp8_scores_host). An index built without bank_dtype is what it was.
+
 Out of scope: dual_softmax (it needs the whole matrix), the va / vta / atv directions, a bank sharded over GPUs,
-deletion, approximate search."""
+deletion, approximate search; for fp8 banks also coarse banks (they need an fp8 GEMM), block-scaled (MX) codes, exact re-scoring of the
+candidates, and fp8 anywhere in validate_ret or training."""
 import ctypes
 
 import torch
@@ -88,6 +95,73 @@ def topk_workspace_bytes(R, C, k):
     return n.value
 
 
+# ------------------------------------------------------------------ the fp8 bank's laws on the host (checks only)
+BANK_DTYPES = (None, "fp8")
+_FP8_MAX, _FP8_TINY = 448.0, 2.0 ** -64
+
+
+def quantize_rows_host(x):
+    """What valor_fp8_quantize_rows computes, restated on the CPU: x [..., D] -> (uint8 e4m3fn codes [..., D], fp32 scales [...]). All
+    in fp32: amax = max |x|; amax < 2^-64: scale 0, codes 0x00; else scale = amax / 448, inv = 448 / amax, code = e4m3fn(clamp(x * inv,
+    -448, 448)) (torch's CPU conversion: round to nearest even, subnormals and sign kept; the clamp keeps it away from NaN)."""
+    x = x.detach().float().cpu()
+    amax = x.abs().amax(-1, keepdim=True)
+    live = amax >= _FP8_TINY
+    safe = torch.where(live, amax, torch.ones_like(amax))
+    scale = torch.where(live, safe / _FP8_MAX, torch.zeros_like(amax))
+    # a tensor / tensor division: `448.0 / safe` would be reciprocal-then-multiply, two roundings, and bf16 inputs put many products
+    # x * inv exactly on e4m3 ties, where the last bit of inv decides the code
+    inv = torch.where(live, torch.full_like(amax, _FP8_MAX) / safe, torch.zeros_like(amax))
+    codes = (x * inv).clamp(-_FP8_MAX, _FP8_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+    return torch.where(live, codes, torch.zeros_like(codes)), scale.squeeze(-1)
+
+
+def fp8_scores_host(codesA, scaleA, codesB, scaleB, maskA, maskB, wA, wB):
+    """What valor_fine_fused_fwd_fp8 computes, in fp64 on the CPU: compute_fine_matrix_slice (pretrain.py:191-211) on the dequantised
+    rows. codesA uint8 [NA, T, D], scaleA [NA, T], codesB [NB, Nv, D], scaleB [NB, Nv], masks and SOFTMAXED token weights [NA, T] /
+    [NB, Nv]. sim = scaleA scaleB sum_d codeA codeB; x = sim maskA maskB; score = (sum_t wA max_v x + sum_v wB max_t x) / 2. [NA, NB] fp64."""
+    f64 = lambda t: t.detach().cpu().double()
+    de = lambda c: c.detach().cpu().view(torch.float8_e4m3fn).float().double()
+    sA, sB, mA, mB = f64(scaleA), f64(scaleB), f64(maskA), f64(maskB)
+    sim = torch.einsum("atd,bvd->abtv", de(codesA), de(codesB)) * sA[:, None, :, None] * sB[None, :, None, :]
+    x = sim * mA[:, None, :, None] * mB[None, :, None, :]
+    return (torch.einsum("abt,at->ab", x.max(dim=3)[0], f64(wA)) + torch.einsum("abv,bv->ab", x.max(dim=2)[0], f64(wB))) / 2.0
+
+
+def quantize_rows(x):
+    """valor_fp8_quantize_rows on device bf16 / fp32 rows x [..., D] (D % 16 == 0; a 2-D x may be a column slice of a wider matrix):
+    (uint8 codes [..., D] dense, fp32 scales [...]). A non-finite value raises ValueError (one isfinite reduction on the device, read
+    back by the host: bank rows and query rows alike, the law is undefined on such rows)."""
+    K._check_gpu(x)
+    if x.dtype not in (torch.bfloat16, torch.float32) or x.dim() < 1 or x.shape[-1] % 16 or x.shape[-1] == 0:
+        raise ValueError(f"quantize_rows: bf16 or fp32 rows of a multiple of 16 elements, got {tuple(x.shape)} {x.dtype}")
+    cols = x.shape[-1]
+    strided = x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= cols and (x.stride(0) * x.element_size()) % 16 == 0 and x.data_ptr() % 16 == 0
+    if not strided:
+        x = x.contiguous()
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("quantize_rows: the rows hold a non-finite value")
+    rows = x.numel() // cols
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    lib.call("valor_fp8_quantize_rows", K._stream(), 0 if x.dtype == torch.bfloat16 else 1, x.data_ptr(), x.stride(0) if strided else cols, rows,
+             cols, codes.data_ptr(), scales.data_ptr())
+    return codes, scales
+
+
+def _scores_fp8(qc, qs, bc, bs, maskA, maskB, wA, wB, out):
+    """out [NA, nb] (dense fp32) = valor_fine_fused_fwd_fp8 on contiguous codes / scales, the A rows in pieces under the kernel's byte limit"""
+    NA, T, D = qc.shape
+    nb, Nv = bc.shape[:2]
+    st = K._stream()
+    ra = max(1, min(NA, (E._FUSED_BYTES - 1) // (T * D)))
+    for a0 in range(0, NA, ra):
+        na = min(ra, NA - a0)
+        lib.call("valor_fine_fused_fwd_fp8", st, qc[a0:a0 + na].data_ptr(), qs[a0:a0 + na].data_ptr(), bc.data_ptr(), bs.data_ptr(),
+                 maskA[a0:a0 + na].data_ptr(), maskB.data_ptr(), wA[a0:a0 + na].data_ptr(), wB.data_ptr(), out[a0:a0 + na].data_ptr(), na, nb, T, Nv, D)
+    return out
+
+
 class SearchResult:
     """scores fp32 [NQ, k] and indices int64 [NQ, k] on the device (-inf / -1 where the bank has fewer than k clips); `.ids` reads the
     indices back and maps them to the bank's clip ids (None for -1)."""
@@ -137,14 +211,21 @@ def _softmax_ones_mask(raw):
 
 class RetrievalIndex:
     """A clip bank on the device for one retrieval group ('tv', 'tva', 'ta'). parts: one (features, weights) pair, or two under
-    late_fusion 'tva' (video, audio: their scores are added). weights are the softmaxed token weights of a fine bank, None for coarse."""
+    late_fusion 'tva' (video, audio: their scores are added). weights are the softmaxed token weights of a fine bank, None for coarse.
+    bank_dtype "fp8" (fine banks): the parts are stored as e4m3 codes and row scales. `feats` are then bf16 / fp32 device features,
+    quantised here, or -- with `scales` (one fp32 [clips, tokens] tensor per part) and `dtype` (the feature dtype the codes were made
+    from) -- the uint8 codes themselves, on any device."""
 
-    def __init__(self, group, contra_type, late_fusion, feats, weights, ids):
+    def __init__(self, group, contra_type, late_fusion, feats, weights, ids, bank_dtype=None, *, scales=None, dtype=None):
         if group not in GROUPS:
             raise ValueError(f"group {group!r}: one of {GROUPS} (the va / vta / atv directions are not searchable)")
         if contra_type not in ("fine", "coarse"):
             raise ValueError(f"contra_type {contra_type!r}")
-        self.group, self.contra_type, self.late_fusion = group, contra_type, bool(late_fusion)
+        if bank_dtype not in BANK_DTYPES:
+            raise ValueError(f"bank_dtype {bank_dtype!r}: one of {BANK_DTYPES}")
+        if bank_dtype == "fp8" and contra_type != "fine":
+            raise ValueError("bank_dtype='fp8': only fine banks are covered (a coarse bank needs an fp8 GEMM)")
+        self.group, self.contra_type, self.late_fusion, self.bank_dtype = group, contra_type, bool(late_fusion), bank_dtype
         nparts = 2 if (self.late_fusion and group == "tva") else 1
         if len(feats) != nparts or len(weights) != nparts:
             raise ValueError(f"group {group!r}, late_fusion={self.late_fusion}: {nparts} feature bank(s), got {len(feats)}")
@@ -154,6 +235,21 @@ class RetrievalIndex:
                 raise ValueError(f"a {contra_type} bank holds [{len(ids)} clips, {'tokens, ' if dims == 3 else ''}D] features, got {tuple(f.shape)}")
             if (w is None) != (contra_type == "coarse") or (w is not None and (tuple(w.shape) != tuple(f.shape[:2]) or w.dtype != torch.float32)):
                 raise ValueError("a fine bank carries fp32 token weights [clips, tokens], a coarse bank none")
+        self._scales = None
+        if bank_dtype == "fp8":
+            for f in feats:
+                if f.shape[-1] % 128 or f.shape[1] > 64 or f.shape[1] < 1:
+                    raise ValueError(f"bank_dtype='fp8': D % 128 == 0 and 1 .. 64 tokens per clip (valor_fine_fused_fwd_fp8 has no GEMM "
+                                     f"fallback), got {tuple(f.shape)}")
+            if scales is None:
+                self._dtype = feats[0].dtype
+                feats, scales = zip(*[quantize_rows(f) for f in feats])
+            else:
+                if (feats[0].dtype != torch.uint8 or dtype not in (torch.bfloat16, torch.float32) or len(scales) != nparts
+                        or any(tuple(s.shape) != tuple(f.shape[:2]) or s.dtype != torch.float32 for f, s in zip(feats, scales))):
+                    raise ValueError("an fp8 bank given as codes: uint8 [clips, tokens, D], fp32 scales [clips, tokens], dtype bf16 / fp32")
+                self._dtype = dtype
+            self._scales = [_Bank(s) for s in scales]
         self._feats = [_Bank(f) for f in feats]
         self._weights = [None if w is None else _Bank(w) for w in weights]
         self.ids = list(ids)
@@ -168,7 +264,8 @@ class RetrievalIndex:
 
     @property
     def dtype(self):
-        return self._feats[0].data.dtype
+        """the feature dtype the index was built from (an fp8 bank: what its codes were quantised from, and what queries may be)"""
+        return self._dtype if self.bank_dtype == "fp8" else self._feats[0].data.dtype
 
     @property
     def feats(self):
@@ -179,13 +276,26 @@ class RetrievalIndex:
         return [None if b is None else b.view() for b in self._weights]
 
     @property
+    def scales(self):
+        """an fp8 bank's fp32 row scales [NB, Nv] per part (`feats` are then the uint8 codes); None otherwise"""
+        return None if self._scales is None else [b.view() for b in self._scales]
+
+    def bank_bytes(self):
+        """device bytes of the filled rows: features or codes, scales, token weights"""
+        banks = self._feats + [b for b in self._weights if b is not None] + (self._scales or [])
+        return sum(b.view().numel() * b.data.element_size() for b in banks)
+
+    @property
     def unit_text_weights(self):
         """late-fusion fine scores use unit token weights on both sides (test.py:571-579)"""
         return self.contra_type == "fine" and len(self._feats) == 2
 
     def fingerprint(self):
-        return {"group": self.group, "contra_type": self.contra_type, "late_fusion": self.late_fusion, "D": int(self._feats[0].data.shape[-1]),
-                "tokens": [int(b.data.shape[1]) if self.contra_type == "fine" else 1 for b in self._feats], "dtype": str(self.dtype)}
+        fp = {"group": self.group, "contra_type": self.contra_type, "late_fusion": self.late_fusion, "D": int(self._feats[0].data.shape[-1]),
+              "tokens": [int(b.data.shape[1]) if self.contra_type == "fine" else 1 for b in self._feats], "dtype": str(self.dtype)}
+        if self.bank_dtype == "fp8":
+            fp["bank_dtype"] = "fp8_e4m3"
+        return fp
 
     def _check_model(self, model):
         sp = model.spec
@@ -195,11 +305,14 @@ class RetrievalIndex:
 
     # ------------------------------------------------------------------ construction
     @classmethod
-    def from_features(cls, feats, weights=None, ids=None, *, group="tv", contra_type="fine", late_fusion=False, weights_softmaxed=False):
+    def from_features(cls, feats, weights=None, ids=None, *, group="tv", contra_type="fine", late_fusion=False, weights_softmaxed=False,
+                      bank_dtype=None):
         """An index over given tensors (device tensors; a CPU index can be saved and loaded but not searched). feats: [NB, Nv, D] (fine)
         or [NB, D] (coarse), or a (video, audio) pair for late_fusion 'tva'. weights (fine, one parts): the RAW token weights [NB, Nv],
         softmaxed here as validate_ret does; None = unit weights, which is what late_fusion always uses. weights_softmaxed: `weights`
-        (one tensor per part) already are the softmaxed values."""
+        (one tensor per part) already are the softmaxed values. bank_dtype "fp8": the features are quantised on the device and dropped."""
+        if bank_dtype == "fp8" and contra_type != "fine":
+            raise ValueError("bank_dtype='fp8': only fine banks are covered (a coarse bank needs an fp8 GEMM)")
         if group not in GROUPS:
             raise ValueError(f"group {group!r}: one of {GROUPS} (the va / vta / atv directions are not searchable)")
         feats = list(feats) if isinstance(feats, (list, tuple)) else [feats]
@@ -213,7 +326,14 @@ class RetrievalIndex:
                 raise ValueError("late_fusion scores use unit token weights: pass none")
             ws = [_softmax_ones_mask(torch.ones(f.shape[:2], dtype=torch.float32, device=f.device) if w is None else w) for f, w in zip(feats, raw)]
         ids = list(range(feats[0].shape[0])) if ids is None else list(ids)
-        return cls(group, contra_type, late_fusion, feats, ws, ids)
+        return cls(group, contra_type, late_fusion, feats, ws, ids, bank_dtype)
+
+    def quantize(self):
+        """A new fp8 index over this fine bf16 / fp32 bank, quantised on the device; this index is untouched."""
+        if self.bank_dtype is not None:
+            raise ValueError("the bank is quantised already")
+        return RetrievalIndex(self.group, self.contra_type, self.late_fusion, self.feats, [None if w is None else w.clone() for w in self.weights],
+                              self.ids, "fp8")
 
     @staticmethod
     def encode_gallery(model, batch, group):
@@ -241,14 +361,15 @@ class RetrievalIndex:
 
     @classmethod
     @torch.no_grad()
-    def build(cls, model, loader, group):
-        """Encode every batch of `loader` (valor_collate batches with 'ids') once and keep the bank on the model's device."""
+    def build(cls, model, loader, group, bank_dtype=None):
+        """Encode every batch of `loader` (valor_collate batches with 'ids') once and keep the bank on the model's device
+        (bank_dtype "fp8": as e4m3 codes, each batch quantised as it arrives)."""
         index = None
         model.eval()
         for batch in loader:
             if index is None:
                 feats, ws = cls.encode_gallery(model, batch, group)
-                index = cls(group, model.spec.contra_type, bool(model.spec.late_fusion), feats, ws, list(batch["ids"]))
+                index = cls(group, model.spec.contra_type, bool(model.spec.late_fusion), feats, ws, list(batch["ids"]), bank_dtype)
             else:
                 index.add(model, batch)
         if index is None:
@@ -264,10 +385,18 @@ class RetrievalIndex:
         self.add_features(feats, ws, batch["ids"])
 
     def add_features(self, feats, weights, ids):
-        """add() on encoded rows: one tensor per part, weights already softmaxed (None for coarse)"""
+        """add() on encoded rows: one tensor per part, weights already softmaxed (None for coarse). An fp8 bank takes bf16 / fp32
+        features and quantises them first; a non-finite row raises ValueError before anything is appended."""
         ids = list(ids)
         if len(feats) != len(self._feats) or any(f.shape[0] != len(ids) for f in feats):
             raise ValueError("one feature tensor per bank part, one row per id")
+        if self.bank_dtype == "fp8":
+            for bank, f in zip(self._feats, feats):
+                if f.shape[1:] != bank.data.shape[1:]:
+                    raise ValueError(f"bank rows {tuple(f.shape[1:])} against {tuple(bank.data.shape[1:])}")
+            feats, scales = zip(*[quantize_rows(f) for f in feats])
+            for bank, s in zip(self._scales, scales):
+                bank.append(s)
         for bank, f in zip(self._feats, feats):
             bank.append(f)
         for bank, w in zip(self._weights, weights):
@@ -277,17 +406,27 @@ class RetrievalIndex:
 
     # ------------------------------------------------------------------ persistence
     def save(self, path):
+        if self.bank_dtype == "fp8":
+            torch.save({"format": "valor_amd.RetrievalIndex/2", "fingerprint": self.fingerprint(), "ids": self.ids,
+                        "codes": [f.cpu().clone() for f in self.feats], "scales": [s.cpu().clone() for s in self.scales],
+                        "weights": [w.cpu().clone() for w in self.weights]}, path)
+            return
         torch.save({"format": "valor_amd.RetrievalIndex/1", "fingerprint": self.fingerprint(), "ids": self.ids,
                     "feats": [f.cpu().clone() for f in self.feats], "weights": [None if w is None else w.cpu().clone() for w in self.weights]}, path)
 
     @classmethod
     def load(cls, path, device):
         blob = torch.load(path, map_location="cpu", weights_only=True)      # tensors, strings, numbers, lists and dicts only
-        if not isinstance(blob, dict) or blob.get("format") != "valor_amd.RetrievalIndex/1":
+        if not isinstance(blob, dict) or blob.get("format") not in ("valor_amd.RetrievalIndex/1", "valor_amd.RetrievalIndex/2"):
             raise ValueError(f"{path}: not a RetrievalIndex file")
         fp = blob["fingerprint"]
-        index = cls(fp["group"], fp["contra_type"], fp["late_fusion"], [f.to(device) for f in blob["feats"]],
-                    [None if w is None else w.to(device) for w in blob["weights"]], blob["ids"])
+        if blob["format"].endswith("/2"):
+            feature_dtype = {str(t): t for t in (torch.bfloat16, torch.float32)}.get(fp.get("dtype"))
+            index = cls(fp["group"], fp["contra_type"], fp["late_fusion"], [c.to(device) for c in blob["codes"]],
+                        [w.to(device) for w in blob["weights"]], blob["ids"], "fp8", scales=[s.to(device) for s in blob["scales"]], dtype=feature_dtype)
+        else:
+            index = cls(fp["group"], fp["contra_type"], fp["late_fusion"], [f.to(device) for f in blob["feats"]],
+                        [None if w is None else w.to(device) for w in blob["weights"]], blob["ids"])
         if index.fingerprint() != fp:
             raise ValueError(f"{path}: the stored tensors do not match the stored fingerprint {fp}")
         return index
@@ -318,7 +457,8 @@ class RetrievalIndex:
         ft = q["feat_t"]
         if not ft.is_cuda or not self.device.type == "cuda":
             raise lib.ValorHipError("RetrievalIndex.search needs the bank and the queries on the GPU (no CPU fallback)")
-        if ft.shape[-1] != self._feats[0].data.shape[-1] or ft.dtype != self.dtype or ft.dim() != (3 if self.contra_type == "fine" else 2):
+        dtype_ok = ft.dtype in (torch.bfloat16, torch.float32) if self.bank_dtype == "fp8" else ft.dtype == self.dtype
+        if ft.shape[-1] != self._feats[0].data.shape[-1] or not dtype_ok or ft.dim() != (3 if self.contra_type == "fine" else 2):
             raise ValueError(f"query features {tuple(ft.shape)} {ft.dtype} against a {self.contra_type} bank of D={self._feats[0].data.shape[-1]}, {self.dtype}")
         ft = ft.contiguous()
         if self.contra_type == "coarse":
@@ -333,6 +473,8 @@ class RetrievalIndex:
         raw = torch.ones((NQ, T), **f32) if raw is None else raw.float().contiguous()
         wq = torch.empty((NQ, T), **f32)
         lib.call("valor_fine_weight_softmax", K._stream(), raw.data_ptr(), mask.data_ptr(), wq.data_ptr(), NQ, T)
+        if self.bank_dtype == "fp8" and T > 64:
+            raise ValueError("an fp8 bank scores queries of at most 64 tokens (valor_fine_fused_fwd_fp8)")
         return ft, mask, wq
 
     def _fused(self, ft, part):
@@ -347,7 +489,7 @@ class RetrievalIndex:
             tokens = b.data.shape[1] if self.contra_type == "fine" else 1
             per_clip = max(per_clip, tokens * D * b.data.element_size())
         chunk = (E._FUSED_BYTES - 1) // per_clip
-        if self.contra_type == "fine":
+        if self.contra_type == "fine" and self.bank_dtype is None:
             for part, b in enumerate(self._feats):
                 if not (self.dtype == torch.bfloat16 and T <= 64 and b.data.shape[1] <= 64 and D % 64 == 0):
                     chunk = min(chunk, _GEMM_PATH_BYTES // (NQ * T * ((b.data.shape[1] + 7) // 8 * 8) * 4))
@@ -359,6 +501,9 @@ class RetrievalIndex:
     def _score_part(self, part, ft, mask, wq, c0, nb, ones, out):
         """out [NQ, nb] (dense fp32) = the scores of clips [c0, c0 + nb) of one bank part; ones: the clips' all-ones token mask [nb, Nv]"""
         fb = self._feats[part].data[c0:c0 + nb]
+        if self.bank_dtype == "fp8":                                     # ft = the queries' (codes, scales)
+            _scores_fp8(ft[0], ft[1], fb, self._scales[part].data[c0:c0 + nb], mask, ones, wq, self._weights[part].data[c0:c0 + nb], out)
+            return
         if self.contra_type == "coarse":
             K.gemm(ft, fb, out=out, out_dtype=torch.float32)
             return
@@ -377,6 +522,8 @@ class RetrievalIndex:
         # the clips' token mask is all ones: one tensor per part for the whole walk, a chunk reads its leading rows
         ones = [torch.ones((chunk, b.data.shape[1]), dtype=torch.float32, device=ft.device) if self.contra_type == "fine" else None
                 for b in self._feats]
+        if self.bank_dtype == "fp8":
+            ft = quantize_rows(ft)                                       # the query rows, once per call
         for c0 in range(0, NB, chunk):
             nb = min(chunk, NB - c0)
             outs = [b[:NQ * nb].view(NQ, nb) for b in bufs]
