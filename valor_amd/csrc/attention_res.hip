@@ -291,10 +291,13 @@ DEVINL void attn_res_bwd_body(const AttnArgs& p) {
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
                         f32x4_t m4 = {0.f, 0.f, 0.f, 0.f}, pdrop;
+                        // keys past S score 0 against the zero rows of the K image: P = 2^(-lse), harmless (dS meets zero K^T columns) until a
+                        // row's lse is far below zero -- every key closed by -10000 -- where it is +inf and inf * 0 = NaN reaches dQ. Under a
+                        // mask these keys are closed like the ones the mask closes (the same in the two pipelined kernels below).
                         if (MASK && qr[rt] < S) {
                             const float* mrowp = p.mask + (int64_t)b * p.mask_bs + (int64_t)qr[rt] * p.mask_rs;
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) { const int key = kv0 + kt * 16 + 4 * g + r; if (key < S) m4[r] = mrowp[key] * LOG2E_F; }
+                            for (int r = 0; r < 4; ++r) { const int key = kv0 + kt * 16 + 4 * g + r; m4[r] = key < S ? mrowp[key] * LOG2E_F : -INFINITY; }
                         }
                         const uint32_t e0 = (uint32_t)qr[rt] * (uint32_t)p.Skv + (uint32_t)(kv0 + kt * 16 + 4 * g);
                         softmax_bwd4<DROP, false>(sa[rt], pa[rt], m4, splat4(lse2[rt]), splat4(dlt[rt]), sl2, hk, e0, 1u, thr, keep_scale, pdrop, ds[rt][k2]);
@@ -594,7 +597,7 @@ __global__ __launch_bounds__(512, 2) void attn_res_bwd_pipe_kernel(AttnArgs p, i
                             if (MASK && qr[rt] < S) {
                                 const float* mrowp = p.mask + (int64_t)b * p.mask_bs + (int64_t)qr[rt] * p.mask_rs;
 #pragma unroll
-                                for (int r = 0; r < 4; ++r) { const int key = kv0 + kt * 16 + 4 * g + r; if (key < S) m4[r] = mrowp[key] * LOG2E_F; }
+                                for (int r = 0; r < 4; ++r) { const int key = kv0 + kt * 16 + 4 * g + r; m4[r] = key < S ? mrowp[key] * LOG2E_F : -INFINITY; }
                             }
                             const uint32_t e0 = (uint32_t)qr[rt] * (uint32_t)p.Skv + (uint32_t)(kv0 + kt * 16 + 4 * g);
                             softmax_bwd4<DROP, false>(sa[rt], pa[rt], m4, splat4(lse2[rt]), splat4(dlt[rt]), sl2, hk, e0, 1u, thr, keep_scale, pdrop, ds[rt][k2]);
@@ -952,7 +955,7 @@ __global__ __launch_bounds__(512, 2) void attn_res_bwd_pipe2_kernel(AttnArgs p, 
                             if (MASK && rowi[rt] < S) {
                                 const float* mrowp = p.mask + (int64_t)b * p.mask_bs + (int64_t)rowi[rt] * p.mask_rs;
 #pragma unroll
-                                for (int r = 0; r < 4; ++r) { const int key = kv0 + kt * 16 + 4 * g + r; if (key < S) m4[r] = mrowp[key] * LOG2E_F; }
+                                for (int r = 0; r < 4; ++r) { const int key = kv0 + kt * 16 + 4 * g + r; m4[r] = key < S ? mrowp[key] * LOG2E_F : -INFINITY; }
                             }
                             const uint32_t e0 = (uint32_t)rowi[rt] * (uint32_t)p.Skv + (uint32_t)(kv0 + kt * 16 + 4 * g);
                             softmax_bwd4<DROP, false>(sa[rt], pa[rt], m4, splat4(lse2[rt]), splat4(dlt[rt]), sl2, hk, e0, 1u, thr, keep_scale, pdrop, ds[rt][k2]);
