@@ -450,6 +450,21 @@ int valor_fine_fused_fwd_fp8(void* stream, const uint8_t* codesA, const float* s
                              const float* maskA, const float* maskB, const float* wA, const float* wB, float* score, int NA, int NB,
                              int T, int Nv, int D);
 
+/* ---- retrieval search, pair scores: every query against ITS OWN candidate list, read by index from a feature store (csrc/search_pairs.hip;
+ * valor_amd/search.py score_pairs, RetrievalIndex.rescore / search(within=) / the two-stage search of an fp8 bank). gfx950.
+ *   featA bf16 [NA, T, D]; maskA (the text mask) and wA (the SOFTMAXED text token weights) fp32 [NA, T], as in valor_fine_fused_fwd.
+ *   storeB bf16 [NS, Nv, D]: any device-addressable feature store (a bank, or a staging buffer of gathered rows; it may exceed 2 GiB);
+ *   wStoreB fp32 [NS, Nv]: its SOFTMAXED clip token weights. The clip mask is all ones and implicit. cand int64 [NA, ld_cand], of
+ *   which C columns are read. score fp32 [NA, ld_score]: score[a, c], c < C, is the scores-only result of valor_fine_fused_fwd
+ *   (compute_fine_matrix_slice, pretrain.py:191-211) for the pair (query a, clip cand[a, c]), with that kernel's padding law and
+ *   reduction order; columns c >= C are not written. A candidate outside [0, NS), -1 included, is never dereferenced: its score is
+ *   -inf. Duplicates are scored like any other candidate. D % 64 == 0 (D <= 2^20), 1 <= T, Nv <= 64; featA and storeB 16-byte
+ *   aligned, cand 8-byte aligned. One launch; no workspace. NA == 0 or C == 0: no-op. VALOR_ERR_ARG before any launch on a null or
+ *   misaligned pointer, ld_cand < C, ld_score < C, a negative count or a shape outside the coverage. */
+int valor_fine_score_pairs(void* stream, const void* featA, const float* maskA, const float* wA, const void* storeB,
+                           const float* wStoreB, int64_t NS, const int64_t* cand, int64_t ld_cand, float* score, int64_t ld_score,
+                           int NA, int C, int T, int Nv, int D);
+
 /* ---- fused multi-tensor AdamW + global-norm clip over flat arenas.  Replaces optim/adamw.py:40-103, optim/misc.py:66-77
  * (10 param groups), torch clip_grad_norm_ (train_utils.py:358-360) and apex-amp's master<->model copies
  * (apex/apex/amp/_process_optimizer.py:14-22). n % valor_adamw_chunk() == 0; chunk_group: int8 [n/chunk], -1 = skip. */

@@ -17,7 +17,15 @@ scales, valor_fine_fused_fwd_fp8) instead of / beside the bf16 bank, on the same
 timed windows per bank, alternating bf16, fp8, bf16, ... so that drift of the shared host hits both alike; the median window is reported
 with the spread. Per (NB, NQ, k): search ms, bank bytes (RetrievalIndex.bank_bytes) and bank read GB/s of each bank, the ratio, and the
 share of the bf16 bank's top-k clips that the fp8 bank returns too (the banks are random unit vectors: neighbouring scores lie closer
-than the quantisation error, so this is a lower bound for structured data). Default --out profiles/search_fp8_bench.json."""
+than the quantisation error, so this is a lower bound for structured data). Default --out profiles/search_fp8_bench.json.
+
+--rescore times the two-stage search (an fp8 bank with an exact store: the fp8 walk returns a shortlist, valor_fine_score_pairs re-scores
+it on the bf16 features, the exact top k is returned) on the same shapes, in one process, the variants alternating inside each of
+`--rounds` rounds: the bf16 bank (exhaustive, the answer the others are held to), the fp8 bank alone (shortlist=0), and the fp8 bank with
+a "device" and with a "host" store at shortlists of k, 2 k, 4 k and 256. Per (NB, NQ, k) and variant: the median ms per search with the
+spread, the time over the fp8-only search of the same run, and the share of the bf16 bank's k best clips that the variant returns.
+The host store's search synchronises once per call (device events still span it: the stream idles meanwhile). Default --out
+profiles/search_rescore_bench.json."""
 import argparse
 import json
 import os
@@ -107,6 +115,56 @@ def compare_banks(a, dev):
             "timing": "device events over warmed calls; the median of `rounds` windows per bank, the banks alternating", "cases": cases}
 
 
+def compare_rescore(a, dev):
+    """--rescore"""
+    free = torch.cuda.mem_get_info()[0]
+    cases = []
+    for NB in a.nb:
+        if NB * NV * (D * 6 + 24) * 1.2 > free:                         # bf16 bank, two code banks, the device store
+            print(f"NB={NB}: the banks do not fit", flush=True)
+            continue
+        g = torch.Generator(device=dev).manual_seed(1)
+        fb = unit_bf16(NB, NV, dev, 2)
+        wb_raw = torch.randn((NB, NV), generator=g, device=dev)
+        bf16 = S.RetrievalIndex.from_features(fb, wb_raw, group="tva")
+        on_dev, on_host = bf16.quantize(exact="device"), bf16.quantize(exact="host")
+        for NQ in a.nq:
+            fa = unit_bf16(NQ, T, dev, 3)
+            wa_raw = torch.randn((NQ, T), generator=g, device=dev)
+            mask = (torch.arange(T, device=dev)[None] < torch.randint(8, T + 1, (NQ, 1), generator=g, device=dev)).float()
+            q = {"feat_t": fa, "mask": mask, "weight": wa_raw}
+            iters = max(3, min(a.iters, int(2e8 / (NB * NQ))))
+            for k in a.k:
+                shortlists = sorted({min(s_, S.MAX_SHORTLIST) for s_ in (k, 2 * k, 4 * k, S.MAX_SHORTLIST)})
+                variants = {"bf16": lambda: bf16.search(None, q, k), "fp8": lambda: on_dev.search(None, q, k, shortlist=0)}
+                for s_ in shortlists:
+                    variants[f"fp8+device/{s_}"] = lambda s_=s_: on_dev.search(None, q, k, shortlist=s_)
+                    variants[f"fp8+host/{s_}"] = lambda s_=s_: on_host.search(None, q, k, shortlist=s_)
+                ms = {name: [] for name in variants}
+                for _ in range(a.rounds):
+                    for name, fn in variants.items():
+                        ms[name].append(timed(fn, iters))
+                want = variants["bf16"]().indices.cpu().tolist()
+                med = {name: sorted(v)[len(v) // 2] for name, v in ms.items()}
+                res = {"NB": NB, "NQ": NQ, "k": k, "iters": iters, "rounds": a.rounds, "default_shortlist": on_dev.default_shortlist(k), "variants": {}}
+                for name, fn in variants.items():
+                    got = fn().indices.cpu().tolist()
+                    res["variants"][name] = {
+                        "search_ms": round(med[name], 4), "search_ms_min_max": [round(min(ms[name]), 4), round(max(ms[name]), 4)],
+                        "over_fp8_only": round(med[name] / med["fp8"], 3),
+                        "topk_overlap": round(sum(len(set(g_) & set(w_)) for g_, w_ in zip(got, want)) / (min(k, NB) * NQ), 4)}
+                res["device_bytes_GB"] = {"bf16": round(bf16.bank_bytes() / 1e9, 4), "fp8+device": round(on_dev.bank_bytes() / 1e9, 4),
+                                          "fp8+host": round(on_host.bank_bytes() / 1e9, 4)}
+                print(json.dumps(res), flush=True)
+                cases.append(res)
+        del bf16, on_dev, on_host, fb, wb_raw
+        torch.cuda.empty_cache()
+    return {"bench": "search_rescore", "geometry": {"T": T, "Nv": NV, "D": D, "feature_dtype": "bfloat16"}, "device": torch.cuda.get_device_name(0),
+            "timing": "device events over warmed calls; the median of `rounds` windows per variant, the variants alternating inside a round",
+            "overlap": "share of the bf16 bank's k best clips that the variant returns (random unit vectors: a lower bound for structured data)",
+            "cases": cases}
+
+
 def write(doc, out):
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as fh:
@@ -122,10 +180,15 @@ def main():
     ap.add_argument("--iters", type=int, default=200, help="most calls per timed window (large cases take fewer)")
     ap.add_argument("--bank-dtype", choices=("bf16", "fp8", "both"), default="bf16", help="fp8 / both: the fp8 bank instead of / beside the bf16 bank")
     ap.add_argument("--rounds", type=int, default=3, help="--bank-dtype fp8 / both: timed windows per bank")
-    ap.add_argument("--out", default=None, help="default profiles/search_bench.json (bf16) or profiles/search_fp8_bench.json (fp8, both)")
+    ap.add_argument("--rescore", action="store_true", help="the two-stage search on an fp8 bank with an exact store beside the bf16 and the fp8-only search")
+    ap.add_argument("--out", default=None, help="default profiles/search_bench.json (bf16), profiles/search_fp8_bench.json (fp8, both) or "
+                                                "profiles/search_rescore_bench.json (--rescore)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "search_bench.py measures on the GPU"
     dev = torch.device("cuda:0")
+    if a.rescore:
+        write(compare_rescore(a, dev), a.out or os.path.join(ROOT, "profiles", "search_rescore_bench.json"))
+        return
     if a.bank_dtype != "bf16":
         write(compare_banks(a, dev), a.out or os.path.join(ROOT, "profiles", "search_fp8_bench.json"))
         return

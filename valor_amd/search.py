@@ -13,14 +13,26 @@ for coarse) and are folded into the running [NQ, k] result by valor_topk_rows(me
 of size [NQ, NB] exists, and nothing comes back to the host before the caller reads `.ids`.
 
 bank_dtype="fp8" (fine banks only, opt-in; csrc/search_fp8.hip): the bank keeps OCP e4m3 codes [NB, Nv, D] (uint8) and one fp32 scale per
-token row [NB, Nv] instead of the features -- half the bytes of a bf16 bank, and no bf16 copy is kept. build / add / from_features /
-quantize() encode the incoming rows with valor_fp8_quantize_rows; search() quantises the query rows per call with the same kernel and
-scores a chunk with valor_fine_fused_fwd_fp8 (the e4m3 MFMA form of valor_fine_fused_fwd, scores only). The quantisation law and the
-score law are restated on the host below (quantize_rows_host, fp8_scores_host). An index built without bank_dtype is what it was.
+token row [NB, Nv] instead of the features -- half the bytes of a bf16 bank. build / add / from_features / quantize() encode the
+incoming rows with valor_fp8_quantize_rows; search() quantises the query rows per call with the same kernel and scores a chunk with
+valor_fine_fused_fwd_fp8 (the e4m3 MFMA form of valor_fine_fused_fwd, scores only). The quantisation law and the score law are restated
+on the host below (quantize_rows_host, fp8_scores_host). An index built without bank_dtype is what it was.
+
+Pair scores (csrc/search_pairs.hip): valor_fine_score_pairs scores every query against ITS OWN list of clips, read by index from a bf16
+feature store (score_pairs; the law restated in fp64 by pair_scores_host). Three things stand on it:
+  rescore(model, queries, candidates)   the exact scores [NQ, C] of given bank indices (-1 allowed: -inf).
+  search(..., within=candidates)        the k best of each query's candidate list, in the search's one total order (score descending,
+                                        then bank index ascending): the rows are sorted ascending and de-duplicated on the device,
+                                        the pairs scored, valor_topk_rows selects, positions map back. Nothing of size [NQ, NB].
+  exact="device" | "host" (fp8 banks)   the bf16 features the codes were made from are kept too, on the device or in pinned host
+                                        memory, and search(..., shortlist=k') becomes a two-stage search: the fp8 walk returns k'
+                                        candidates, they are re-scored on the exact features, the exact top k is returned with the
+                                        exact scores. shortlist=0 (and every index without a store) is the fp8-only search.
 
 Out of scope: dual_softmax (it needs the whole matrix), the va / vta / atv directions, a bank sharded over GPUs,
-deletion, approximate search; for fp8 banks also coarse banks (they need an fp8 GEMM), block-scaled (MX) codes, exact re-scoring of the
-candidates, and fp8 anywhere in validate_ret or training."""
+deletion, approximate search, a coarse first stage, kernel reads of host memory (the host store is gathered and copied), fp32 or
+coarse pair scores; for fp8 banks also coarse banks (they need an fp8 GEMM), block-scaled (MX) codes, and fp8 anywhere in validate_ret
+or training."""
 import ctypes
 
 import torch
@@ -162,6 +174,83 @@ def _scores_fp8(qc, qs, bc, bs, maskA, maskB, wA, wB, out):
     return out
 
 
+# ------------------------------------------------------------------ pair scores: the law on the host (checks only) and the wrapper
+EXACT_MODES = (None, "device", "host")
+MAX_SHORTLIST = 256                   # valor_topk_rows selects at most 256 per row
+# the default shortlist of a two-stage search is min(MAX_SHORTLIST, SHORTLIST_FACTOR * k). The 4 began as a starting point nobody had
+# measured; DESIGN.md section 3.4 (profiles/search_rescore_bench.json) holds the measurement and says whether it moved.
+SHORTLIST_FACTOR = 4
+
+
+def pair_scores_host(featA, maskA, wA, store, wstore, cand):
+    """What valor_fine_score_pairs computes, in fp64 on the CPU: the law of fp8_scores_host on bf16-rounded features, for the pairs
+    (query a, clip cand[a, c]) only, the clip mask all ones. featA [NA, T, D], maskA and SOFTMAXED wA [NA, T], store [NS, Nv, D], SOFTMAXED
+    wstore [NS, Nv], cand int64 [NA, C]. A candidate outside [0, NS) scores -inf. [NA, C] fp64."""
+    bf = lambda t: t.detach().cpu().to(torch.bfloat16).double()
+    f64 = lambda t: t.detach().cpu().double()
+    fa, fs, mA, wa, ws = bf(featA), bf(store), f64(maskA), f64(wA), f64(wstore)
+    cand = cand.detach().cpu().long()
+    NS = fs.shape[0]
+    ok = (cand >= 0) & (cand < NS)
+    safe = torch.where(ok, cand, torch.zeros_like(cand))
+    out = torch.empty(cand.shape, dtype=torch.float64)
+    for a in range(cand.shape[0]):
+        x = torch.einsum("td,cvd->ctv", fa[a], fs[safe[a]]) * mA[a][None, :, None]
+        out[a] = (x.max(dim=2)[0] @ wa[a] + (x.max(dim=1)[0] * ws[safe[a]]).sum(1)) / 2.0
+    return torch.where(ok, out, torch.full_like(out, float("-inf")))
+
+
+def score_pairs(ft, mask, wq, store, wstore, cand):
+    """valor_fine_score_pairs: fp32 [NA, C] scores of the pairs (query a, clip cand[a, c]). ft bf16 [NA, T, D], mask and SOFTMAXED wq
+    fp32 [NA, T], store bf16 [NS, Nv, D] and its SOFTMAXED weights fp32 [NS, Nv] (all contiguous, on the device), cand int64 [NA, C]
+    with unit column stride. D % 64 == 0 and at most 64 tokens on either side; a candidate outside [0, NS) scores -inf."""
+    K._check_gpu(ft, mask, wq, store, wstore, cand)
+    if ft.dtype != torch.bfloat16 or store.dtype != torch.bfloat16 or ft.dim() != 3 or store.dim() != 3 or ft.shape[2] != store.shape[2]:
+        raise ValueError(f"score_pairs: bf16 [NA, T, D] queries and a bf16 [NS, Nv, D] store, got {tuple(ft.shape)} {ft.dtype}, {tuple(store.shape)} {store.dtype}")
+    NA, T, D = ft.shape
+    NS, Nv = store.shape[:2]
+    if D % 64 or D == 0 or not 1 <= T <= 64 or not 1 <= Nv <= 64:
+        raise ValueError(f"score_pairs: D % 64 == 0 and 1 .. 64 tokens on either side (valor_fine_score_pairs has no fallback), got T={T}, Nv={Nv}, D={D}")
+    for name, t, shape in (("mask", mask, (NA, T)), ("wq", wq, (NA, T)), ("wstore", wstore, (NS, Nv))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"score_pairs: {name}: a contiguous fp32 {list(shape)} tensor")
+    if not ft.is_contiguous() or not store.is_contiguous():
+        raise ValueError("score_pairs: contiguous features")
+    if cand.dtype != torch.int64 or cand.dim() != 2 or cand.shape[0] != NA or (cand.shape[1] > 1 and cand.stride(1) != 1):
+        raise ValueError(f"score_pairs: cand: an int64 [{NA}, C] tensor with unit column stride")
+    C = cand.shape[1]
+    out = torch.empty((NA, C), dtype=torch.float32, device=ft.device)
+    if NA and C:
+        lib.call("valor_fine_score_pairs", K._stream(), ft.data_ptr(), mask.data_ptr(), wq.data_ptr(), store.data_ptr(), wstore.data_ptr(), NS,
+                 cand.data_ptr(), cand.stride(0) if NA > 1 else max(cand.stride(0), C), out.data_ptr(), C, NA, C, T, Nv, D)
+    return out
+
+
+def within_prepare(cand, NB):
+    """The candidate rows of a subset search, made ready for the selection (torch ops: the device path and the host plan share them):
+    every row sorted ascending, repeated entries and entries outside [0, NB) turned into -1. A position then stands for one clip, and
+    position order is bank index order, so valor_topk_rows' tie rule (position ascending) is the search's (bank index ascending)."""
+    srt = torch.sort(cand, dim=1)[0]
+    dup = torch.zeros_like(srt, dtype=torch.bool)
+    dup[:, 1:] = srt[:, 1:] == srt[:, :-1]
+    return torch.where(dup | (srt < 0) | (srt >= NB), torch.full_like(srt, -1), srt)
+
+
+def within_finish(top_val, top_pos, srt):
+    """positions of the selection -> bank indices; a slot that selected nothing, or a -1 entry, is -inf / -1"""
+    idx = torch.where(top_pos >= 0, srt.gather(1, top_pos.clamp(min=0)), torch.full_like(top_pos, -1))
+    return torch.where(idx >= 0, top_val, torch.full_like(top_val, float("-inf"))), idx
+
+
+def within_host(score, cand, k):
+    """The plan of search(within=) on the host, on a full score matrix [NQ, NB] (checks only): sort ascending, de-duplicate, gather the
+    pair scores, topk_host, map back. (val fp32 [NQ, k], idx int64 [NQ, k])."""
+    score = score.detach().float().cpu()
+    srt = within_prepare(cand.detach().cpu().long(), score.shape[1])
+    pair = torch.where(srt >= 0, score.gather(1, srt.clamp(min=0)), torch.full(srt.shape, float("-inf")))
+    return within_finish(*topk_host(pair, k), srt)
+
+
 class SearchResult:
     """scores fp32 [NQ, k] and indices int64 [NQ, k] on the device (-inf / -1 where the bank has fewer than k clips); `.ids` reads the
     indices back and maps them to the bank's clip ids (None for -1)."""
@@ -179,18 +268,31 @@ class SearchResult:
         return iter((self.ids, self.scores, self.indices))
 
 
-class _Bank:
-    """one growing device tensor [capacity, ...]; the first n rows are filled"""
+def _pinned_empty(shape, dtype):
+    """host memory the device can copy from without a staging step; plain host memory where there is no GPU (a CPU index is kept, saved
+    and loaded, never searched)"""
+    return torch.empty(shape, dtype=dtype, pin_memory=torch.cuda.is_available())
 
-    def __init__(self, first):
-        self.data, self.n = first.contiguous(), first.shape[0]
+
+class _Bank:
+    """one growing tensor [capacity, ...]; the first n rows are filled. On the device of its first rows, or (pin) in pinned host memory."""
+
+    def __init__(self, first, pin=False):
+        self.pin = pin
+        if pin:
+            self.data = _pinned_empty(tuple(first.shape), first.dtype)
+            self.data.copy_(first)
+        else:
+            self.data = first.contiguous()
+        self.n = first.shape[0]
 
     def append(self, rows):
         if rows.shape[1:] != self.data.shape[1:] or rows.dtype != self.data.dtype:
             raise ValueError(f"bank rows {tuple(rows.shape[1:])} {rows.dtype} against {tuple(self.data.shape[1:])} {self.data.dtype}")
         need = self.n + rows.shape[0]
         if need > self.data.shape[0]:                                  # doubling: add() is amortised
-            grown = torch.empty((max(need, 2 * self.data.shape[0]),) + tuple(self.data.shape[1:]), dtype=self.data.dtype, device=self.data.device)
+            shape = (max(need, 2 * self.data.shape[0]),) + tuple(self.data.shape[1:])
+            grown = _pinned_empty(shape, self.data.dtype) if self.pin else torch.empty(shape, dtype=self.data.dtype, device=self.data.device)
             grown[:self.n] = self.data[:self.n]
             self.data = grown
         self.data[self.n:need] = rows.to(self.data.device)
@@ -214,9 +316,13 @@ class RetrievalIndex:
     late_fusion 'tva' (video, audio: their scores are added). weights are the softmaxed token weights of a fine bank, None for coarse.
     bank_dtype "fp8" (fine banks): the parts are stored as e4m3 codes and row scales. `feats` are then bf16 / fp32 device features,
     quantised here, or -- with `scales` (one fp32 [clips, tokens] tensor per part) and `dtype` (the feature dtype the codes were made
-    from) -- the uint8 codes themselves, on any device."""
+    from) -- the uint8 codes themselves, on any device.
+    exact "device" / "host" (fp8 banks of bf16 features): the features the codes were made from are kept as well, on the bank's device
+    or in pinned host memory (the device then holds only the codes); search() re-scores its shortlist on them. With codes given,
+    `exact_feats` are those features, one bf16 [clips, tokens, D] tensor per part."""
 
-    def __init__(self, group, contra_type, late_fusion, feats, weights, ids, bank_dtype=None, *, scales=None, dtype=None):
+    def __init__(self, group, contra_type, late_fusion, feats, weights, ids, bank_dtype=None, *, scales=None, dtype=None, exact=None,
+                 exact_feats=None):
         if group not in GROUPS:
             raise ValueError(f"group {group!r}: one of {GROUPS} (the va / vta / atv directions are not searchable)")
         if contra_type not in ("fine", "coarse"):
@@ -225,7 +331,12 @@ class RetrievalIndex:
             raise ValueError(f"bank_dtype {bank_dtype!r}: one of {BANK_DTYPES}")
         if bank_dtype == "fp8" and contra_type != "fine":
             raise ValueError("bank_dtype='fp8': only fine banks are covered (a coarse bank needs an fp8 GEMM)")
+        if exact not in EXACT_MODES:
+            raise ValueError(f"exact {exact!r}: one of {EXACT_MODES}")
+        if exact is not None and bank_dtype != "fp8":
+            raise ValueError("exact=: only an fp8 bank keeps a second, exact store (a bf16 bank is its own: rescore() reads it directly)")
         self.group, self.contra_type, self.late_fusion, self.bank_dtype = group, contra_type, bool(late_fusion), bank_dtype
+        self.exact = exact
         nparts = 2 if (self.late_fusion and group == "tva") else 1
         if len(feats) != nparts or len(weights) != nparts:
             raise ValueError(f"group {group!r}, late_fusion={self.late_fusion}: {nparts} feature bank(s), got {len(feats)}")
@@ -236,6 +347,7 @@ class RetrievalIndex:
             if (w is None) != (contra_type == "coarse") or (w is not None and (tuple(w.shape) != tuple(f.shape[:2]) or w.dtype != torch.float32)):
                 raise ValueError("a fine bank carries fp32 token weights [clips, tokens], a coarse bank none")
         self._scales = None
+        self._exact, self._stage = None, {}
         if bank_dtype == "fp8":
             for f in feats:
                 if f.shape[-1] % 128 or f.shape[1] > 64 or f.shape[1] < 1:
@@ -243,12 +355,20 @@ class RetrievalIndex:
                                      f"fallback), got {tuple(f.shape)}")
             if scales is None:
                 self._dtype = feats[0].dtype
+                exact_feats = feats if exact is not None else None
                 feats, scales = zip(*[quantize_rows(f) for f in feats])
             else:
                 if (feats[0].dtype != torch.uint8 or dtype not in (torch.bfloat16, torch.float32) or len(scales) != nparts
                         or any(tuple(s.shape) != tuple(f.shape[:2]) or s.dtype != torch.float32 for f, s in zip(feats, scales))):
                     raise ValueError("an fp8 bank given as codes: uint8 [clips, tokens, D], fp32 scales [clips, tokens], dtype bf16 / fp32")
                 self._dtype = dtype
+            if exact is not None:
+                if (self._dtype != torch.bfloat16 or exact_feats is None or len(exact_feats) != nparts
+                        or any(e.dtype != torch.bfloat16 or tuple(e.shape) != tuple(f.shape) for e, f in zip(exact_feats, feats))):
+                    raise ValueError("exact=: the store holds the bf16 features the codes were made from, one [clips, tokens, D] tensor per "
+                                     "part (valor_fine_score_pairs scores bf16 only)")
+                # "device": a copy of its own (the caller's tensor is not aliased, as the codes are not); "host": pinned, growing
+                self._exact = [_Bank(e, pin=True) if exact == "host" else _Bank(e.to(feats[0].device).clone()) for e in exact_feats]
             self._scales = [_Bank(s) for s in scales]
         self._feats = [_Bank(f) for f in feats]
         self._weights = [None if w is None else _Bank(w) for w in weights]
@@ -280,9 +400,16 @@ class RetrievalIndex:
         """an fp8 bank's fp32 row scales [NB, Nv] per part (`feats` are then the uint8 codes); None otherwise"""
         return None if self._scales is None else [b.view() for b in self._scales]
 
+    @property
+    def exact_feats(self):
+        """the exact store of an fp8 bank: bf16 [NB, Nv, D] per part, on the device or in pinned host memory; None without one"""
+        return None if self._exact is None else [b.view() for b in self._exact]
+
     def bank_bytes(self):
-        """device bytes of the filled rows: features or codes, scales, token weights"""
+        """device bytes of the filled rows: features or codes, scales, token weights, and an exact store kept on the device"""
         banks = self._feats + [b for b in self._weights if b is not None] + (self._scales or [])
+        if self.exact == "device":
+            banks = banks + self._exact
         return sum(b.view().numel() * b.data.element_size() for b in banks)
 
     @property
@@ -295,6 +422,8 @@ class RetrievalIndex:
               "tokens": [int(b.data.shape[1]) if self.contra_type == "fine" else 1 for b in self._feats], "dtype": str(self.dtype)}
         if self.bank_dtype == "fp8":
             fp["bank_dtype"] = "fp8_e4m3"
+        if self.exact is not None:
+            fp["exact"] = self.exact
         return fp
 
     def _check_model(self, model):
@@ -306,11 +435,12 @@ class RetrievalIndex:
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_features(cls, feats, weights=None, ids=None, *, group="tv", contra_type="fine", late_fusion=False, weights_softmaxed=False,
-                      bank_dtype=None):
+                      bank_dtype=None, exact=None):
         """An index over given tensors (device tensors; a CPU index can be saved and loaded but not searched). feats: [NB, Nv, D] (fine)
         or [NB, D] (coarse), or a (video, audio) pair for late_fusion 'tva'. weights (fine, one parts): the RAW token weights [NB, Nv],
         softmaxed here as validate_ret does; None = unit weights, which is what late_fusion always uses. weights_softmaxed: `weights`
-        (one tensor per part) already are the softmaxed values. bank_dtype "fp8": the features are quantised on the device and dropped."""
+        (one tensor per part) already are the softmaxed values. bank_dtype "fp8": the features are quantised on the device and dropped,
+        unless exact "device" / "host" keeps them for the two-stage search."""
         if bank_dtype == "fp8" and contra_type != "fine":
             raise ValueError("bank_dtype='fp8': only fine banks are covered (a coarse bank needs an fp8 GEMM)")
         if group not in GROUPS:
@@ -326,14 +456,15 @@ class RetrievalIndex:
                 raise ValueError("late_fusion scores use unit token weights: pass none")
             ws = [_softmax_ones_mask(torch.ones(f.shape[:2], dtype=torch.float32, device=f.device) if w is None else w) for f, w in zip(feats, raw)]
         ids = list(range(feats[0].shape[0])) if ids is None else list(ids)
-        return cls(group, contra_type, late_fusion, feats, ws, ids, bank_dtype)
+        return cls(group, contra_type, late_fusion, feats, ws, ids, bank_dtype, exact=exact)
 
-    def quantize(self):
-        """A new fp8 index over this fine bf16 / fp32 bank, quantised on the device; this index is untouched."""
+    def quantize(self, exact=None):
+        """A new fp8 index over this fine bf16 / fp32 bank, quantised on the device; this index is untouched. exact "device" / "host":
+        the new index keeps a copy of the bf16 features beside the codes."""
         if self.bank_dtype is not None:
             raise ValueError("the bank is quantised already")
         return RetrievalIndex(self.group, self.contra_type, self.late_fusion, self.feats, [None if w is None else w.clone() for w in self.weights],
-                              self.ids, "fp8")
+                              self.ids, "fp8", exact=exact)
 
     @staticmethod
     def encode_gallery(model, batch, group):
@@ -361,15 +492,15 @@ class RetrievalIndex:
 
     @classmethod
     @torch.no_grad()
-    def build(cls, model, loader, group, bank_dtype=None):
+    def build(cls, model, loader, group, bank_dtype=None, exact=None):
         """Encode every batch of `loader` (valor_collate batches with 'ids') once and keep the bank on the model's device
-        (bank_dtype "fp8": as e4m3 codes, each batch quantised as it arrives)."""
+        (bank_dtype "fp8": as e4m3 codes, each batch quantised as it arrives; exact: the bf16 rows are kept too)."""
         index = None
         model.eval()
         for batch in loader:
             if index is None:
                 feats, ws = cls.encode_gallery(model, batch, group)
-                index = cls(group, model.spec.contra_type, bool(model.spec.late_fusion), feats, ws, list(batch["ids"]), bank_dtype)
+                index = cls(group, model.spec.contra_type, bool(model.spec.late_fusion), feats, ws, list(batch["ids"]), bank_dtype, exact=exact)
             else:
                 index.add(model, batch)
         if index is None:
@@ -394,7 +525,13 @@ class RetrievalIndex:
             for bank, f in zip(self._feats, feats):
                 if f.shape[1:] != bank.data.shape[1:]:
                     raise ValueError(f"bank rows {tuple(f.shape[1:])} against {tuple(bank.data.shape[1:])}")
+                if self._exact is not None and f.dtype != torch.bfloat16:
+                    raise ValueError("an index with an exact store takes bf16 rows")
+            rows = feats
             feats, scales = zip(*[quantize_rows(f) for f in feats])
+            if self._exact is not None:                                  # after the quantiser: it refuses non-finite rows
+                for bank, f in zip(self._exact, rows):
+                    bank.append(f)
             for bank, s in zip(self._scales, scales):
                 bank.append(s)
         for bank, f in zip(self._feats, feats):
@@ -407,9 +544,13 @@ class RetrievalIndex:
     # ------------------------------------------------------------------ persistence
     def save(self, path):
         if self.bank_dtype == "fp8":
-            torch.save({"format": "valor_amd.RetrievalIndex/2", "fingerprint": self.fingerprint(), "ids": self.ids,
-                        "codes": [f.cpu().clone() for f in self.feats], "scales": [s.cpu().clone() for s in self.scales],
-                        "weights": [w.cpu().clone() for w in self.weights]}, path)
+            blob = {"format": "valor_amd.RetrievalIndex/2", "fingerprint": self.fingerprint(), "ids": self.ids,
+                    "codes": [f.cpu().clone() for f in self.feats], "scales": [s.cpu().clone() for s in self.scales],
+                    "weights": [w.cpu().clone() for w in self.weights]}
+            if self.exact is not None:                                   # format 3 = format 2 + the exact store
+                blob["format"] = "valor_amd.RetrievalIndex/3"
+                blob["exact_feats"] = [e.cpu().clone() for e in self.exact_feats]
+            torch.save(blob, path)
             return
         torch.save({"format": "valor_amd.RetrievalIndex/1", "fingerprint": self.fingerprint(), "ids": self.ids,
                     "feats": [f.cpu().clone() for f in self.feats], "weights": [None if w is None else w.cpu().clone() for w in self.weights]}, path)
@@ -417,13 +558,16 @@ class RetrievalIndex:
     @classmethod
     def load(cls, path, device):
         blob = torch.load(path, map_location="cpu", weights_only=True)      # tensors, strings, numbers, lists and dicts only
-        if not isinstance(blob, dict) or blob.get("format") not in ("valor_amd.RetrievalIndex/1", "valor_amd.RetrievalIndex/2"):
+        if not isinstance(blob, dict) or blob.get("format") not in ("valor_amd.RetrievalIndex/1", "valor_amd.RetrievalIndex/2",
+                                                                         "valor_amd.RetrievalIndex/3"):
             raise ValueError(f"{path}: not a RetrievalIndex file")
         fp = blob["fingerprint"]
-        if blob["format"].endswith("/2"):
+        if blob["format"].endswith(("/2", "/3")):
+            third = blob["format"].endswith("/3")
             feature_dtype = {str(t): t for t in (torch.bfloat16, torch.float32)}.get(fp.get("dtype"))
             index = cls(fp["group"], fp["contra_type"], fp["late_fusion"], [c.to(device) for c in blob["codes"]],
-                        [w.to(device) for w in blob["weights"]], blob["ids"], "fp8", scales=[s.to(device) for s in blob["scales"]], dtype=feature_dtype)
+                        [w.to(device) for w in blob["weights"]], blob["ids"], "fp8", scales=[s.to(device) for s in blob["scales"]], dtype=feature_dtype,
+                        exact=fp.get("exact") if third else None, exact_feats=blob["exact_feats"] if third else None)
         else:
             index = cls(fp["group"], fp["contra_type"], fp["late_fusion"], [f.to(device) for f in blob["feats"]],
                         [None if w is None else w.to(device) for w in blob["weights"]], blob["ids"])
@@ -533,16 +677,116 @@ class RetrievalIndex:
                 outs[0].add_(outs[1])                                    # late fusion: the tv and ta scores added (test.py:571-579)
             yield c0, outs[0]
 
+    # ------------------------------------------------------------------ pair scores
+    def _pair_store(self):
+        """the bf16 feature store per part that pair scores read, or ValueError with the reason (there is no fallback)"""
+        if self.contra_type != "fine":
+            raise ValueError("pair scores cover fine banks only (a coarse score is one GEMM row: use scores())")
+        if self.bank_dtype == "fp8":
+            if self._exact is None:
+                raise ValueError("this fp8 bank keeps no exact store (build it with exact='device' or exact='host'): its candidates cannot be "
+                                 "re-scored exactly")
+            return self._exact
+        if self.dtype != torch.bfloat16:
+            raise ValueError(f"pair scores cover bf16 banks only (valor_fine_score_pairs), this bank is {self.dtype}")
+        return self._feats
+
+    def _pair_queries(self, ft):
+        store = self._pair_store()
+        if ft.dtype != torch.bfloat16 or ft.shape[1] > 64 or ft.shape[2] % 64 or any(b.data.shape[1] > 64 for b in store):
+            raise ValueError(f"pair scores take bf16 queries, D % 64 == 0 and at most 64 tokens on either side (valor_fine_score_pairs has no "
+                             f"fallback), got {tuple(ft.shape)} {ft.dtype}")
+        return store
+
+    def _check_candidates(self, cand, NQ):
+        if not torch.is_tensor(cand) or cand.dtype != torch.int64 or cand.dim() != 2 or cand.shape[0] != NQ or cand.device != self.device:
+            raise ValueError(f"candidates: an int64 [{NQ}, C] tensor of bank indices on {self.device} (-1 = no candidate)")
+        return cand.contiguous()
+
+    def _pair_scores(self, ft, mask, wq, cand):
+        """fp32 [NQ, C]: the exact scores of the bank indices cand (int64 [NQ, C] on the device; outside [0, NB): -inf), the parts of a
+        late-fusion bank added. A host store costs one synchronisation: the indices are read back, their rows gathered into a pinned
+        staging buffer and copied once; the kernel then reads the staging buffer with cand = arange."""
+        store = self._pair_queries(ft)
+        NQ, C = cand.shape
+        NB = len(self)
+        out = None
+        if self.exact == "host" and NQ * C:
+            ok = (cand >= 0) & (cand < NB)
+            flat = torch.where(ok, cand, torch.zeros_like(cand)).view(-1)
+            local = torch.where(ok, torch.arange(NQ * C, dtype=torch.int64, device=cand.device).view(NQ, C), torch.full_like(cand, -1))
+            flat_host = flat.cpu()                                       # the one synchronisation of a host-store search
+        for part, bank in enumerate(store):
+            ws = self._weights[part].view()
+            if self.exact == "host" and NQ * C:
+                rows = (NQ * C,) + tuple(bank.data.shape[1:])
+                if part not in self._stage or self._stage[part][0].shape[0] < NQ * C:          # one pair of buffers per part, reused
+                    self._stage[part] = (_pinned_empty(rows, torch.bfloat16), torch.empty(rows, dtype=torch.bfloat16, device=cand.device))
+                host, devbuf = self._stage[part][0][:NQ * C], self._stage[part][1][:NQ * C]
+                torch.index_select(bank.view(), 0, flat_host, out=host)
+                devbuf.copy_(host, non_blocking=True)
+                sc = score_pairs(ft, mask, wq, devbuf, ws.index_select(0, flat), local)
+            else:
+                sc = score_pairs(ft, mask, wq, bank.view(), ws, cand)
+            out = sc if out is None else out.add_(sc)                    # late fusion: the tv and ta scores added, as the chunk path does
+        return out
+
     @torch.no_grad()
-    def search(self, model, batch_or_tokens, k, chunk=None):
+    def rescore(self, model, batch_or_tokens, candidates):
+        """The exact scores fp32 [NQ, C] of given bank indices: candidates int64 [NQ, C] on the device, -1 (or anything outside the bank)
+        = no candidate, scored -inf. A bf16 fine bank is read directly, an fp8 bank through its exact store (a "host" store: one
+        synchronisation per call); under late_fusion the two parts' pair scores are added. Coarse banks, fp32 banks and fp8 banks
+        without a store raise ValueError. Queries as in search()."""
+        self._pair_store()
+        ft, mask, wq = self._queries(model, batch_or_tokens)
+        return self._pair_scores(ft, mask, wq, self._check_candidates(candidates, ft.shape[0]))
+
+    def _select_within(self, ft, mask, wq, cand, k):
+        """the k best of every row of candidates under the search's total order: (scores [NQ, k], bank indices [NQ, k])"""
+        if cand.shape[1] == 0:                                           # an empty list: nothing to select from
+            NQ = cand.shape[0]
+            return (torch.full((NQ, k), float("-inf"), dtype=torch.float32, device=cand.device), torch.full((NQ, k), -1, dtype=torch.int64, device=cand.device))
+        srt = within_prepare(cand, len(self))
+        top_val, top_pos = topk_rows(self._pair_scores(ft, mask, wq, srt), k)
+        return within_finish(top_val, top_pos, srt)
+
+    def default_shortlist(self, k):
+        """candidates the fp8 walk of a two-stage search returns for re-scoring when the caller names no number"""
+        return min(MAX_SHORTLIST, SHORTLIST_FACTOR * int(k))
+
+    @torch.no_grad()
+    def search(self, model, batch_or_tokens, k, chunk=None, *, within=None, shortlist=None):
         """The k best clips of every query: SearchResult (ids: list of lists, on demand; scores, indices: device [NQ, k]), best first,
         equal scores in index order. model None: batch_or_tokens = {'feat_t', 'mask', 'weight'} holds encoded queries (feat_t [NQ, T, D]
-        or [NQ, D]; the text mask and RAW token weights of a fine model, None = ones)."""
+        or [NQ, D]; the text mask and RAW token weights of a fine model, None = ones).
+        within (int64 [NQ, C] on the device; -1 and repeats allowed): the k best of each query's own candidate list instead of the
+        bank, by exact pair scores (rescore()'s coverage), in the same order; the bank is not walked.
+        shortlist (an fp8 bank with an exact store): the fp8 walk returns `shortlist` candidates (k <= shortlist <= 256), they are
+        re-scored on the exact features and the exact top k is returned with the exact scores. None = default_shortlist(k) = min(256,
+        4 k); 0 = fp8 scores only, which is all an index without a store does. With a "host" store the shortlist indices are read back,
+        their rows gathered and copied: ONE host synchronisation per search; with a "device" store there is none."""
         if not 1 <= int(k) <= 256:
             raise ValueError("1 <= k <= 256 (valor_topk_rows)")
         k = int(k)
+        if shortlist is None:
+            shortlist = self.default_shortlist(k) if (self._exact is not None and within is None) else 0
+        shortlist = int(shortlist)
+        if shortlist:
+            if within is not None:
+                raise ValueError("within= scores its candidates exactly already: no shortlist")
+            if self._exact is None:
+                raise ValueError("shortlist: a two-stage search needs an fp8 bank with an exact store (exact='device' or 'host')")
+            if not k <= shortlist <= MAX_SHORTLIST:
+                raise ValueError(f"k <= shortlist <= {MAX_SHORTLIST} (valor_topk_rows), got k={k}, shortlist={shortlist}")
+        if within is not None:
+            self._pair_store()
         ft, mask, wq = self._queries(model, batch_or_tokens)
         NQ = ft.shape[0]
+        if within is not None:
+            return SearchResult(*self._select_within(ft, mask, wq, self._check_candidates(within, NQ), k), self.ids)
+        if shortlist:
+            self._pair_queries(ft)
+            k_out, k = k, shortlist
         top_val = torch.full((NQ, k), float("-inf"), dtype=torch.float32, device=ft.device)
         top_idx = torch.full((NQ, k), -1, dtype=torch.int64, device=ft.device)
         ws = None
@@ -551,6 +795,8 @@ class RetrievalIndex:
             if ws is None or ws.numel() < need:
                 ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=ft.device)
             topk_rows(score, k, col_base=c0, state=(top_val, top_idx), workspace=ws)
+        if shortlist:                                                    # the second stage: exact scores of the fp8 walk's candidates
+            top_val, top_idx = self._select_within(ft, mask, wq, top_idx, k_out)
         return SearchResult(top_val, top_idx, self.ids)
 
     @torch.no_grad()
