@@ -561,6 +561,30 @@ int valor_beam_select(void* stream, const float* logits, int64_t ld, int64_t row
  * The caller advances offset by R * ceil(V / 4) per step. One workgroup per row, no atomics: deterministic. */
 int valor_sample_tokens(void* stream, const float* logits, int64_t ld, int R, int V, uint64_t seed, uint64_t offset, int64_t eos,
                         uint8_t* unfinished, int64_t* tok, int64_t* sents, int64_t sents_ld, float* logprobs, int64_t lp_ld);
+/* valor_sample_tokens with temperature, top-k and nucleus (top-p) filters, one launch. Per row r with unfinished[r] != 0:
+ *   1. y_w = logits[r, w] * inv_temperature: one rounded fp32 multiply.
+ *   2. top-k, when 1 <= top_k < #{w : y_w > -inf}: theta_k = the top_k-th largest y counting duplicates, S_k = {w : y_w >= theta_k}
+ *      (more than top_k columns when values tie at theta_k). Otherwise S_k = {w : y_w > -inf}. Exact: integer comparisons only.
+ *   3. top-p, when top_p < 1: M = sum over S_k of exp(y_w - max y); walking S_k in descending value, theta_p is the value at which the
+ *      running mass first reaches top_p * M; S = {w in S_k : y_w >= theta_p} (never empty: the arg max is always kept). With top_p == 1,
+ *      S = S_k. The masses are sums of floor(exp(y_w - max y) * 2^40) in 64-bit integers: independent of the summation order, and the
+ *      ratio compared with top_p is within 1e-6 of its exact value, so a boundary closer than that may fall either way.
+ *   4. the draw is valor_sample_tokens' on the row where(w in S, y_w, -inf): the same Philox4x32-10 counters offset + r * ceil(V / 4)
+ *      + w / 4, word w % 4, indexed by the column of the FULL row (filtering moves no uniform), the same u grid, the same key
+ *      y_w - logf(-logf(u_w)), ties to the lower index.
+ *   5. logprobs[r * lp_ld] = y_w* - log sum_S exp(y): the log-probability under the distribution drawn from (fp32 statistics).
+ *   6. tok / sents / unfinished, rows with unfinished[r] == 0 and rows with a NaN (or no column above -inf) behave as in
+ *      valor_sample_tokens. kept[r] = |S| and cut[r] = min over S of y, where the pointers are not NULL; a row that does not draw
+ *      (finished before, or NaN) writes kept 0 and cut NaN.
+ *   7. inv_temperature == 1, top-k off (0 or >= V) and top_p == 1: tok, sents, logprobs and unfinished are bit-identical to
+ *      valor_sample_tokens (that kernel is launched when kept and cut are NULL).
+ * R == 0: no-op. VALOR_ERR_ARG, before any launch: a null logits / unfinished / tok / sents / logprobs, R < 0, V < 1 or > 65535 (the
+ * bound of the integer masses), ld < V, eos outside [0, V), negative sents_ld / lp_ld / top_k, inv_temperature not finite or <= 0,
+ * top_p NaN, <= 0 or > 1. One 1024-thread workgroup per row, 17 KiB of LDS, no workspace, no floating-point atomic: the result does not
+ * depend on how the threads split the row, graph replay equals eager issue. The caller advances offset by R * ceil(V / 4) per step. */
+int valor_sample_tokens_filtered(void* stream, const float* logits, int64_t ld, int R, int V, uint64_t seed, uint64_t offset, int64_t eos,
+                                 float inv_temperature, int top_k, float top_p, uint8_t* unfinished, int64_t* tok, int64_t* sents,
+                                 int64_t sents_ld, float* logprobs, int64_t lp_ld, int32_t* kept, float* cut);
 /* ---- the SCST caption reward on the device: CIDEr-D + BLEU-4 per hypothesis row (csrc/reward.hip; the rules are those of
  * valor_amd/scst.py: scorer/cider_scorer.py:119-200 with n = 1..4 and sigma 6, scorer/bleu_scorer.py:202-250 option 'closest').
  *   KEY of the n-gram (t_0 .. t_{n-1}): (t_i + 1) in bits [16 i, 16 i + 16) of a uint64, unused fields 0 -- exact, n = the number of

@@ -7,7 +7,11 @@ caption-msrvtt shape (task cap%tva%tv, a CaptionScorer of 20 synthetic reference
 sampled decoding, scoring and the loss pass (forward + backward), and one scorer call of B hypotheses. GEN_SCORER=host (default) scores
 with scst.CaptionScorer on the host, GEN_SCORER=device with scst.DeviceCaptionScorer (valor_caption_reward: one launch for the sample and
 greedy rows of both groups, timed up to a device synchronisation); score_ms / scorer_ms_per_call are those of the scorer in use.
-usage: [GEN_MODES=greedy,beam3,sample,scst] [GEN_SCORER=host|device] python tools/gen_bench.py out.json [batch] [max_len]"""
+Mode 'sampled' is the captioner's sampling: generate_cap(mode='sample') with the filters off, top_k 50, top_p 0.9, temperature 0.7 +
+top_k 50 + top_p 0.9, and num_return_sequences 4 at batch / 4 clips (the same number of decoder rows), each as captions/s; and the time
+of one sampler launch at R = batch rows, V = 30522 and 49408 -- valor_sample_tokens next to valor_sample_tokens_filtered under the same
+settings -- between device events in this process (20 launches per event pair, the median of 15 pairs, after a warm-up).
+usage: [GEN_MODES=greedy,beam3,sample,sampled,scst] [GEN_SCORER=host|device] python tools/gen_bench.py out.json [batch] [max_len]"""
 import json
 import os
 import sys
@@ -51,6 +55,63 @@ with torch.no_grad():
         t = timed(lambda: decode.generate_cap(model, batch, ["tva"], beam_size=beam, max_generation_len=L, mode=mode), reps=2)
         res[name] = {"seconds": round(t, 3), "captions_per_s": round(B / t, 1), "tokens_per_s": round(B * L / t, 1),
                      "ms_per_decoding_step": round((t * 1e3 - res["encode_ms"]) / L, 2)}
+
+SAMPLED = (("filters_off", {}), ("top_k_50", {"top_k": 50}), ("top_p_0.9", {"top_p": 0.9}),
+           ("t0.7_k50_p0.9", {"temperature": 0.7, "top_k": 50, "top_p": 0.9}))
+
+
+def sampler_launch_us(R, V, inv, k, p, filtered):
+    """one sampler launch on R rows of V logits: device events around 20 launches, the median of 15 such groups"""
+    from valor_amd import kernels as K
+    logits = torch.zeros((R, (V + 31) // 32 * 32), dtype=torch.float32, device=dev)[:, :V]
+    logits.copy_(torch.randn((R, V), generator=torch.Generator().manual_seed(V)) * 2)
+    unf = torch.ones(R, dtype=torch.bool, device=dev)
+    tok = torch.empty(R, dtype=torch.int64, device=dev)
+    sents = torch.empty((R, 1), dtype=torch.int64, device=dev)
+    lp = torch.empty((R, 1), dtype=torch.float32, device=dev)
+    kept = torch.empty(R, dtype=torch.int32, device=dev)
+
+    def launch(i):
+        if filtered:                                        # (kept given: the filtered kernel runs even with every filter off)
+            K.sample_tokens_filtered(logits, 1, i * R * V, 0, unf, tok, sents[:, 0], lp[:, 0], inv, k, p, kept)
+        else:
+            K.sample_tokens(logits, 1, i * R * V, 0, unf, tok, sents[:, 0], lp[:, 0])
+    logits[:, 0] = -float("inf")                            # column 0 is the end token here: never drawn, no row finishes
+    for i in range(10):
+        launch(i)
+    times = []
+    for _ in range(15):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(20):
+            launch(i)
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1) * 1e3 / 20)
+    assert bool(unf.all())
+    return round(sorted(times)[len(times) // 2], 2)
+
+
+if "sampled" in MODES:
+    with torch.no_grad():
+        model.eval()
+        out = res["sampled"] = {}
+        for name, kw in SAMPLED:
+            t = timed(lambda: decode.generate_cap(model, batch, ["tva"], max_generation_len=L, mode="sample", seed=1, **kw), reps=3)
+            out[name] = {"seconds": round(t, 4), "captions_per_s": round(B / t, 1),
+                         "ms_per_decoding_step": round((t * 1e3 - res["encode_ms"]) / L, 3)}
+        n = 4
+        small = {k: (v[:B // n] if torch.is_tensor(v) else v) for k, v in batch.items()}
+        t = timed(lambda: decode.generate_cap(model, small, ["tva"], max_generation_len=L, mode="sample", seed=1, temperature=0.7, top_k=50,
+                                              top_p=0.9, num_return_sequences=n), reps=3)
+        out[f"t0.7_k50_p0.9_x{n}_at_{B // n}_clips"] = {"seconds": round(t, 4), "captions_per_s": round(B // n * n / t, 1)}
+        kern = res["sampler_launch_us"] = {}
+        for V in (30522, 49408):
+            kern[f"V{V}"] = {"valor_sample_tokens": sampler_launch_us(B, V, 1.0, 0, 1.0, False),
+                             "filtered_all_off": sampler_launch_us(B, V, 1.0, 0, 1.0, True),
+                             "filtered_top_k_50": sampler_launch_us(B, V, 1.0, 50, 1.0, True),
+                             "filtered_top_p_0.9": sampler_launch_us(B, V, 1.0, 0, 0.9, True),
+                             "filtered_t0.7_k50_p0.9": sampler_launch_us(B, V, 1 / 0.7, 50, 0.9, True)}
 
 if "scst" in MODES:
     import numpy as np

@@ -538,11 +538,69 @@ def set_sampler_state(model, st):
         sampler_of(model).set_state(st)
 
 
-def decode_sample_cached(sess, b, max_len, stream):
+class Sampling:
+    """the filters of the sampled decode: temperature (the logits are divided by it), top_k (0: off; ties at the k-th value are kept),
+    top_p (the nucleus, over what top-k left; 1: off). The defaults are all off: the unmodified softmax."""
+    __slots__ = ("temperature", "top_k", "top_p")
+
+    def __init__(self, temperature=1.0, top_k=0, top_p=1.0):
+        temperature, top_p = float(temperature), float(top_p)
+        if temperature == 0.0:
+            raise ValueError("Sampling: temperature 0 is the arg max -- use mode='greedy'")
+        if not (temperature > 0.0 and temperature != float("inf")):
+            raise ValueError(f"Sampling: temperature {temperature!r} must be a finite number > 0")
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError(f"Sampling: top_k {top_k!r} must be an integer >= 0 (0: off)")
+        if not (0.0 < top_p <= 1.0):
+            raise ValueError(f"Sampling: top_p {top_p!r} must be in (0, 1] (1: off)")
+        self.temperature, self.top_k, self.top_p = temperature, int(top_k), top_p
+
+    @property
+    def off(self):
+        return self.temperature == 1.0 and self.top_k == 0 and self.top_p == 1.0
+
+    @property
+    def inv_temperature(self):
+        """1 / temperature rounded to fp32: what the kernel multiplies the logits by"""
+        return float(torch.tensor(1.0 / self.temperature, dtype=torch.float32))
+
+    def __repr__(self):
+        return f"Sampling(temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p})"
+
+
+def filter_row(y, top_k=0, top_p=1.0):
+    """Rules 2 and 3 of valor_sample_tokens_filtered (include/valor_hip.h) restated on the host for ONE row y (any float dtype, already
+    multiplied by 1 / temperature, no NaN) -> (kept, cut): the size of the kept set S and min over S of y (kept 0, cut NaN when no column
+    is above -inf). The masses are summed in fp64."""
+    y = y.detach().double().cpu().reshape(-1)
+    vals = torch.sort(y[y > -float("inf")], descending=True).values
+    if vals.numel() == 0:
+        return 0, float("nan")
+    if 1 <= top_k < vals.numel():
+        vals = vals[vals >= vals[top_k - 1]]
+    if top_p < 1.0:
+        mass = torch.cumsum(torch.exp(vals - vals[0]), 0)
+        first = int((mass >= top_p * mass[-1]).nonzero()[0])
+        vals = vals[vals >= vals[first]]
+    return int(vals.numel()), float(vals[-1])
+
+
+def _draw_step(logits, stream, sampling, unfinished, tok, sents_t, logprobs_t):
+    """one sampler launch: valor_sample_tokens, or the filtered kernel when a filter is on"""
+    seed, off = stream.take(logits.shape[0], logits.shape[1])
+    if sampling is None or sampling.off:
+        K.sample_tokens(logits, seed, off, EOS, unfinished, tok, sents_t, logprobs_t)
+    else:
+        K.sample_tokens_filtered(logits, seed, off, EOS, unfinished, tok, sents_t, logprobs_t, sampling.inv_temperature, sampling.top_k,
+                                 sampling.top_p)
+
+
+def decode_sample_cached(sess, b, max_len, stream, sampling=None):
     """VALOR.decode_greedy mode 'sample' (pretrain.py:1005-1020) on a DecodeSession: one step, then one valor_sample_tokens launch that draws
     from softmax(logits), writes the logP of the draw and does the [SEP] bookkeeping. The tokens stay on the device; whether every row has
     ended is asked every eighth step, as in decode_greedy_cached. -> (sents int64 [b, max_len], logprobs fp32 [b, max_len]); after a row's
-    first [SEP] its tokens are [SEP] and its logprobs 0."""
+    first [SEP] its tokens are [SEP] and its logprobs 0. sampling: a Sampling (None or all off: the unmodified softmax); the sampler
+    launch sits outside the captured step and takes its parameters by value, so a kept session serves any setting."""
     dev = sess.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
     logprobs = torch.zeros((b, max_len), device=dev)
@@ -550,14 +608,13 @@ def decode_sample_cached(sess, b, max_len, stream):
     tok = torch.empty(b, dtype=torch.long, device=dev)
     for t in range(max_len):
         logits = sess.step(None if t == 0 else tok)
-        seed, off = stream.take(b, logits.shape[1])
-        K.sample_tokens(logits, seed, off, EOS, unfinished, tok, sents[:, t], logprobs[:, t])
+        _draw_step(logits, stream, sampling, unfinished, tok, sents[:, t], logprobs[:, t])
         if t % 8 == 7 and t + 1 < max_len and not bool(unfinished.any()):
             break
     return sents, logprobs
 
 
-def decode_sample(step, b, max_len, stream):
+def decode_sample(step, b, max_len, stream, sampling=None):
     """decode_sample_cached on the re-run path (_Stepper: VALOR_KV_CACHE=0, a cross-attention block per modality); the same draws"""
     dev = step.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
@@ -567,8 +624,7 @@ def decode_sample(step, b, max_len, stream):
     state = None
     for t in range(max_len):
         logits = step.logits(state, b).contiguous()
-        seed, off = stream.take(b, logits.shape[1])
-        K.sample_tokens(logits, seed, off, EOS, unfinished, tok, sents[:, t], logprobs[:, t])
+        _draw_step(logits, stream, sampling, unfinished, tok, sents[:, t], logprobs[:, t])
         w_host = tok.cpu().unsqueeze(1)
         state = w_host if state is None else torch.cat((state, w_host), dim=1)
         if not bool(unfinished.any()):
@@ -576,9 +632,9 @@ def decode_sample(step, b, max_len, stream):
     return sents, logprobs
 
 
-def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None):
+def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None, sampling=None):
     """{group: (sequences, logprobs | None)} for the query groups present, through the K|V-cached session or the re-run path.
-    stream: a SampleStream (after begin_call) -> sampled decoding (beam 1)"""
+    stream: a SampleStream (after begin_call) -> sampled decoding (beam 1) under `sampling` (a Sampling or None)"""
     if isinstance(prompt, str):
         prompt = model.get_task_prompt(PROMPTS[prompt], b) if model.use_task_prompt else None
     if stream is not None:
@@ -594,13 +650,13 @@ def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, s
         if sess is not None:
             sess.begin_group(ranges[g] if kv_layers is not None else None, prompt)
             if stream is not None:
-                out[g] = decode_sample_cached(sess, b, max_len, stream)
+                out[g] = decode_sample_cached(sess, b, max_len, stream, sampling)
             else:
                 out[g] = (decode_beam_cached(sess, b, beam, max_len), None) if beam > 1 else decode_greedy_cached(sess, b, max_len)
         else:
             step = _Stepper(model, g, kv_layers, ranges, prompt, b)
             if stream is not None:
-                out[g] = decode_sample(step, b, max_len, stream)
+                out[g] = decode_sample(step, b, max_len, stream, sampling)
             else:
                 out[g] = (decode_beam(step, b, beam, max_len), None) if beam > 1 else decode_greedy(step, b, max_len)
     return out
@@ -629,14 +685,40 @@ def _sample_stream(model, seed):
     return (sampler_of(model) if seed is None else SampleStream(seed)).begin_call()
 
 
+def _repeat_clips(model, kv_layers, b, n):
+    """every clip's per-layer K|V rows n times, clip-major (rows i * n .. i * n + n - 1 are clip i): one row gather per layer, the
+    way generate_qa serves sample_num"""
+    if kv_layers is None:
+        return None
+    idx = model._dev(torch.arange(b, dtype=torch.long).repeat_interleave(n))
+    rows_of = lambda kvs: None if kvs is None else [ops.gather_rows(kv.reshape(b, -1), idx).view(idx.numel(), *kv.shape[1:]) for kv in kvs]
+    return _BlockKV(rows_of(kv_layers.v), rows_of(kv_layers.a)) if isinstance(kv_layers, _BlockKV) else rows_of(kv_layers)
+
+
 @torch.no_grad()
-def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, mode=None, seed=None):
+def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None, top_k=None,
+                 top_p=None, num_return_sequences=1):
     """VALOR.generate_cap, model/pretrain.py:914-985 -> {'generated_sequences_t_v' | '_t_va' | '_t_a' (+ 'logprobs_*' when greedy or
     sampled)}. mode: None (beam search when beam_size > 1, else greedy), 'greedy' (whatever beam_size says) or 'sample' (decode_greedy's
     sample mode, :1007-1011: a draw from softmax(logits) per step, logprobs_* = the logP of the draws). seed: the sampled draws' seed
-    (None: the model's own SampleStream, seeded from opts.seed, advances one call)."""
+    (None: the model's own SampleStream, seeded from opts.seed, advances one call).
+    mode 'sample' only: temperature / top_k / top_p filter the distribution of every step (Sampling; None: the model's options
+    sample_temperature / sample_top_k / sample_top_p, absent = off; logprobs_* are then the logP under the filtered distribution), and
+    num_return_sequences = n draws n captions per clip: the encoders and the K|V projections run once per clip, the decoder runs b * n
+    rows, and every output is [b * n, L] clip-major (rows i * n .. i * n + n - 1 belong to clip i)."""
     if mode not in (None, "greedy", "sample"):
         raise ValueError(f"generate_cap: mode {mode!r} (None, 'greedy' or 'sample')")
+    n = int(num_return_sequences)
+    if n != num_return_sequences or n < 1:
+        raise ValueError(f"generate_cap: num_return_sequences {num_return_sequences!r} must be an integer >= 1")
+    sampling = None
+    if mode == "sample":
+        from .model.valor import _opt
+        sampling = Sampling(_opt(model.opts, "sample_temperature", 1.0) if temperature is None else temperature,
+                            _opt(model.opts, "sample_top_k", 0) if top_k is None else top_k,
+                            _opt(model.opts, "sample_top_p", 1.0) if top_p is None else top_p)
+    elif temperature is not None or top_k is not None or top_p is not None or n != 1:
+        raise ValueError("generate_cap: temperature / top_k / top_p / num_return_sequences need mode='sample'")
     beam = model.beam_size if beam_size is None else beam_size
     if mode is not None:
         beam = 1
@@ -645,9 +727,12 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
     model.eval()
     try:
         b, kv_layers, ranges = encode_for_generation(model, batch, groups)
+        if n > 1:
+            kv_layers = _repeat_clips(model, kv_layers, b, n)
+            b *= n
         out = {}
         stream = _sample_stream(model, seed) if mode == "sample" else None
-        for g, (seq, lp) in _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, stream).items():
+        for g, (seq, lp) in _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, stream, sampling).items():
             key = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]
             out["generated_sequences_" + key] = seq
             if lp is not None:

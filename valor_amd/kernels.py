@@ -594,6 +594,25 @@ def sample_tokens(logits, seed, offset, eos, unfinished, tok, sents, logprobs):
              _ptr(sents), sents.stride(0), _ptr(logprobs), logprobs.stride(0))
 
 
+def sample_tokens_filtered(logits, seed, offset, eos, unfinished, tok, sents, logprobs, inv_temperature=1.0, top_k=0, top_p=1.0, kept=None,
+                           cut=None):
+    """sample_tokens with temperature, top-k and nucleus filters (valor_sample_tokens_filtered; the law: include/valor_hip.h): the draw
+    comes from softmax over S of y = logits * inv_temperature, S = what top-k (ties at the k-th value kept; 0: off) and then top-p over
+    its mass (1: off) leave. kept int32 [R] / cut fp32 [R] (optional) receive |S| and min over S of y. The arguments of sample_tokens
+    keep their meaning; with every filter off and no kept / cut this IS sample_tokens."""
+    _check_gpu(logits, unfinished, tok, sents, logprobs, kept, cut)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    assert unfinished.dtype == torch.bool and unfinished.is_contiguous() and tok.dtype == torch.int64 and tok.is_contiguous()
+    assert sents.dtype == torch.int64 and logprobs.dtype == torch.float32 and sents.dim() == logprobs.dim() == 1
+    R, V = logits.shape
+    assert unfinished.numel() == tok.numel() == sents.numel() == logprobs.numel() == R
+    assert kept is None or (kept.dtype == torch.int32 and kept.is_contiguous() and kept.numel() == R)
+    assert cut is None or (cut.dtype == torch.float32 and cut.is_contiguous() and cut.numel() == R)
+    lib.call("valor_sample_tokens_filtered", _stream(), _ptr(logits), logits.stride(0), R, V, int(seed), int(offset), int(eos),
+             float(inv_temperature), int(top_k), float(top_p), _ptr(unfinished), _ptr(tok), _ptr(sents), sents.stride(0), _ptr(logprobs),
+             logprobs.stride(0), None if kept is None else _ptr(kept), None if cut is None else _ptr(cut))
+
+
 def fbank(wave, offsets, slice_idx, tables, melbins, T, mean, std, out=None):
     """log-mel filterbank of the selected slices in the model's layout (valor_fbank): wave = the clips packed back to back, fp32 or int16
     PCM [n]; offsets int64 [B + 1]; slice_idx int32 [B, A] (-1: no audio); tables = preprocess.fbank_tables(...).to_device() (window,
