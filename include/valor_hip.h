@@ -585,6 +585,30 @@ int valor_sample_tokens(void* stream, const float* logits, int64_t ld, int R, in
 int valor_sample_tokens_filtered(void* stream, const float* logits, int64_t ld, int R, int V, uint64_t seed, uint64_t offset, int64_t eos,
                                  float inv_temperature, int top_k, float top_p, uint8_t* unfinished, int64_t* tok, int64_t* sents,
                                  int64_t sents_ld, float* logprobs, int64_t lp_ld, int32_t* kept, float* cut);
+/* generation controls of one decoding step, in place on fp32 logits [R, V] (row pitch ld >= V), one launch between the step and the
+ * selection (arg max, valor_beam_select, valor_sample_tokens[_filtered]). Row r reads its own generated tokens (prompt and question
+ * tokens are not part of it): t int64 ids with unit stride at hist + (r % b) * hist_stride_s + (r / b) * hist_stride_k -- the two
+ * strides the way valor_beam_select takes them: beam-major rows r = k * b + s over words kept as [b, beam, max_len] pass
+ * hist_stride_s = beam * max_len, hist_stride_k = max_len; a row-ordered history passes b = R, hist_stride_k = 0. t is the same for
+ * all rows. Per row r where active is null or active[r] != 0:
+ *   1. repetition penalty, when penalty != 1: for every DISTINCT token w of hist[r, 0..t) with 0 <= w < V,
+ *      z_w = z_w > 0 ? z_w * inv_penalty : z_w * penalty -- one rounded fp32 multiply, applied once however often w occurs
+ *      (inv_penalty = 1 / penalty rounded to fp32 by the caller; -inf stays -inf, +-0 and NaN take the * penalty branch).
+ *   2. no repeated n-gram, when ngram = n >= 1 and t >= n - 1: for every i in [0, t - n] with hist[r, i .. i+n-2] ==
+ *      hist[r, t-n+1 .. t-1], z_w = -inf for w = hist[r, i+n-1] (n == 1: every token of the history). Overlapping and multiple
+ *      matches all count; ids are compared as int64 values.
+ *   3. minimum length: when t < min_len, z_eos = -inf.
+ *   4. suppressed tokens: z_w = -inf for every w of suppress[0 .. n_suppress) (device int32; duplicates allowed).
+ *   Rule 1 runs before the bans: a banned column is -inf whatever rule 1 did to it. Ids outside [0, V), in the history or in the
+ *   list, touch no column (in the history they still take part in the n-gram comparison). Columns >= V (the pad of the row), rows
+ *   with active[r] == 0 and every column no rule names keep their bits.
+ * R == 0: no-op. VALOR_ERR_ARG, before any launch: null logits, null hist with t > 0, R < 0, V < 1, ld < V, t < 0 or > 512 (the
+ * history is held in LDS; the decoder has at most 512 positions), b < 1, a negative history stride, ngram < 0, min_len < 0, eos outside
+ * [0, V), penalty not finite or <= 0, n_suppress < 0, null suppress with n_suppress > 0. One 256-thread workgroup per row, 4 KiB of
+ * LDS, no atomics, no workspace: the result does not depend on how the threads split the history, graph replay equals eager issue. */
+int valor_logits_constrain(void* stream, float* logits, int64_t ld, int R, int V, const int64_t* hist, int64_t hist_stride_s,
+                           int64_t hist_stride_k, int b, int t, int64_t eos, float penalty, float inv_penalty, int ngram, int min_len,
+                           const int32_t* suppress, int n_suppress, const uint8_t* active);
 /* ---- the SCST caption reward on the device: CIDEr-D + BLEU-4 per hypothesis row (csrc/reward.hip; the rules are those of
  * valor_amd/scst.py: scorer/cider_scorer.py:119-200 with n = 1..4 and sigma 6, scorer/bleu_scorer.py:202-250 option 'closest').
  *   KEY of the n-gram (t_0 .. t_{n-1}): (t_i + 1) in bits [16 i, 16 i + 16) of a uint64, unused fields 0 -- exact, n = the number of

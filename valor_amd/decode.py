@@ -20,6 +20,10 @@ Beam rows are kept in the reference's (sample, beam) order on the host side; the
 so that a row's cross-attention K|V is row % b -- the kv_bmod addressing the training passes use -- instead of beam copies of K|V
 (pretrain.py:1133-1139 expands video_input / audio_input beam_size times).
 
+Generation controls (`Constraints`: repetition penalty, no repeated n-gram, minimum length, suppressed tokens) are one
+valor_logits_constrain launch per step on the step's logits, between the step and the selection, in every loop below; with the controls
+off no launch is issued. `constrain_rows_host` restates the kernel's law on the host.
+
 Everything here is inference: torch.no_grad, dropout off regardless of model.training (the reference calls it under model.eval())."""
 import contextlib
 import gc
@@ -351,15 +355,139 @@ def beam_select(logits, b, cur, beam, seq_logprob, seq_mask, beam_major, lse="ke
     return val, idx
 
 
-def decode_greedy(step, b, max_len):
+class Constraints:
+    """the controls of a generation, applied to every step's logits before the selection (valor_logits_constrain, one launch per step):
+    repetition_penalty (1: off; the logit of every token generated so far is divided by it when positive, multiplied when not),
+    no_repeat_ngram_size (0: off; no n-gram occurs twice in a sequence), min_length (no [SEP] before that many tokens),
+    suppress_tokens (ids that are never generated). length_penalty = alpha (0: off) belongs to beam search alone: the final pick among
+    the `beam` hypotheses ranks them by logP / length^alpha. The defaults are all off: the decoders of the reference."""
+    __slots__ = ("repetition_penalty", "no_repeat_ngram_size", "min_length", "suppress_tokens", "length_penalty")
+
+    def __init__(self, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=(), length_penalty=0.0):
+        repetition_penalty, length_penalty = float(repetition_penalty), float(length_penalty)
+        if not (repetition_penalty > 0.0 and repetition_penalty != float("inf")):
+            raise ValueError(f"Constraints: repetition_penalty {repetition_penalty!r} must be a finite number > 0 (1: off)")
+        if float(torch.tensor(repetition_penalty, dtype=torch.float32)) in (0.0, float("inf")):
+            raise ValueError(f"Constraints: repetition_penalty {repetition_penalty!r} is not a finite fp32 number > 0")
+        if int(no_repeat_ngram_size) != no_repeat_ngram_size or no_repeat_ngram_size < 0:
+            raise ValueError(f"Constraints: no_repeat_ngram_size {no_repeat_ngram_size!r} must be an integer >= 0 (0: off)")
+        if int(min_length) != min_length or min_length < 0:
+            raise ValueError(f"Constraints: min_length {min_length!r} must be an integer >= 0")
+        if suppress_tokens is None:
+            suppress_tokens = ()
+        if torch.is_tensor(suppress_tokens):
+            suppress_tokens = suppress_tokens.reshape(-1).tolist()
+        for w in suppress_tokens:
+            if int(w) != w or not (-2 ** 31 <= w < 2 ** 31):
+                raise ValueError(f"Constraints: suppress_tokens holds {w!r}: token ids are 32-bit integers")
+        if length_penalty != length_penalty or length_penalty in (float("inf"), -float("inf")):
+            raise ValueError(f"Constraints: length_penalty {length_penalty!r} must be a finite number (0: off)")
+        self.repetition_penalty, self.no_repeat_ngram_size, self.min_length = repetition_penalty, int(no_repeat_ngram_size), int(min_length)
+        self.suppress_tokens, self.length_penalty = tuple(int(w) for w in suppress_tokens), length_penalty
+
+    @property
+    def logits_off(self):
+        """no rule of valor_logits_constrain is on: no launch"""
+        return self.repetition_penalty == 1.0 and self.no_repeat_ngram_size == 0 and self.min_length == 0 and not self.suppress_tokens
+
+    @property
+    def off(self):
+        return self.logits_off and self.length_penalty == 0.0
+
+    @property
+    def penalty(self):
+        """repetition_penalty rounded to fp32: what the kernel multiplies by"""
+        return float(torch.tensor(self.repetition_penalty, dtype=torch.float32))
+
+    @property
+    def inv_penalty(self):
+        """1 / repetition_penalty rounded to fp32: the kernel's other factor"""
+        return float(torch.tensor(1.0 / self.repetition_penalty, dtype=torch.float32))
+
+    def __repr__(self):
+        return (f"Constraints(repetition_penalty={self.repetition_penalty}, no_repeat_ngram_size={self.no_repeat_ngram_size}, "
+                f"min_length={self.min_length}, suppress_tokens={self.suppress_tokens}, length_penalty={self.length_penalty})")
+
+
+def constrain_rows_host(logits, hist, t, constraints, eos, active=None):
+    """Rules 1-4 of valor_logits_constrain (include/valor_hip.h) restated on the host in fp32: logits [R, V] (any device; not modified),
+    hist int64 [R, >= t] in ROW order (row r's own tokens; None while t == 0), active [R] or None -> a new fp32 host tensor [R, V].
+    A single fp32 multiply per penalised column and -inf writes: bit-identical to the kernel."""
+    c = constraints
+    out = logits.detach().to(device="cpu", dtype=torch.float32).clone()
+    R, V = out.shape
+    pen, inv = torch.tensor(c.penalty, dtype=torch.float32), torch.tensor(c.inv_penalty, dtype=torch.float32)
+    n = c.no_repeat_ngram_size
+    ninf = -float("inf")
+    for r in range(R):
+        if active is not None and not bool(active[r]):
+            continue
+        h = [] if t == 0 else hist[r, :t].tolist()
+        z = out[r]
+        if c.penalty != 1.0:
+            seen = sorted({w for w in h if 0 <= w < V})
+            if seen:
+                idx = torch.tensor(seen, dtype=torch.long)
+                x = z[idx]
+                z[idx] = torch.where(x > 0, x * inv, x * pen)
+        if n >= 1 and t >= n - 1:
+            tail = h[t - n + 1:]
+            for i in range(t - n + 1):
+                if h[i:i + n - 1] == tail and 0 <= h[i + n - 1] < V:
+                    z[h[i + n - 1]] = ninf
+        if t < c.min_length:
+            z[eos] = ninf
+        for w in c.suppress_tokens:
+            if 0 <= w < V:
+                z[w] = ninf
+    return out
+
+
+class _Constrainer:
+    """the per-step launch of a decode loop under `constraints`: holds the device copy of the suppress list"""
+
+    def __init__(self, constraints, dev):
+        c = self.c = constraints
+        self.penalty, self.inv_penalty = c.penalty, c.inv_penalty
+        self.suppress = torch.tensor(c.suppress_tokens, dtype=torch.int32, device=dev) if c.suppress_tokens else None
+
+    def __call__(self, logits, hist, t, active, b=None, hist_stride_s=None, hist_stride_k=0):
+        c = self.c
+        return K.logits_constrain(logits, hist if t > 0 else None, t, EOS, self.penalty, self.inv_penalty, c.no_repeat_ngram_size, c.min_length,
+                                  self.suppress, active, b, hist_stride_s, hist_stride_k)
+
+
+def _constrainer(constraints, dev):
+    """None when no rule touches the logits: the loops then issue no launch and are the parent's, bit for bit"""
+    return None if constraints is None or constraints.logits_off else _Constrainer(constraints, dev)
+
+
+def _final_beam_order(seq_logprob, outputs, max_len, constraints):
+    """the final ranking of the `beam` hypotheses: seq_logprob [b, beam, 1], outputs int64 [b, beam, max_len] -> sort_idx [b, beam, 1].
+    length_penalty alpha == 0: the reference's sort of the summed logP. Otherwise logP / len^alpha in fp32, len = the tokens up to and
+    including the first [SEP] (max_len without one), descending, ties to the lower beam index."""
+    alpha = 0.0 if constraints is None else constraints.length_penalty
+    if alpha == 0.0:
+        return torch.sort(seq_logprob, 1, descending=True)[1]
+    ended = outputs == EOS
+    first = torch.where(ended.any(-1), ended.long().argmax(-1) + 1, max_len)                 # [b, beam]
+    score = seq_logprob[..., 0] / torch.pow(first.to(torch.float32), torch.tensor(alpha, dtype=torch.float32, device=first.device))
+    return torch.sort(score, dim=1, descending=True, stable=True)[1].unsqueeze(-1)
+
+
+def decode_greedy(step, b, max_len, constraints=None):
     """VALOR.decode_greedy, model/pretrain.py:988-1028, mode 'greedy' (its logprobs are zeros in that mode)."""
     dev = step.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
     logprobs = torch.zeros((b, max_len), device=dev)
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     state = None
+    con = _constrainer(constraints, dev)
     for t in range(max_len):
-        wt = step.logits(state, b).max(1)[1].view(-1).long()
+        logits = step.logits(state, b)
+        if con is not None:
+            logits = con(logits.contiguous(), sents, t, unfinished)
+        wt = logits.max(1)[1].view(-1).long()
         unfinished = unfinished & (wt != EOS)
         wt = torch.where(unfinished, wt, torch.full_like(wt, EOS))
         sents[:, t] = wt
@@ -370,17 +498,23 @@ def decode_greedy(step, b, max_len):
     return sents, logprobs
 
 
-def decode_beam(step, b, beam, max_len):
+def decode_beam(step, b, beam, max_len, constraints=None):
     """VALOR.decode_beam / select / _adjust_tensor, model/pretrain.py:1054-1180. A beam that produced [SEP] keeps its score for every
     candidate word (:1091-1094), so its V candidates tie and the reference's sort picks among them arbitrarily: sequences are only
-    defined up to that choice once a beam has ended (the tokens behind [SEP] are dropped by decode_sequence :146-164 anyway)."""
+    defined up to that choice once a beam has ended (the tokens behind [SEP] are dropped by decode_sequence :146-164 anyway).
+    constraints: the rows here are (sample, beam) ordered, and so is the history the launch reads; an ended beam's row is left alone."""
     dev = step.m.device
     seq_logprob = torch.zeros((b, 1, 1), device=dev)
     seq_mask = torch.ones((b, beam, 1), device=dev)
     outputs, selected_words, state = [], None, None
+    con = _constrainer(constraints, dev)
     for t in range(max_len):
         cur = 1 if t == 0 else beam
-        word_logprob = log_softmax_rows(step.logits(state, b * cur)).view(b, cur, -1)
+        logits = step.logits(state, b * cur)
+        if con is not None:
+            active = None if t == 0 else ((seq_mask[:, :, 0] != 0) & (selected_words.view(b, cur) != EOS)).reshape(-1)
+            logits = con(logits.contiguous(), None if t == 0 else torch.cat(outputs, -1).reshape(b * cur, t), t, active)
+        word_logprob = log_softmax_rows(logits).view(b, cur, -1)
         cand = seq_logprob + word_logprob
         if t > 0:
             mask = (selected_words.view(b, cur) != EOS).float().unsqueeze(-1)
@@ -400,21 +534,27 @@ def decode_beam(step, b, beam, max_len):
             state = torch.cat((state, w_host), dim=1)
         else:
             state = w_host
-    seq_logprob, sort_idx = torch.sort(seq_logprob, 1, descending=True)
-    outputs = torch.gather(torch.cat(outputs, -1), 1, sort_idx.expand(b, beam, max_len))
+    outputs = torch.cat(outputs, -1)
+    sort_idx = _final_beam_order(seq_logprob, outputs, max_len, constraints)
+    outputs = torch.gather(outputs, 1, sort_idx.expand(b, beam, max_len))
     return outputs.contiguous()[:, 0]
 
 
-def decode_greedy_cached(sess, b, max_len):
+def decode_greedy_cached(sess, b, max_len, constraints=None):
     """decode_greedy on a DecodeSession: the tokens stay on the device (the next step's input is this step's argmax); whether every row
-    has ended is asked every eighth step (a finished row keeps producing [SEP], pretrain.py:1005-1010: the result is the same)."""
+    has ended is asked every eighth step (a finished row keeps producing [SEP], pretrain.py:1005-1010: the result is the same).
+    constraints: one valor_logits_constrain launch on the step's logits, outside the captured step (history: sents, active: unfinished)."""
     dev = sess.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
     logprobs = torch.zeros((b, max_len), device=dev)
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     tok = None
+    con = _constrainer(constraints, dev)
     for t in range(max_len):
-        wt = sess.step(tok).max(1)[1]
+        logits = sess.step(tok)
+        if con is not None:
+            con(logits, sents, t, unfinished)
+        wt = logits.max(1)[1]
         unfinished = unfinished & (wt != EOS)
         tok = torch.where(unfinished, wt, EOS)
         sents[:, t] = tok
@@ -423,9 +563,11 @@ def decode_greedy_cached(sess, b, max_len):
     return sents, logprobs
 
 
-def decode_beam_cached(sess, b, beam, max_len):
+def decode_beam_cached(sess, b, beam, max_len, constraints=None):
     """decode_beam on a DecodeSession (rows beam-major): the selection arithmetic of pretrain.py:1054-1180 on the device, the chosen
-    beams as the next step's `parent` rows. Step 0 runs `beam` identical copies of every sequence and reads the first."""
+    beams as the next step's `parent` rows. Step 0 runs `beam` identical copies of every sequence and reads the first.
+    constraints: one valor_logits_constrain launch per step on the open beams' rows (the history follows the beams: `outputs`), and
+    length_penalty at the final pick; in-search ranking stays the reference's."""
     dev = sess.m.device
     seq_logprob = torch.zeros((b, 1, 1), device=dev)
     seq_mask = torch.ones((b, beam, 1), device=dev)
@@ -433,6 +575,8 @@ def decode_beam_cached(sess, b, beam, max_len):
     outputs = torch.zeros((b, beam, max_len), dtype=torch.int64, device=dev)
     selected_words, tok, parent = None, None, None
     fused = beam_select_enabled() and beam <= 8
+    con = _constrainer(constraints, dev)
+    open_rows = torch.empty((beam, b), dtype=torch.bool, device=dev) if con is not None else None
     for t in range(max_len):
         cur = 1 if t == 0 else beam
         logits = sess.step(tok, parent)
@@ -440,6 +584,10 @@ def decode_beam_cached(sess, b, beam, max_len):
         if t > 0:
             mask = (selected_words.view(b, cur) != EOS).float().unsqueeze(-1)
             seq_mask = seq_mask * mask
+        if con is not None:                                          # the words so far sit in `outputs` as (sample, beam); the rows are beam-major
+            if t > 0:
+                torch.ne(seq_mask.view(b, beam).t(), 0, out=open_rows)
+            con(logits[:b * cur], outputs, t, open_rows.view(-1) if t > 0 else None, b, beam * max_len, max_len)
         if fused:
             # (lse='kernel' -- the log-sum-exp inside the launch -- measured equal: 64 workgroups make three more passes over their rows)
             sel_logprob, sel_idx = beam_select(logits[:b * cur], b, cur, beam, seq_logprob, seq_mask, beam_major=True, lse="xent")
@@ -458,7 +606,7 @@ def decode_beam_cached(sess, b, beam, max_len):
         outputs[:, :, t] = selected_words
         parent = (sel_beam.t() * b + base[None]).reshape(-1)        # row (k, s) continues row (sel_beam[s, k], s)
         tok = selected_words.t().reshape(-1)
-    seq_logprob, sort_idx = torch.sort(seq_logprob, 1, descending=True)
+    sort_idx = _final_beam_order(seq_logprob, outputs, max_len, constraints)
     outputs = torch.gather(outputs, 1, sort_idx.expand(b, beam, max_len))
     return outputs.contiguous()[:, 0]
 
@@ -595,26 +743,30 @@ def _draw_step(logits, stream, sampling, unfinished, tok, sents_t, logprobs_t):
                                  sampling.top_p)
 
 
-def decode_sample_cached(sess, b, max_len, stream, sampling=None):
+def decode_sample_cached(sess, b, max_len, stream, sampling=None, constraints=None):
     """VALOR.decode_greedy mode 'sample' (pretrain.py:1005-1020) on a DecodeSession: one step, then one valor_sample_tokens launch that draws
     from softmax(logits), writes the logP of the draw and does the [SEP] bookkeeping. The tokens stay on the device; whether every row has
     ended is asked every eighth step, as in decode_greedy_cached. -> (sents int64 [b, max_len], logprobs fp32 [b, max_len]); after a row's
     first [SEP] its tokens are [SEP] and its logprobs 0. sampling: a Sampling (None or all off: the unmodified softmax); the sampler
-    launch sits outside the captured step and takes its parameters by value, so a kept session serves any setting."""
+    launch sits outside the captured step and takes its parameters by value, so a kept session serves any setting. constraints come
+    first (valor_logits_constrain on the step's logits): temperature / top-k / top-p and the logP see what the constraints left."""
     dev = sess.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
     logprobs = torch.zeros((b, max_len), device=dev)
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     tok = torch.empty(b, dtype=torch.long, device=dev)
+    con = _constrainer(constraints, dev)
     for t in range(max_len):
         logits = sess.step(None if t == 0 else tok)
+        if con is not None:
+            con(logits, sents, t, unfinished)
         _draw_step(logits, stream, sampling, unfinished, tok, sents[:, t], logprobs[:, t])
         if t % 8 == 7 and t + 1 < max_len and not bool(unfinished.any()):
             break
     return sents, logprobs
 
 
-def decode_sample(step, b, max_len, stream, sampling=None):
+def decode_sample(step, b, max_len, stream, sampling=None, constraints=None):
     """decode_sample_cached on the re-run path (_Stepper: VALOR_KV_CACHE=0, a cross-attention block per modality); the same draws"""
     dev = step.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
@@ -622,8 +774,11 @@ def decode_sample(step, b, max_len, stream, sampling=None):
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     tok = torch.empty(b, dtype=torch.long, device=dev)
     state = None
+    con = _constrainer(constraints, dev)
     for t in range(max_len):
         logits = step.logits(state, b).contiguous()
+        if con is not None:
+            con(logits, sents, t, unfinished)
         _draw_step(logits, stream, sampling, unfinished, tok, sents[:, t], logprobs[:, t])
         w_host = tok.cpu().unsqueeze(1)
         state = w_host if state is None else torch.cat((state, w_host), dim=1)
@@ -632,9 +787,11 @@ def decode_sample(step, b, max_len, stream, sampling=None):
     return sents, logprobs
 
 
-def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None, sampling=None):
+def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None, sampling=None, constraints=None):
     """{group: (sequences, logprobs | None)} for the query groups present, through the K|V-cached session or the re-run path.
-    stream: a SampleStream (after begin_call) -> sampled decoding (beam 1) under `sampling` (a Sampling or None)"""
+    stream: a SampleStream (after begin_call) -> sampled decoding (beam 1) under `sampling` (a Sampling or None). constraints: a
+    Constraints or None, for every mode"""
+    c = constraints
     if isinstance(prompt, str):
         prompt = model.get_task_prompt(PROMPTS[prompt], b) if model.use_task_prompt else None
     if stream is not None:
@@ -650,15 +807,15 @@ def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, s
         if sess is not None:
             sess.begin_group(ranges[g] if kv_layers is not None else None, prompt)
             if stream is not None:
-                out[g] = decode_sample_cached(sess, b, max_len, stream, sampling)
+                out[g] = decode_sample_cached(sess, b, max_len, stream, sampling, c)
             else:
-                out[g] = (decode_beam_cached(sess, b, beam, max_len), None) if beam > 1 else decode_greedy_cached(sess, b, max_len)
+                out[g] = (decode_beam_cached(sess, b, beam, max_len, c), None) if beam > 1 else decode_greedy_cached(sess, b, max_len, c)
         else:
             step = _Stepper(model, g, kv_layers, ranges, prompt, b)
             if stream is not None:
-                out[g] = decode_sample(step, b, max_len, stream, sampling)
+                out[g] = decode_sample(step, b, max_len, stream, sampling, c)
             else:
-                out[g] = (decode_beam(step, b, beam, max_len), None) if beam > 1 else decode_greedy(step, b, max_len)
+                out[g] = (decode_beam(step, b, beam, max_len, c), None) if beam > 1 else decode_greedy(step, b, max_len, c)
     return out
 
 
@@ -695,9 +852,26 @@ def _repeat_clips(model, kv_layers, b, n):
     return _BlockKV(rows_of(kv_layers.v), rows_of(kv_layers.a)) if isinstance(kv_layers, _BlockKV) else rows_of(kv_layers)
 
 
+def _constraints_of(model, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty):
+    """the Constraints of a generate_* call: an argument that is None takes the model's option generation_<name> (absent: off)"""
+    from .model.valor import _opt
+    pick = lambda v, name, default: _opt(model.opts, "generation_" + name, default) if v is None else v
+    return Constraints(pick(repetition_penalty, "repetition_penalty", 1.0), pick(no_repeat_ngram_size, "no_repeat_ngram_size", 0),
+                       pick(min_length, "min_length", 0), pick(suppress_tokens, "suppress_tokens", ()),
+                       pick(length_penalty, "length_penalty", 0.0))
+
+
+def _sampling_of(model, temperature, top_k, top_p):
+    from .model.valor import _opt
+    return Sampling(_opt(model.opts, "sample_temperature", 1.0) if temperature is None else temperature,
+                    _opt(model.opts, "sample_top_k", 0) if top_k is None else top_k,
+                    _opt(model.opts, "sample_top_p", 1.0) if top_p is None else top_p)
+
+
 @torch.no_grad()
 def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None, top_k=None,
-                 top_p=None, num_return_sequences=1):
+                 top_p=None, num_return_sequences=1, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None,
+                 suppress_tokens=None, length_penalty=None):
     """VALOR.generate_cap, model/pretrain.py:914-985 -> {'generated_sequences_t_v' | '_t_va' | '_t_a' (+ 'logprobs_*' when greedy or
     sampled)}. mode: None (beam search when beam_size > 1, else greedy), 'greedy' (whatever beam_size says) or 'sample' (decode_greedy's
     sample mode, :1007-1011: a draw from softmax(logits) per step, logprobs_* = the logP of the draws). seed: the sampled draws' seed
@@ -705,7 +879,10 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
     mode 'sample' only: temperature / top_k / top_p filter the distribution of every step (Sampling; None: the model's options
     sample_temperature / sample_top_k / sample_top_p, absent = off; logprobs_* are then the logP under the filtered distribution), and
     num_return_sequences = n draws n captions per clip: the encoders and the K|V projections run once per clip, the decoder runs b * n
-    rows, and every output is [b * n, L] clip-major (rows i * n .. i * n + n - 1 belong to clip i)."""
+    rows, and every output is [b * n, L] clip-major (rows i * n .. i * n + n - 1 belong to clip i).
+    Every mode: repetition_penalty / no_repeat_ngram_size / min_length / suppress_tokens (Constraints; None: the model's options
+    generation_<name>, absent = off) rewrite each step's logits on the device before the selection -- before temperature / top-k / top-p
+    too, and the log-probabilities are those of what is left; length_penalty ranks the final hypotheses of a beam search."""
     if mode not in (None, "greedy", "sample"):
         raise ValueError(f"generate_cap: mode {mode!r} (None, 'greedy' or 'sample')")
     n = int(num_return_sequences)
@@ -713,12 +890,10 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
         raise ValueError(f"generate_cap: num_return_sequences {num_return_sequences!r} must be an integer >= 1")
     sampling = None
     if mode == "sample":
-        from .model.valor import _opt
-        sampling = Sampling(_opt(model.opts, "sample_temperature", 1.0) if temperature is None else temperature,
-                            _opt(model.opts, "sample_top_k", 0) if top_k is None else top_k,
-                            _opt(model.opts, "sample_top_p", 1.0) if top_p is None else top_p)
+        sampling = _sampling_of(model, temperature, top_k, top_p)
     elif temperature is not None or top_k is not None or top_p is not None or n != 1:
         raise ValueError("generate_cap: temperature / top_k / top_p / num_return_sequences need mode='sample'")
+    constraints = _constraints_of(model, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty)
     beam = model.beam_size if beam_size is None else beam_size
     if mode is not None:
         beam = 1
@@ -732,7 +907,8 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
             b *= n
         out = {}
         stream = _sample_stream(model, seed) if mode == "sample" else None
-        for g, (seq, lp) in _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, stream, sampling).items():
+        for g, (seq, lp) in _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, stream, sampling,
+                                                constraints).items():
             key = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]
             out["generated_sequences_" + key] = seq
             if lp is not None:
@@ -743,15 +919,30 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
 
 
 @torch.no_grad()
-def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation_len=None):
+def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None,
+                top_k=None, top_p=None, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None, suppress_tokens=None,
+                length_penalty=None):
     """VALOR.generate_qa, model/pretrain.py:1366-1459: the caption decoders with the question rows as the prompt ->
-    {'generated_answers_t_v' | '_t_va' | '_t_a'}. sample_num[i] consecutive question rows belong to clip i (:1378-1390): the reference
+    {'generated_answers_t_v' | '_t_va' | '_t_a'}. mode, seed, temperature / top_k / top_p and the Constraints arguments are
+    generate_cap's: None (beam search when beam_size_qa > 1, else greedy), 'greedy', or 'sample' -- one sampled answer per question, with
+    'logprobs_*' (the logP of the draws) beside the answers; the question tokens are no part of the history the constraints read.
+    sample_num[i] consecutive question rows belong to clip i (:1378-1390): the reference
     expands the [video | audio] token rows per question; here the per-layer K|V projections are computed once per CLIP and their rows
     gathered per question (valor_gather_rows), so the projection GEMMs do not grow with the question count."""
+    if mode not in (None, "greedy", "sample"):
+        raise ValueError(f"generate_qa: mode {mode!r} (None, 'greedy' or 'sample')")
+    sampling = None
+    if mode == "sample":
+        sampling = _sampling_of(model, temperature, top_k, top_p)
+    elif temperature is not None or top_k is not None or top_p is not None:
+        raise ValueError("generate_qa: temperature / top_k / top_p need mode='sample'")
+    constraints = _constraints_of(model, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty)
     sample_num = [int(n) for n in batch.get("sample_num", [])]
     # the reference switches to beam search when beam_size_qa > 1 but decode_beam always searches with self.beam_size, task 'qa'
     # included (pretrain.py:1061): beam_size_qa is the switch, beam_size the width
     beam = (model.beam_size if model.beam_size_qa > 1 else 1) if beam_size is None else beam_size
+    if mode is not None:
+        beam = 1
     max_len = model.max_generation_len if max_generation_len is None else max_generation_len
     was_training = model.training
     model.eval()
@@ -765,7 +956,12 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
             rows_of = lambda kvs: None if kvs is None else [ops.gather_rows(kv.reshape(b, -1), idx).view(idx.numel(), *kv.shape[1:]) for kv in kvs]
             kv_layers = _BlockKV(rows_of(kv_layers.v), rows_of(kv_layers.a)) if isinstance(kv_layers, _BlockKV) else rows_of(kv_layers)
             b = int(idx.numel())
-        res = _decode_groups(model, groups, b, kv_layers, ranges, prompt_cpu, beam, max_len)
-        return {"generated_answers_" + {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]: seq for g, (seq, _lp) in res.items()}
+        stream = _sample_stream(model, seed) if mode == "sample" else None
+        res = _decode_groups(model, groups, b, kv_layers, ranges, prompt_cpu, beam, max_len, stream, sampling, constraints)
+        keys = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}
+        out = {"generated_answers_" + keys[g]: seq for g, (seq, _lp) in res.items()}
+        if mode == "sample":
+            out.update({"logprobs_" + keys[g]: lp for g, (_seq, lp) in res.items()})
+        return out
     finally:
         model.train(was_training)

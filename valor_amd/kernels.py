@@ -613,6 +613,36 @@ def sample_tokens_filtered(logits, seed, offset, eos, unfinished, tok, sents, lo
              logprobs.stride(0), None if kept is None else _ptr(kept), None if cut is None else _ptr(cut))
 
 
+def logits_constrain(logits, hist, t, eos, penalty=1.0, inv_penalty=1.0, ngram=0, min_len=0, suppress=None, active=None, b=None,
+                     hist_stride_s=None, hist_stride_k=0):
+    """generation controls of one decoding step, in place (valor_logits_constrain; the law: include/valor_hip.h): logits fp32 [R, V]
+    (row pitch = stride(0)); hist int64, unit stride along the tokens (None while t == 0); suppress int32 [n] or None; active bool /
+    uint8 [R] or None. Row r reads its t tokens at hist.data_ptr + (r % b) * hist_stride_s + (r / b) * hist_stride_k (elements). The
+    default is a row-ordered history [R, >= t]: b = R, hist_stride_s = hist.stride(0). Returns logits."""
+    _check_gpu(logits, hist, suppress, active)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    R, V = logits.shape
+    t = int(t)
+    if hist is not None:
+        assert hist.dtype == torch.int64 and hist.stride(-1) == 1 and hist.shape[-1] >= t
+        if hist_stride_s is None:
+            assert hist.dim() == 2 and hist.shape[0] >= R
+            hist_stride_s = hist.stride(0)
+    else:
+        assert t == 0
+    b = R if b is None else int(b)
+    if hist is not None and t > 0 and R > 0:            # the furthest token a row reads lies inside the tensor's storage
+        last = ((min(R, b) - 1) * int(hist_stride_s) + ((R - 1) // b) * int(hist_stride_k) + t - 1) if b >= 1 else 0
+        assert hist.storage_offset() + last < hist.untyped_storage().nbytes() // 8
+    assert suppress is None or (suppress.dtype == torch.int32 and suppress.dim() == 1 and suppress.is_contiguous())
+    assert active is None or (active.dtype in (torch.bool, torch.uint8) and active.is_contiguous() and active.numel() == R)
+    lib.call("valor_logits_constrain", _stream(), _ptr(logits), logits.stride(0), R, V, None if hist is None else _ptr(hist),
+             int(hist_stride_s or 0), int(hist_stride_k), b, t, int(eos), float(penalty), float(inv_penalty),
+             int(ngram), int(min_len), None if suppress is None else _ptr(suppress), 0 if suppress is None else suppress.numel(),
+             None if active is None else _ptr(active))
+    return logits
+
+
 def fbank(wave, offsets, slice_idx, tables, melbins, T, mean, std, out=None):
     """log-mel filterbank of the selected slices in the model's layout (valor_fbank): wave = the clips packed back to back, fp32 or int16
     PCM [n]; offsets int64 [B + 1]; slice_idx int32 [B, A] (-1: no audio); tables = preprocess.fbank_tables(...).to_device() (window,
