@@ -36,8 +36,41 @@ def set_host_rng_state(st):
     torch.set_rng_state(st["torch"].cpu().to(torch.uint8))
 
 
+def micro_batch_size(batch):
+    """rows of one micro-batch: of its token tensors, else of its pixels / spectrograms"""
+    toks = batch.get("txt_tokens") or {}
+    for t in list(toks.values()) + [batch.get("video_pixels"), batch.get("audio_spectrograms")]:
+        if t is not None:
+            return int(t.shape[0])
+    raise ValueError("micro-batch without txt_tokens, video_pixels or audio_spectrograms")
+
+
+def window_bank(passes):
+    """The window bank of TrainEngine.train_window: the feature passes' feat_t / feat_v / feat_a (each a list entry with .feat_t, .feat_v,
+    .feat_a, .tokens; a modality the task does not use is None in every entry) concatenated along the rows in micro-batch order --
+    micro-batch m owns rows [m b, (m + 1) b), as rank m does in the reference's all-gather -- and made leaves that take a gradient; the
+    contrastive text tokens likewise (no gradient)."""
+    bank = {}
+    for key in ("feat_t", "feat_v", "feat_a"):
+        parts = [getattr(p, key) for p in passes]
+        if any(f is None for f in parts):
+            if not all(f is None for f in parts):
+                raise ValueError(f"window bank: {key} is missing from some micro-batches only")
+            bank[key] = None
+            continue
+        bank[key] = torch.cat([f.detach() for f in parts], dim=0).requires_grad_(True)
+    toks = [p.tokens for p in passes]
+    bank["tokens"] = None if any(t is None for t in toks) else torch.cat(toks, dim=0)
+    return bank
+
+
+def bank_slice(t, m, b):
+    """rows of micro-batch m (b rows each) of a bank tensor"""
+    return t[m * b:(m + 1) * b]
+
+
 class TrainEngine:
-    def __init__(self, model, opts, optimizer=None, manage_gc=True, graphs=None):
+    def __init__(self, model, opts, optimizer=None, manage_gc=True, graphs=None, contra_window=None):
         # the reference clips unless grad_norm == -1 (train_utils.py:358): 0 would clip every gradient to zero, a negative value flip
         # its sign -- the fused clip treats any max_norm <= 0 as "off", so such values are refused here instead of silently meaning -1
         grad_norm = float(getattr(opts, "grad_norm", 5.0))
@@ -94,6 +127,11 @@ class TrainEngine:
         self._headroom_done = False
         self.grad_norm = grad_norm
         self._task = None
+        # contra_window (argument, else opts.contra_window): train_step on a LIST of micro-batches is one window step (train_window) --
+        # the contrastive loss over all the window's rows -- instead of an error
+        self.contra_window = bool(getattr(opts, "contra_window", False) if contra_window is None else contra_window)
+        self.keep_window = False         # debugging / tests: train_window leaves its bank and the training passes' features in last_window
+        self.last_window = None
         self._micro = 0
         self._window_open = False        # the last train_step returned without an optimizer step: partial gradient sums are in the arena
         self._saver = None               # valor_amd.checkpoint's non-blocking writer, once save_run(blocking=False) was used
@@ -108,7 +146,14 @@ class TrainEngine:
         """One iteration of conduct_train's loop body (train_utils.py:302-364). accum_steps = n > 1 is dataset_mix_type='accum'
         (:311-317,341: loss / n, one optimizer step every n iterations, gradients of the n micro-steps -- possibly of different
         tasks -- summed): the arena simply keeps accumulating, the data-parallel reduction runs once per window."""
-        model, opt = self.model, self.optimizer
+        if isinstance(batch, (list, tuple)):
+            if not self.contra_window:
+                raise TypeError("train_step got a list of micro-batches: pass contra_window=True (engine argument or option) to run it as "
+                                "one window step, or call train_window")
+            if accum_steps != 1:
+                raise ValueError("train_step: a list of micro-batches is one window step; accum_steps does not apply")
+            return self.train_window(batch, task)
+        model = self.model
         if not model.arena.grads_bound():
             raise RuntimeError("parameter .grad tensors were detached from the gradient arena (p.grad = None / zero_grad(set_to_none=True) "
                                "on the raw parameters?): call model.zero_grad() (it re-binds) before the next step")
@@ -116,21 +161,7 @@ class TrainEngine:
         if task != self._task:
             self.reducer.reset_task(task)
             self._task = task
-        tracing = self.trace is not None and model.arena.flat.is_cuda
-        if tracing:
-            import time as _time
-            t_in = _time.perf_counter()
-        wait_s = 0.0
-        if self.max_ahead > 0 and len(self._step_events) >= self.max_ahead:
-            if tracing:
-                t_w = _time.perf_counter()
-                self._step_events.pop(0).synchronize()
-                wait_s = _time.perf_counter() - t_w
-            else:
-                self._step_events.pop(0).synchronize()
-        if tracing:
-            head = torch.cuda.Event(enable_timing=True)
-            head.record()
+        tracing, t_in, wait_s, head = self._enter_step()
         model.train()
         DropoutState.check_restored()      # a restored device-mode state that never met its counter (graphs were on when it was saved)
         DropoutState.begin_step()          # device mode (model.enable_graphs): by-value offsets restart, the device counter advances
@@ -157,28 +188,170 @@ class TrainEngine:
         if tracing and self.world > 1:
             r1.record()
         self._window_open = not last
+        loss_dict["total_loss"] = loss.detach()
         if not last:
-            loss_dict["total_loss"] = loss.detach()
             return loss_dict
+        self._optimizer_step(active, (tracing, t_in, wait_s, head), (r0, r1) if tracing and self.world > 1 else None)
+        return loss_dict
+
+    def train_window(self, batches, task):
+        """ONE optimizer step on a window of M equally sized micro-batches whose contrastive loss is computed over all N = M * b rows:
+        what the reference computes at world size M with micro-batch m as rank m (utils/distributed.py:38-93, pretrain.py:278-291 --
+        every rank evaluates the loss on the gathered features and back-propagates its own slice, DDP averages the gradients), where
+        train_step(accum_steps=M) sums M steps that each see b - 1 negatives.
+
+        1. feature pass: every micro-batch through the encoders and contrastive heads of the task, no autograd, training mode, no token
+           masker; the features and contrastive tokens go into a bank of N rows. The pass draws the dropout windows (VideoSwin: the
+           stochastic-depth factors) the training pass of the same micro-batch draws again in 3.
+        2. the contrastive block (VALOR.contrastive_loss) ONCE on the bank, the bank's features as leaves: its backward leaves
+           G = d contra_loss / d bank and the full gradients of the parameters applied to gathered features (fine-weight heads,
+           temperature, va_fusion), which every reference rank computes identically -- DDP's mean leaves them as they are.
+        3. training pass: every micro-batch through the ordinary forward without a contrastive loss of its own; one backward from
+           (caption + mlm losses) / M and G[m b:(m + 1) b] / M at the micro-batch's features. The arena accumulates.
+        4. LR schedule, clip, fused AdamW: the tail of train_step.
+
+        Returns the window's contra_loss, the mean over the micro-batches of the other losses, and total_loss. M = 1 is train_step on
+        that batch. A task without contrastive groups ('cap%', 'qa%', SCST, a 'pt_' task without 'contra') has no window-wide term:
+        ValueError -- use train_step(accum_steps=M). The step is atomic: no accumulation window is open before or after it."""
+        from .model.valor import WindowPass
+        model = self.model
+        batches = list(batches)
+        if not batches:
+            raise ValueError("train_window: no micro-batches")
+        if self.world > 1:
+            raise NotImplementedError("train_window with world > 1: bank rows from other ranks are not gathered; use train_step, whose "
+                                      "contrastive loss already runs on the ranks' gathered features")
+        if self._window_open:
+            raise RuntimeError("train_window: an accumulation window is open (the last train_step did not reach its optimizer step); "
+                               "close it with its remaining micro-steps first")
+        contra_task, contra_ratio = model.task_groups(task)[2:]
+        if not contra_task:
+            raise ValueError(f"train_window: task {task!r} has no contrastive groups, so nothing spans the window; "
+                             "use train_step(batch, task, accum_steps=M)")
+        sizes = [micro_batch_size(b) for b in batches]
+        if len(set(sizes)) != 1:
+            raise ValueError(f"train_window: micro-batches of unequal size {sizes} (the reference's ranks are equal too)")
+        if not model.arena.grads_bound():
+            raise RuntimeError("parameter .grad tensors were detached from the gradient arena (p.grad = None / zero_grad(set_to_none=True) "
+                               "on the raw parameters?): call model.zero_grad() (it re-binds) before the next step")
+        M, b = len(batches), sizes[0]
+        if task != self._task:
+            self.reducer.reset_task(task)
+            self._task = task
+        entered = self._enter_step()
+        model.train()
+        DropoutState.check_restored()
+        try:
+            # ---- 1. feature pass
+            np_state = np.random.get_state()               # VideoSwin stochastic depth: the training passes draw the same factors again
+            passes, windows = self.feature_pass(batches, task)
+            bank = window_bank(passes)
+            # ---- 2. one contrastive evaluation on the bank (every backward of the window only accumulates: one reduction-free window)
+            self.reducer.prepare_backward(defer=True)
+            contra_loss = model.contrastive_loss(bank["feat_t"], bank["feat_v"], bank["feat_a"], bank["tokens"], contra_task, contra_ratio)
+            contra_loss.backward()
+            self.reducer.finish_backward(last=False)
+            # ---- 3. training passes
+            np.random.set_state(np_state)
+            sums, kept = {}, []
+            for m, batch in enumerate(batches):
+                tail = DropoutState.offset                  # host-mode dropout: behind every window handed out so far
+                DropoutState.rewind(windows[m])
+                wp = WindowPass(features_only=False, draws_end=passes[m].draws_end, resume=tail if DropoutState.base is None else None)
+                self.reducer.prepare_backward(defer=True)
+                out = model(batch, task=task, compute_loss=True, window=wp)
+                roots, grads = [], []
+                if out:
+                    local = sum(out.values())
+                    roots.append(local / M if M > 1 else local)
+                    grads.append(None)
+                for key, f in (("feat_t", wp.feat_t), ("feat_v", wp.feat_v), ("feat_a", wp.feat_a)):
+                    if f is not None:
+                        g = bank_slice(bank[key].grad, m, b)
+                        roots.append(f)
+                        grads.append(g / M if M > 1 else g)
+                torch.autograd.backward(roots, grads)
+                active = self.reducer.finish_backward(last=m == M - 1)
+                for k, v in out.items():
+                    sums[k] = v.detach() if k not in sums else sums[k] + v.detach()
+                if self.keep_window:
+                    kept.append({k: f.detach().clone() for k, f in (("feat_t", wp.feat_t), ("feat_v", wp.feat_v), ("feat_a", wp.feat_a))
+                                 if f is not None})
+        except BaseException:
+            # nothing of a failed window may reach a later step: its partial gradient sums and the reducer's record of them go
+            model.arena.grad.zero_()
+            self.reducer.window = None
+            raise
+        self.last_window = {"bank": bank, "train_feats": kept} if self.keep_window else None
+        loss_dict = {"contra_loss": contra_loss.detach()}
+        loss_dict.update({k: (v / M if M > 1 else v) for k, v in sums.items()})
+        loss_dict["total_loss"] = sum(loss_dict.values())
+        self._optimizer_step(active, entered)
+        return loss_dict
+
+    def feature_pass(self, batches, task):
+        """Step 1 of train_window on its own: every micro-batch through the encoders and contrastive heads of `task` without autograd, in
+        training mode, with the kernels of the training path (ops.replayed_pass) and without the token masker -> (one WindowPass per
+        micro-batch holding feat_t / feat_v / feat_a / tokens, the dropout window each pass drew from). Each pass opens a dropout step
+        of its own (DropoutState.begin_step), exactly as the training pass of a micro-step would."""
+        from .model.valor import WindowPass
+        from .ops import replayed_pass
+        model = self.model
+        model.train()
+        passes, windows = [], []
+        with torch.no_grad(), replayed_pass():
+            for batch in batches:
+                DropoutState.begin_step()
+                windows.append(DropoutState.window())
+                wp = WindowPass(features_only=True)
+                model(batch, task=task, compute_loss=True, window=wp)
+                passes.append(wp)
+        return passes, windows
+
+    def _enter_step(self):
+        """top of a call that may end in an optimizer step: the `max_ahead` throttle and, when someone asked for a trace, the timing
+        event in front of the call's first launch -> (tracing, host time at entry, seconds blocked in the throttle, head event)"""
+        tracing = self.trace is not None and self.model.arena.flat.is_cuda
+        t_in = head = None
+        if tracing:
+            import time as _time
+            t_in = _time.perf_counter()
+        wait_s = 0.0
+        if self.max_ahead > 0 and len(self._step_events) >= self.max_ahead:
+            if tracing:
+                t_w = _time.perf_counter()
+                self._step_events.pop(0).synchronize()
+                wait_s = _time.perf_counter() - t_w
+            else:
+                self._step_events.pop(0).synchronize()
+        if tracing:
+            head = torch.cuda.Event(enable_timing=True)
+            head.record()
+        return tracing, t_in, wait_s, head
+
+    def _optimizer_step(self, active, entered, reduce_events=None):
+        """the tail of an optimizer step (train_utils.py:344-362): warmup-linear LR, global-norm clip + fused AdamW on the parameters that
+        received a gradient, the step's end event for the throttle / the trace, allocator head-room, the generation-0 collection"""
+        tracing, t_in, wait_s, head = entered
+        model, opt = self.model, self.optimizer
         self.global_step += 1
         if getattr(self.opts, "num_train_steps", 0):
             ratio = get_lr_sched(self.global_step, self.opts)                      # train_utils.py:344-347
             for g in opt.param_groups:
                 g["lr"] = g["init_lr"] * ratio
         opt.step(active_names=active, max_grad_norm=self.grad_norm, world_size=self.world)   # clip :358-360, step :362
-        loss_dict["total_loss"] = loss.detach()
         if self.max_ahead > 0 and model.arena.flat.is_cuda:
             ev = torch.cuda.Event(enable_timing=tracing)
             ev.record()
             self._step_events.append(ev)
             if tracing:
+                import time as _time
                 self.trace.append({"wait_ms": wait_s * 1e3, "host_ms": (_time.perf_counter() - t_in) * 1e3, "head": head, "tail": ev,
-                                   "reduce": (r0, r1) if self.world > 1 else None})
+                                   "reduce": reduce_events})
         if not self._headroom_done and self.global_step >= 2:
             self.reserve_headroom()
         if self.manage_gc:
             gc.collect(0 if self.global_step % 64 else 2)
-        return loss_dict
 
     def _assert_same_window(self):
         import zlib

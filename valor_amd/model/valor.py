@@ -210,6 +210,32 @@ class _BlockKV:
         return self.v if m == "v" else self.a
 
 
+class WindowPass:
+    """One pass of a window step (TrainEngine.train_window) over one micro-batch, handed to VALOR.forward as `window=`.
+    features_only: the feature pass -- the forward stops behind the contrastive features, which at_features() keeps here (feat_t /
+    feat_v / feat_a / tokens); no token masker runs. Otherwise the training pass: the contrastive block is skipped, the features stay
+    in the autograd graph and are kept here for the caller to back-propagate the bank's gradient slice into.
+    draws_end: the by-value dropout offset the feature pass of this micro-batch stopped at -- the training pass must stand at the same
+    offset when it reaches the features (same encoders, same order, same windows) or the replay is broken (RuntimeError).
+    resume: the offset the training pass continues from behind the features (host-mode dropout: past every window the step has
+    handed out, the later micro-batches' feature passes included); None: carry on where it stands."""
+
+    def __init__(self, features_only, draws_end=None, resume=None):
+        self.features_only, self.draws_end, self.resume = features_only, draws_end, resume
+        self.feat_t = self.feat_v = self.feat_a = self.tokens = None
+
+    def at_features(self, feat_t, feat_v, feat_a, tokens):
+        self.feat_t, self.feat_v, self.feat_a, self.tokens = feat_t, feat_v, feat_a, tokens
+        if self.features_only:
+            self.draws_end = ops.DropoutState.offset
+            return
+        if self.draws_end is not None and ops.DropoutState.offset != self.draws_end:
+            raise RuntimeError(f"window step: the training pass drew dropout windows up to offset {ops.DropoutState.offset} in front of the "
+                               f"contrastive features, the feature pass of the same micro-batch up to {self.draws_end}: the passes differ")
+        if self.resume is not None:
+            ops.DropoutState.offset = self.resume
+
+
 class VALOR(nn.Module):
     def __init__(self, opts=None, spec: ValorSpec = None, dtype=torch.bfloat16, device="cuda", vocab_tokens=None):
         super().__init__()
@@ -1277,24 +1303,26 @@ class VALOR(nn.Module):
         return out
 
     # ------------------------------------------------------------------ the hot path
-    def forward(self, batch, task, compute_loss=True):
-        """VALOR.forward, model/pretrain.py:125-135"""
+    def forward(self, batch, task, compute_loss=True, window=None):
+        """VALOR.forward, model/pretrain.py:125-135. window: a WindowPass (TrainEngine.train_window; 'pt_*' / 'ret%*' tasks only)"""
         if task.startswith("pt"):
-            return self.forward_pt(batch, task, compute_loss=compute_loss)
+            return self.forward_pt(batch, task, compute_loss=compute_loss, window=window)
         if task.startswith("ret"):
-            return self.forward_ret(batch, task, compute_loss=compute_loss)
+            return self.forward_ret(batch, task, compute_loss=compute_loss, window=window)
+        if window is not None:
+            raise ValueError(f"task {task!r} has no contrastive groups: a window pass is for 'pt_*' / 'ret%*' tasks")
         if task.startswith("cap"):
             return self.forward_cap(batch, task, compute_loss=compute_loss)
         if task.startswith("qa"):
             return self.forward_qa(batch, task, compute_loss=compute_loss)
         raise NotImplementedError(f"task {task!r}: 'pt_*', 'ret%*', 'cap%*' and 'qa%*' are the reference's task families (pretrain.py:125-135)")
 
-    def forward_ret(self, batch, task, compute_loss=True):
+    def forward_ret(self, batch, task, compute_loss=True, window=None):
         """VALOR.forward_ret, model/pretrain.py:544-711 (config/fast-retrieval-*.json: 'ret%tva%tv'): the contrastive branch of forward_pt
         (:252-407 -- the same encoders, pooling, heads, gathers, fine matrices and InfoNCE, line for line) on the groups after 'ret%';
         the mean of the group losses is NOT scaled by contra_loss_ratio (:706 vs :406). compute_loss=False returns
         feat_t / feat_v / feat_a / txt_tokens (:708-715), what evaluate.compute_fine_matrix consumes."""
-        return self._forward_groups(batch, [], [], task.split("%")[1:], compute_loss, contra_ratio=1.0)
+        return self._forward_groups(batch, [], [], task.split("%")[1:], compute_loss, contra_ratio=1.0, window=window)
 
     def forward_cap(self, batch, task, compute_loss=True):
         """VALOR.forward_cap, model/pretrain.py:713-725 (config/caption-*.json: 'cap%tva%tv'; caption_type 'unimlm', no label smoothing /
@@ -1540,17 +1568,10 @@ class VALOR(nn.Module):
                 self._dec_nodrop = saved
         return ctx()
 
-    def forward_pt(self, batch, task, compute_loss=True):
+    def forward_pt(self, batch, task, compute_loss=True, window=None):
         """VALOR.forward_pt, model/pretrain.py:214-541."""
-        mlm_task, caption_task, contra_task = [], [], []
-        for i in task.split("_"):
-            if "mlm" in i:
-                mlm_task = i.split("%")[1:]
-            elif "caption" in i:
-                caption_task = i.split("%")[1:]
-            elif "contra" in i:
-                contra_task = i.split("%")[1:]
-        return self._forward_groups(batch, mlm_task, caption_task, contra_task, compute_loss, contra_ratio=self.contra_loss_ratio)
+        mlm_task, caption_task, contra_task, ratio = self.task_groups(task)
+        return self._forward_groups(batch, mlm_task, caption_task, contra_task, compute_loss, contra_ratio=ratio, window=window)
 
     def mask_text(self, txt, mask_prob):
         """the MLM / caption masker of the configured mode (token_masker): TokenMasker -> host (tokens, labels), DeviceTokenMasker ->
@@ -1577,8 +1598,88 @@ class VALOR(nn.Module):
         labels[labels == 0] = -1
         return txt, labels
 
-    def _forward_groups(self, batch, mlm_task, caption_task, contra_task, compute_loss, contra_ratio=1.0):
-        """The body of VALOR.forward_pt (model/pretrain.py:226-541) on parsed group lists; forward_ret / forward_cap run it with one branch."""
+    def task_groups(self, task):
+        """(mlm groups, caption groups, contrastive groups, contra ratio) of a 'pt_*' / 'ret%*' task string, as forward_pt / forward_ret
+        parse it; a task of another family has no contrastive groups: ([], [], [], 1.0)"""
+        if task.startswith("pt"):
+            mlm_task, caption_task, contra_task = [], [], []
+            for i in task.split("_"):
+                if "mlm" in i:
+                    mlm_task = i.split("%")[1:]
+                elif "caption" in i:
+                    caption_task = i.split("%")[1:]
+                elif "contra" in i:
+                    contra_task = i.split("%")[1:]
+            return mlm_task, caption_task, contra_task, self.contra_loss_ratio
+        if task.startswith("ret"):
+            return [], [], task.split("%")[1:], 1.0
+        return [], [], [], 1.0
+
+    def contrastive_loss(self, feat_t, feat_v, feat_a, tok_contra, contra_task, contra_ratio=1.0):
+        """The contrastive block behind the feature gather (pretrain.py:293-407; 'coarse': :375-395): temperature, fine-weight heads and
+        token masks / va_fusion, one InfoNCE per group, their mean times `contra_ratio`. The features are whatever the caller hands in --
+        a micro-batch's own, the ranks' gathered ones, or the bank of a whole accumulation window (TrainEngine.train_window), in which
+        case they are leaves and backward leaves d loss / d bank in their .grad. tok_contra: the contrastive text tokens (host or device)."""
+        P, sp = self.P, self.spec
+        if sp.contra_type == "coarse":
+            k = P["clip_model.logit_scale"].float().exp() if sp.video_encoder == "clip" else 1.0 / P["contra_temp"].float()
+            losses = []
+            for g in contra_task:
+                if g == "tv":
+                    losses.append(ops.coarse_contrastive(feat_t, [feat_v], k))
+                elif g == "ta":
+                    losses.append(ops.coarse_contrastive(feat_t, [feat_a], k))
+                elif g == "tva" and sp.late_fusion:            # the tv and ta matrices summed (:383-384)
+                    losses.append(ops.coarse_contrastive(feat_t, [feat_v, feat_a], k))
+                elif g == "tva":                               # va_fusion(cat(v, a)) (:385-387)
+                    fva = ops.l2_normalize(ops.linear(torch.cat((feat_v, feat_a), dim=-1), P["va_fusion.weight"], P["va_fusion.bias"]))
+                    losses.append(ops.coarse_contrastive(feat_t, [fva], k))
+                else:
+                    raise NotImplementedError(f"contrastive group {g} with contra_type='coarse' (the reference handles tv / tva / ta, pretrain.py:375-395)")
+            return sum(losses) / len(losses) * contra_ratio
+        if sp.video_encoder == "clip":
+            k = P["clip_model.logit_scale"].float().exp()                # 1/temp, modeling.py:420-426
+        else:
+            k = 1.0 / P["contra_temp"].float()
+        maskA = None
+        if tok_contra is not None:
+            maskA = (tok_contra != 0).float().contiguous() if tok_contra.is_cuda else self._dev((tok_contra != 0).float()).contiguous()
+        fw = lambda name, f: ops.rowdot(ops.linear(f, P[f"{name}_fine_weight.0.weight"], P[f"{name}_fine_weight.0.bias"], ACT_RELU),
+                                        P[f"{name}_fine_weight.2.weight"], P[f"{name}_fine_weight.2.bias"]).float().squeeze(-1)
+        wt = fw("text", feat_t) if feat_t is not None else None
+        wv = fw("video", feat_v) if feat_v is not None else None
+        wa = fw("audio", feat_a) if feat_a is not None else None
+        ones = lambda f: torch.ones(f.shape[:2], dtype=torch.float32, device=self.device)
+        losses = []
+        if "tva" in contra_task and sp.late_fusion:       # pretrain.py:313-321: fine(t, v) + fine(t, a) with unit token weights
+            losses.append(ops.late_fusion_fine_contrastive(feat_t, feat_v, feat_a, maskA, k))
+        elif "tva" in contra_task:
+            fB, wB = torch.cat((feat_v, feat_a), dim=1), torch.cat((wv, wa), dim=1)
+            losses.append(ops.fine_contrastive(feat_t, fB, wt.contiguous(), wB.contiguous(), maskA, ones(fB), k))
+        if "tv" in contra_task:
+            losses.append(ops.fine_contrastive(feat_t, feat_v, wt.contiguous(), wv.contiguous(), maskA, ones(feat_v), k))
+        if "ta" in contra_task:
+            losses.append(ops.fine_contrastive(feat_t, feat_a, wt.contiguous(), wa.contiguous(), maskA, ones(feat_a), k))
+        if "va" in contra_task:                            # pretrain.py:346-352: video tokens against audio tokens
+            losses.append(ops.fine_contrastive(feat_v, feat_a, wv.contiguous(), wa.contiguous(), ones(feat_v), ones(feat_a), k))
+        if "vta" in contra_task:                           # :354-361: video queries against [text | audio]
+            fB, wB = torch.cat((feat_t, feat_a), dim=1), torch.cat((wt, wa), dim=1)
+            losses.append(ops.fine_contrastive(feat_v, fB, wv.contiguous(), wB.contiguous(), ones(feat_v),
+                                               torch.cat((maskA, ones(feat_a)), dim=1).contiguous(), k))
+        if "atv" in contra_task:                           # :363-370: audio queries against [text | video]
+            fB, wB = torch.cat((feat_t, feat_v), dim=1), torch.cat((wt, wv), dim=1)
+            losses.append(ops.fine_contrastive(feat_a, fB, wa.contiguous(), wB.contiguous(), ones(feat_a),
+                                               torch.cat((maskA, ones(feat_v)), dim=1).contiguous(), k))
+        for g in contra_task:
+            if g not in ("tva", "tv", "ta", "va", "vta", "atv"):
+                raise NotImplementedError(f"contrastive group {g}")
+        return sum(losses) / len(losses) * contra_ratio
+
+    def _forward_groups(self, batch, mlm_task, caption_task, contra_task, compute_loss, contra_ratio=1.0, window=None):
+        """The body of VALOR.forward_pt (model/pretrain.py:226-541) on parsed group lists; forward_ret / forward_cap run it with one branch.
+        window (a WindowPass): one of the two passes TrainEngine.train_window makes over a micro-batch -- the feature pass (the encoders
+        of ALL the task's groups in the usual order, no token masker, stop behind the contrastive features) or the training pass (the
+        whole forward without its own contrastive loss; the features stay in the graph and are handed to the WindowPass)."""
         P, sp = self.P, self.spec
         self._step_prologue()
         out = {}
@@ -1596,7 +1697,7 @@ class VALOR(nn.Module):
             raise NotImplementedError("full_masker with a pretraining caption task fails in the reference too (model/pretrain.py:454, the tv / ta "
                                       "slices; a 'tva'-only caption task is the one case the reference runs and this model refuses); "
                                       "use it with 'cap%..' / 'qa%..'")
-        if caption_task or mlm_task:
+        if (caption_task or mlm_task) and not (window is not None and window.features_only):
             txt = txt_tokens["bert_tokens"].cpu()
             if caption_task:
                 cap_in, cap_lab = self.caption_inputs(txt)
@@ -1664,26 +1765,14 @@ class VALOR(nn.Module):
                 audio_output = ao.view(audio_output.shape)
                 feat_a = ops.l2_normalize(ops.linear(ops.group_mean(cls_a, A), P["contra_head_a.linear.weight"], None))
             tok_contra = clip_tokens if txt_output is not None else None
-            if compute_loss and self.gather_fn is not None:
+            if window is None and compute_loss and self.gather_fn is not None:
                 feat_t, feat_v, feat_a, tok_contra = self.gather_fn(feat_t, feat_v, feat_a, self._dev(tok_contra))
             if col is not None:
                 col.update(feat_t=feat_t, feat_v=feat_v, feat_a=feat_a)
-            if compute_loss:
-                k = P["clip_model.logit_scale"].float().exp() if sp.video_encoder == "clip" else 1.0 / P["contra_temp"].float()
-                losses = []
-                for g in contra_task:
-                    if g == "tv":
-                        losses.append(ops.coarse_contrastive(feat_t, [feat_v], k))
-                    elif g == "ta":
-                        losses.append(ops.coarse_contrastive(feat_t, [feat_a], k))
-                    elif g == "tva" and sp.late_fusion:            # the tv and ta matrices summed (:383-384)
-                        losses.append(ops.coarse_contrastive(feat_t, [feat_v, feat_a], k))
-                    elif g == "tva":                               # va_fusion(cat(v, a)) (:385-387)
-                        fva = ops.l2_normalize(ops.linear(torch.cat((feat_v, feat_a), dim=-1), P["va_fusion.weight"], P["va_fusion.bias"]))
-                        losses.append(ops.coarse_contrastive(feat_t, [fva], k))
-                    else:
-                        raise NotImplementedError(f"contrastive group {g} with contra_type='coarse' (the reference handles tv / tva / ta, pretrain.py:375-395)")
-                out["contra_loss"] = sum(losses) / len(losses) * contra_ratio
+            if window is not None:
+                window.at_features(feat_t, feat_v, feat_a, tok_contra)
+            elif compute_loss:
+                out["contra_loss"] = self.contrastive_loss(feat_t, feat_v, feat_a, tok_contra, contra_task, contra_ratio)
             else:
                 out.update(feat_t=feat_t, feat_v=feat_v, feat_a=feat_a, txt_tokens=tok_contra)
         # ---------------- MGA contrastive (pretrain.py:266-407)
@@ -1715,50 +1804,18 @@ class VALOR(nn.Module):
                 ao, cls_a = ops.tap_rows(audio_output.reshape(-1, sp.aud_width), idx)
                 audio_output = ao.view(audio_output.shape)
                 feat_a = ops.l2_normalize(ops.linear(cls_a, P["contra_head_a.linear.weight"], None)).view(b, A, -1)
-            if compute_loss and self.gather_fn is not None:       # ddp_allgather_with_grads / ddp_allgather (pretrain.py:278-291)
+            if window is None and compute_loss and self.gather_fn is not None:       # ddp_allgather_with_grads / ddp_allgather (pretrain.py:278-291)
                 feat_t, feat_v, feat_a, tok_contra = self.gather_fn(feat_t, feat_v, feat_a, self._dev(tok_contra))
             if col is not None:
                 col.update(feat_t=feat_t, feat_v=feat_v, feat_a=feat_a)
-            if compute_loss:
-                if sp.video_encoder == "clip":
-                    k = P["clip_model.logit_scale"].float().exp()                # 1/temp, modeling.py:420-426
-                else:
-                    k = 1.0 / P["contra_temp"].float()
-                maskA = None
-                if tok_contra is not None:
-                    maskA = (tok_contra != 0).float().contiguous() if tok_contra.is_cuda else self._dev((tok_contra != 0).float()).contiguous()
-                fw = lambda name, f: ops.rowdot(ops.linear(f, P[f"{name}_fine_weight.0.weight"], P[f"{name}_fine_weight.0.bias"], ACT_RELU),
-                                                P[f"{name}_fine_weight.2.weight"], P[f"{name}_fine_weight.2.bias"]).float().squeeze(-1)
-                wt = fw("text", feat_t) if feat_t is not None else None
-                wv = fw("video", feat_v) if feat_v is not None else None
-                wa = fw("audio", feat_a) if feat_a is not None else None
-                ones = lambda f: torch.ones(f.shape[:2], dtype=torch.float32, device=self.device)
-                losses = []
-                if "tva" in contra_task and sp.late_fusion:       # pretrain.py:313-321: fine(t, v) + fine(t, a) with unit token weights
-                    losses.append(ops.late_fusion_fine_contrastive(feat_t, feat_v, feat_a, maskA, k))
-                elif "tva" in contra_task:
-                    fB, wB = torch.cat((feat_v, feat_a), dim=1), torch.cat((wv, wa), dim=1)
-                    losses.append(ops.fine_contrastive(feat_t, fB, wt.contiguous(), wB.contiguous(), maskA, ones(fB), k))
-                if "tv" in contra_task:
-                    losses.append(ops.fine_contrastive(feat_t, feat_v, wt.contiguous(), wv.contiguous(), maskA, ones(feat_v), k))
-                if "ta" in contra_task:
-                    losses.append(ops.fine_contrastive(feat_t, feat_a, wt.contiguous(), wa.contiguous(), maskA, ones(feat_a), k))
-                if "va" in contra_task:                            # pretrain.py:346-352: video tokens against audio tokens
-                    losses.append(ops.fine_contrastive(feat_v, feat_a, wv.contiguous(), wa.contiguous(), ones(feat_v), ones(feat_a), k))
-                if "vta" in contra_task:                           # :354-361: video queries against [text | audio]
-                    fB, wB = torch.cat((feat_t, feat_a), dim=1), torch.cat((wt, wa), dim=1)
-                    losses.append(ops.fine_contrastive(feat_v, fB, wv.contiguous(), wB.contiguous(), ones(feat_v),
-                                                       torch.cat((maskA, ones(feat_a)), dim=1).contiguous(), k))
-                if "atv" in contra_task:                           # :363-370: audio queries against [text | video]
-                    fB, wB = torch.cat((feat_t, feat_v), dim=1), torch.cat((wt, wv), dim=1)
-                    losses.append(ops.fine_contrastive(feat_a, fB, wa.contiguous(), wB.contiguous(), ones(feat_a),
-                                                       torch.cat((maskA, ones(feat_v)), dim=1).contiguous(), k))
-                for g in contra_task:
-                    if g not in ("tva", "tv", "ta", "va", "vta", "atv"):
-                        raise NotImplementedError(f"contrastive group {g}")
-                out["contra_loss"] = sum(losses) / len(losses) * contra_ratio
+            if window is not None:
+                window.at_features(feat_t, feat_v, feat_a, tok_contra)
+            elif compute_loss:
+                out["contra_loss"] = self.contrastive_loss(feat_t, feat_v, feat_a, tok_contra, contra_task, contra_ratio)
             else:
                 out.update(feat_t=feat_t, feat_v=feat_v, feat_a=feat_a, txt_tokens=tok_contra)
+        if window is not None and window.features_only:
+            return out
 
         # ---------------- decoder inputs (pretrain.py:410-416, modeling.py:485-502)
         if not (caption_task or mlm_task):

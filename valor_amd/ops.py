@@ -105,6 +105,30 @@ class DropoutState:
         if cls.base is not None:
             cls.offset = 0
             cls.base.add_(cls.STEP_STRIDE)
+            cls.steps += 1
+            cls.begun = True
+
+    steps = 0                      # begin_step() calls that moved the device counter (device mode): what window() / rewind() count in
+
+    @classmethod
+    def window(cls):
+        """The draw position, as the handle rewind() takes: (by-value offset, begin_step() count). Taken at the top of a forward pass
+        (device mode: behind its begin_step()) it names the dropout window that pass is about to draw from, so that a second pass over
+        the same micro-batch can draw the same masks (TrainEngine.train_window: feature pass, then training pass)."""
+        return (int(cls.offset), int(cls.steps))
+
+    @classmethod
+    def rewind(cls, win):
+        """Go back to window(). Host mode: the by-value offset. Device mode: the by-value offset and the device counter, moved by the
+        number of begin_step() strides between now and then with one add on the current stream (no read-back) -- the pass that follows
+        must not call begin_step() again, so the step is marked begun. Only meaningful while nothing else changed the state in between
+        (reset / set_state): the caller's window step is atomic."""
+        off, steps = win
+        cls.offset = int(off)
+        if cls.base is not None:
+            if steps != cls.steps:
+                cls.base.add_((int(steps) - cls.steps) * cls.STEP_STRIDE)
+                cls.steps = int(steps)
             cls.begun = True
 
     @classmethod
@@ -229,6 +253,19 @@ def _inference():
     """no autograd graph is being built (torch.no_grad: evaluation, generation) and this is not the first run of a checkpointed layer, which
     must run the kernels its second, differentiated run will (bit-identical activations)"""
     return not torch.is_grad_enabled() and not CheckpointFn.first_pass
+
+
+class replayed_pass:
+    """`with torch.no_grad(), ops.replayed_pass():` -- a forward pass without autograd that a later, differentiated pass over the same
+    inputs must reproduce bit for bit (the feature pass of TrainEngine.train_window): the ops launch the kernels of the training path,
+    not the inference variants (the same switch a checkpointed layer's first run uses)."""
+
+    def __enter__(self):
+        CheckpointFn.first_pass += 1
+
+    def __exit__(self, *exc):
+        CheckpointFn.first_pass -= 1
+        return False
 
 
 # ------------------------------------------------------------------------------------------------
