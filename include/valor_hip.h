@@ -713,6 +713,22 @@ int valor_fbank(void* stream, const void* wave, int is_pcm16, int64_t n_samples,
 int valor_frames_prepare(void* stream, const uint8_t* pixels, int64_t n_bytes, const int64_t* offsets, const int32_t* geom, int F,
                          int R, int antialias, const float* mean, const float* std, float* out);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Device loss meter (valor_amd/train.py LossMeter): running statistics of the scalars of a training step, no read-back.
+ * valor_meter_update: table fp32 [rows, VALOR_METER_FIELDS] (device, 16-byte aligned), one row per metered scalar:
+ *   [last, ema, sum, count, min, max, nonfinite, reserved (0)], initialised by the host to [0, 0, 0, 0, +inf, -inf, 0, 0].
+ *   src: HOST array of n DEVICE pointers to fp32 scalars; row_of: HOST array of n row indices. Both travel as kernel arguments (no copy,
+ *   nothing of them is read after the call returns). One launch of one wave, lane i owns source i. For x = *src[i], r = row_of[i]:
+ *   last = x always; x not finite: nonfinite += 1, nothing else changes; otherwise ema = count == 0 ? x : x * take + ema * keep (each
+ *   product and the sum rounded on its own: no FMA), sum += x, count += 1, min = fminf(min, x), max = fmaxf(max, x). count and nonfinite
+ *   are fp32 counters (exact up to 2^24 updates of a row).
+ *   n == 0: no-op. VALOR_ERR_ARG before any launch: n outside [0, VALOR_METER_MAX_SRC], rows < 1, a null table / src / row_of or entry
+ *   of src, a table that is not 16-byte or a source that is not 4-byte aligned, a row index outside [0, rows), two sources on one row. */
+#define VALOR_METER_FIELDS 8
+#define VALOR_METER_MAX_SRC 32
+int valor_meter_update(void* stream, float* table, int rows, const float* const* src, const int32_t* row_of, int n,
+                       float keep, float take);
+
 #ifdef __cplusplus
 }
 #endif

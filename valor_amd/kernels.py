@@ -678,3 +678,18 @@ def frames_prepare(pixels, offsets, geom, R, mean, std, antialias=False, out=Non
     lib.call("valor_frames_prepare", _stream(), _ptr(pixels), pixels.numel(), _ptr(offsets), _ptr(geom), F, int(R), int(bool(antialias)),
              (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), _ptr(out))
     return out
+
+
+def meter_update(table, srcs, rows, keep, take):
+    """fold the fp32 device scalars `srcs` into the rows `rows` of the meter table fp32 [R, 8] (valor_meter_update: last / ema / sum / count /
+    min / max / nonfinite per row, one launch, nothing is read back). The sources' addresses and the row indices go as kernel arguments."""
+    import ctypes
+    n = len(srcs)
+    if n == 0:
+        return table
+    _check_gpu(table, *srcs)
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[1] == len(lib.METER_FIELDS)
+    assert len(rows) == n and all(t.dtype == torch.float32 and t.numel() == 1 for t in srcs)
+    lib.call("valor_meter_update", _stream(), _ptr(table), table.shape[0], (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs]),
+             (ctypes.c_int32 * n)(*rows), n, float(keep), float(take))
+    return table

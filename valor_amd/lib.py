@@ -173,7 +173,10 @@ SIGNATURES = {
     "valor_colsum": [_vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _i, _i],
     "valor_fbank": [_vp, _vp, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp],
     "valor_frames_prepare": [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _vp],
+    "valor_meter_update": [_vp, _vp, _i, _c.POINTER(_vp), _c.POINTER(_c.c_int32), _i, _f, _f],
 }
+METER_FIELDS = ("last", "ema", "sum", "count", "min", "max", "nonfinite", "reserved")      # VALOR_METER_FIELDS of include/valor_hip.h
+METER_MAX_SRC = 32
 
 _lib = None
 
