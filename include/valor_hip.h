@@ -729,6 +729,38 @@ int valor_frames_prepare(void* stream, const uint8_t* pixels, int64_t n_bytes, c
 int valor_meter_update(void* stream, float* table, int rows, const float* const* src, const int32_t* row_of, int n,
                        float keep, float take);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Training diagnostics (valor_amd/diagnostics.py): statistics per arena tensor and per optimizer group, computed on the device around
+ * the fused update, no read-back; nothing that is trained is written. They take the arenas and tables of valor_adamw_counted --
+ * chunk_group int8 [n/chunk] (-1 = inactive this step), chunk_tensor int32 [n/chunk], chunk_bc as valor_adamw_counted left it, the device
+ * gscale -- and tensor_numel int64 [ntensors] (device): tensor t occupies ceil(tensor_numel[t] / chunk) consecutive chunks and ONLY its
+ * tensor_numel[t] elements count; the padding behind its tail is never read into a statistic (it may hold NaN).
+ *   tensor_stats fp32 [ntensors, VALOR_STATS_FIELDS], group_stats fp32 [ngroups, VALOR_STATS_FIELDS] (device, 16-byte aligned); a row:
+ *     0 g_sumsq      sum of g^2 over the FINITE elements, unscaled        4 w_sumsq  sum of w^2 (fp32 master)
+ *     1 g_absmax     max |g| over the finite elements                     5 u_sumsq  sum of u^2, u = lr_g * bc[1] / bc[0] * m / (sqrtf(v) + eps)
+ *     2 g_nonfinite  number of inf / NaN elements (fp32 counter)          6 w_norm   sqrt(w_sumsq)
+ *     3 g_norm       sqrt(g_sumsq) * norm_mul (units of total_norm)       7 u_ratio  sqrt(u_sumsq) / (w_norm + 1e-12)
+ *   valor_arena_grad_stats (between valor_grad_norm_clip and the update, which clears the gradients) writes fields 0-3 of every row;
+ *   valor_arena_update_stats (behind the update) writes fields 4-7: u is the Adam term the update has just applied, from the moments
+ *   behind the step, without the decay term; lr: HOST array of ngroups floats. A non-finite *gscale_dev (the step was skipped) makes
+ *   fields 5 and 7 zero in every row; gscale_dev may be null. An inactive tensor has zeros in the fields of the call. A group row is the
+ *   fold of its active tensors in tensor-index order: sum, max, sum of the tensor rows, norm and ratio recomputed from the folded sums.
+ *   Deterministic (no floating-point atomics; per-chunk partials in scratch, a tensor's chunks reduced in a fixed order of their own, in
+ *   fp64): two calls on the same data give the same bits and a tensor's row does not depend on which other tensors are active. A sum
+ *   of squares is within 23 fp32 ulp (1.4e-6 relative) of exact arithmetic plus the roundings of the stored rows, whatever the size.
+ *   scratch: fp32 words, 16-byte aligned, >= 4 * n/chunk + 2 * (ntensors rounded up to 4). Three launches each, one read of every arena.
+ *   n == 0: no-op. VALOR_ERR_ARG before any launch: a null pointer (but gscale_dev), n < 0 or not a multiple of valor_adamw_chunk(),
+ *   ntensors < 1, ngroups outside [1, 16], an unknown dtype, an arena / scratch / stats table that is not 16-byte aligned, chunk_tensor
+ *   not 4-byte, tensor_numel / chunk_bc not 8-byte, gscale_dev not 4-byte aligned. */
+#define VALOR_STATS_FIELDS 8
+int valor_arena_grad_stats(void* stream, int dtype, const void* grad, const int8_t* chunk_group, const int32_t* chunk_tensor,
+                           const int64_t* tensor_numel, int ntensors, int64_t n, int ngroups, float norm_mul, float* scratch,
+                           float* tensor_stats, float* group_stats);
+int valor_arena_update_stats(void* stream, const float* master, const float* exp_avg, const float* exp_avg_sq,
+                             const int8_t* chunk_group, const int32_t* chunk_tensor, const float* chunk_bc,
+                             const int64_t* tensor_numel, int ntensors, int64_t n, const float* lr, int ngroups, float eps,
+                             const float* gscale_dev, float* scratch, float* tensor_stats, float* group_stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,7 +70,7 @@ def bank_slice(t, m, b):
 
 
 class TrainEngine:
-    def __init__(self, model, opts, optimizer=None, manage_gc=True, graphs=None, contra_window=None):
+    def __init__(self, model, opts, optimizer=None, manage_gc=True, graphs=None, contra_window=None, diagnostics=None):
         # the reference clips unless grad_norm == -1 (train_utils.py:358): 0 would clip every gradient to zero, a negative value flip
         # its sign -- the fused clip treats any max_norm <= 0 as "off", so such values are refused here instead of silently meaning -1
         grad_norm = float(getattr(opts, "grad_norm", 5.0))
@@ -95,6 +95,9 @@ class TrainEngine:
         if manage_gc:
             gc.disable()
         self.optimizer = optimizer or FusedAdamW(model, opts)
+        # diagnostics: a valor_amd.diagnostics.Diagnostics of this optimizer (or None; it may be set later): every optimizer step --
+        # train_step, the closing micro-step of an accumulation window, train_window -- hands it to FusedAdamW.step
+        self.diagnostics = diagnostics
         self.world = torch.distributed.get_world_size() if vdist.is_dist() else 1
         self.reducer = vdist.Reducer(model.arena)
         if self.world > 1:
@@ -339,7 +342,11 @@ class TrainEngine:
             ratio = get_lr_sched(self.global_step, self.opts)                      # train_utils.py:344-347
             for g in opt.param_groups:
                 g["lr"] = g["init_lr"] * ratio
-        opt.step(active_names=active, max_grad_norm=self.grad_norm, world_size=self.world)   # clip :358-360, step :362
+        if self.diagnostics is None:
+            opt.step(active_names=active, max_grad_norm=self.grad_norm, world_size=self.world)   # clip :358-360, step :362
+        else:
+            self.diagnostics.step_index = self.global_step - 1         # a resumed run keeps the phase of `every`
+            opt.step(active_names=active, max_grad_norm=self.grad_norm, world_size=self.world, diagnostics=self.diagnostics)
         if self.max_ahead > 0 and model.arena.flat.is_cuda:
             ev = torch.cuda.Event(enable_timing=tracing)
             ev.record()

@@ -693,3 +693,49 @@ def meter_update(table, srcs, rows, keep, take):
     lib.call("valor_meter_update", _stream(), _ptr(table), table.shape[0], (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs]),
              (ctypes.c_int32 * n)(*rows), n, float(keep), float(take))
     return table
+
+
+def stats_scratch_floats(n, ntensors, chunk=1024):
+    """fp32 words of scratch valor_arena_grad_stats / valor_arena_update_stats need for an arena of n elements and ntensors tensors"""
+    return 4 * (n // chunk) + 2 * ((ntensors + 3) // 4 * 4)
+
+
+def _check_stats_tables(chunk_group, chunk_tensor, tensor_numel, scratch, tensor_stats, group_stats, n):
+    nt, ng = tensor_numel.numel(), group_stats.shape[0]
+    assert chunk_group.dtype == torch.int8 and chunk_tensor.dtype == torch.int32 and tensor_numel.dtype == torch.int64
+    assert chunk_group.is_contiguous() and chunk_tensor.is_contiguous() and tensor_numel.is_contiguous()
+    for t, rows in ((tensor_stats, nt), (group_stats, ng)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (rows, len(lib.STATS_FIELDS))
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous()
+    if n > 0:
+        chunk = lib.load().valor_adamw_chunk()
+        assert n % chunk or (chunk_group.numel() == chunk_tensor.numel() == n // chunk and scratch.numel() >= stats_scratch_floats(n, nt, chunk))
+    return nt, ng
+
+
+def arena_grad_stats(grad, chunk_group, chunk_tensor, tensor_numel, norm_mul, scratch, tensor_stats, group_stats):
+    """fields 0-3 (g_sumsq, g_absmax, g_nonfinite, g_norm) of the rows of tensor_stats fp32 [ntensors, 8] and group_stats fp32 [ngroups, 8]
+    from the flat gradient arena (valor_arena_grad_stats: three launches, one read of the arena, nothing is read back)"""
+    _check_gpu(grad, chunk_group, chunk_tensor, tensor_numel, scratch, tensor_stats, group_stats)
+    assert grad.is_contiguous() and grad.dim() == 1
+    nt, ng = _check_stats_tables(chunk_group, chunk_tensor, tensor_numel, scratch, tensor_stats, group_stats, grad.numel())
+    lib.call("valor_arena_grad_stats", _stream(), dt_of(grad), _ptr(grad), _ptr(chunk_group), _ptr(chunk_tensor), _ptr(tensor_numel), nt,
+             grad.numel(), ng, float(norm_mul), _ptr(scratch), _ptr(tensor_stats), _ptr(group_stats))
+    return tensor_stats, group_stats
+
+
+def arena_update_stats(master, exp_avg, exp_avg_sq, chunk_group, chunk_tensor, chunk_bc, tensor_numel, lr, eps, gscale, scratch,
+                       tensor_stats, group_stats):
+    """fields 4-7 (w_sumsq, u_sumsq, w_norm, u_ratio) from the fp32 master / moment arenas behind the update (valor_arena_update_stats);
+    lr: one host float per group, gscale: the device scalar of the clip (non-finite = the step was skipped) or None"""
+    import ctypes
+    _check_gpu(master, exp_avg, exp_avg_sq, chunk_group, chunk_tensor, chunk_bc, tensor_numel, gscale, scratch, tensor_stats, group_stats)
+    n = master.numel()
+    for t in (master, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    nt, ng = _check_stats_tables(chunk_group, chunk_tensor, tensor_numel, scratch, tensor_stats, group_stats, n)
+    assert chunk_bc.dtype == torch.float32 and chunk_bc.is_contiguous() and chunk_bc.numel() >= 2 * chunk_group.numel() and len(lr) == ng
+    lib.call("valor_arena_update_stats", _stream(), _ptr(master), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(chunk_group), _ptr(chunk_tensor),
+             _ptr(chunk_bc), _ptr(tensor_numel), nt, n, (ctypes.c_float * ng)(*[float(x) for x in lr]), ng, float(eps), _ptr(gscale),
+             _ptr(scratch), _ptr(tensor_stats), _ptr(group_stats))
+    return tensor_stats, group_stats

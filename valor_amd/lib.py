@@ -174,7 +174,11 @@ SIGNATURES = {
     "valor_fbank": [_vp, _vp, _i, _i64, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp],
     "valor_frames_prepare": [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _vp],
     "valor_meter_update": [_vp, _vp, _i, _c.POINTER(_vp), _c.POINTER(_c.c_int32), _i, _f, _f],
+    "valor_arena_grad_stats": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _vp, _vp, _vp],
+    "valor_arena_update_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _c.POINTER(_f), _i, _f, _vp, _vp, _vp, _vp],
 }
+# a row of the diagnostics tables (VALOR_STATS_FIELDS of include/valor_hip.h)
+STATS_FIELDS = ("g_sumsq", "g_absmax", "g_nonfinite", "g_norm", "w_sumsq", "u_sumsq", "w_norm", "u_ratio")
 METER_FIELDS = ("last", "ema", "sum", "count", "min", "max", "nonfinite", "reserved")      # VALOR_METER_FIELDS of include/valor_hip.h
 METER_MAX_SRC = 32
 

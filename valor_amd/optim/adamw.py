@@ -142,10 +142,12 @@ class FusedAdamW:
             self._tables[key] = t
         return t
 
-    def step(self, active_names=None, max_grad_norm=-1.0, world_size=1):
+    def step(self, active_names=None, max_grad_norm=-1.0, world_size=1, diagnostics=None):
         """One optimizer step over the parameters that received a gradient (`active_names`; None = all).
         The arena holds gradients SUMMED over ranks: they are scaled by 1/world_size (DDP mean) and by the
-        clip coefficient inside the update kernel."""
+        clip coefficient inside the update kernel. diagnostics: a valor_amd.diagnostics.Diagnostics -- on its steps the gradient
+        statistics are taken between the clip and the update (which clears the gradients) and, for level='full', the weight / update
+        statistics behind the update; None: the launches are the clip and the update alone."""
         a = self.arena
         names = list(a.offsets) if active_names is None else [n for n in a.offsets if n in active_names]
         table = self._table(names)
@@ -153,6 +155,9 @@ class FusedAdamW:
         ws = workspace(a.device)
         lib.call("valor_grad_norm_clip", _stream(), dt, _ptr(a.grad), _ptr(table), a.numel, 1.0 / world_size,
                  float(max_grad_norm), _ptr(ws), _ptr(self.total_norm), _ptr(self.gscale))
+        due = diagnostics is not None and diagnostics.due()
+        if due:
+            diagnostics.grad_stats(table, 1.0 / world_size)
         lr = (ctypes.c_float * self.N_GROUPS)(*[g["lr"] for g in self.param_groups])
         wd = (ctypes.c_float * self.N_GROUPS)(*[g["weight_decay"] for g in self.param_groups])
         # (Running the update of everything behind the video tower on the side stream, under the next step's video encoder, was measured:
@@ -164,6 +169,8 @@ class FusedAdamW:
                  _ptr(a.flat) if self.separate_master else None, _ptr(table), _ptr(self._chunk_tensor), _ptr(self._count), self._count.numel(),
                  _ptr(self._chunk_bc), a.numel, lr, wd, self.N_GROUPS, self.betas[0], self.betas[1], self.eps, int(self.correct_bias),
                  _ptr(self.gscale), 1)
+        if due and diagnostics.level == "full":
+            diagnostics.update_stats(table, list(lr))
         return self.total_norm
 
     # ---- the reference's optimizer checkpoint (optimizer_step_N.pt: utils/save.py:57-64 saves torch's Optimizer.state_dict() of the

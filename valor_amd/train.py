@@ -11,7 +11,12 @@ order without giving up what they were built for:
     uninterrupted run's batches.
 
 Out of scope (the caller's): datasets, file reading, tokenizers, argument parsing, launch scripts; the `adam` / `adamax` choices of
---optim; the submit modes; per-group gradient norms; a window that mixes tasks; train_window at world > 1."""
+--optim; the submit modes; a window that mixes tasks; train_window at world > 1.
+
+Diagnostics (valor_amd/diagnostics.py, Trainer(diagnostics=...) or the options diag_level / diag_every): per optimizer group the gradient
+norm and largest gradient and, at level 'full', the update-to-weight ratio and the weight norm, computed on the device around the fused
+update and folded into the meter like the losses; per arena tensor the same through asynchronous snapshots at the logging cadence, and one
+log record that names the tensors whose gradient was not finite when a step was skipped."""
 import json
 import os
 import random
@@ -341,7 +346,8 @@ class Trainer:
     train_step(batch, task, accum_steps=train_loader.ndata). window=M > 1 on an engine built with contra_window=True: M consecutive
     items -- MetaLoader(accum_steps=M) makes them share one task -- are one train_window. Every micro-step's loss_dict goes to the
     meter, at optimizer steps also `grad_norm` and `gscale` (non-finite when the step was skipped: its `nonfinite` count is the number
-    of skipped steps).
+    of skipped steps). With diagnostics, the steps that wrote the group table add its rows (`grad_norm/<group>`, `grad_absmax/<group>`, at level
+    'full' also `update_ratio/<group>`, `weight_norm/<group>`); without, the trainer's files, log lines and launches are what they were.
 
     After the optimizer step that makes (global_step + 1) % valid_steps == 0 (train_utils.py:368), once per optimizer step (the
     reference repeats it for every micro-step of an accumulation window that stands at such a step): meter.flush(), evaluate.validate,
@@ -354,7 +360,7 @@ class Trainer:
     lr_ratio is host-known and rides along); the default sink is JsonlSink(output_dir) when there is an output_dir."""
 
     def __init__(self, engine, train_loader, val_loaders=None, output_dir=None, annotations=None, log_fn=None, log_every=200,
-                 prefetch=True, window=0, meter=None):
+                 prefetch=True, window=0, meter=None, diagnostics=None):
         if not isinstance(engine.optimizer, FusedAdamW):
             raise TypeError("Trainer: the engine's optimizer is not the fused AdamW (the `adam` / `adamax` choices of --optim are out of scope)")
         self.engine, self.train_loader, self.val_loaders = engine, train_loader, val_loaders
@@ -383,12 +389,30 @@ class Trainer:
         self.metric_logger, self.best_indicator = {}, {}
         self.validations, self.checkpoints = {}, []
         self._handle = None
+        # diagnostics: a Diagnostics of the engine's optimizer, or True / a level ('grad', 'full') to build one; None: the options
+        # diag_level (and diag_every) build one when present. It is handed to the engine, which passes it to every optimizer step.
+        level = _opt(opts, "diag_level") if diagnostics is None or diagnostics is True else diagnostics
+        if diagnostics is True and level is None:
+            level = "grad"
+        if isinstance(level, str):
+            from .diagnostics import Diagnostics
+            diagnostics = Diagnostics(engine.optimizer, level=level, every=int(_opt(opts, "diag_every", 1) or 1))
+        self.diagnostics = diagnostics
+        if diagnostics is not None:
+            engine.diagnostics = diagnostics
 
     # ---- logging
     def _log(self, results):
         if self.rank == 0 and self.log_fn is not None:
             for step, scalars in results:
                 self.log_fn(step, scalars)
+
+    def _log_nonfinite(self, tables):
+        """one record per delivered per-tensor table that shows non-finite gradients: {"step": n, "nonfinite_tensors": [names]}"""
+        for t in tables:
+            bad = t.nonfinite_tensors()
+            if bad and self.rank == 0 and self.log_fn is not None:
+                self.log_fn(t.step, {"nonfinite_tensors": bad})
 
     def _host_scalars(self):
         return {"lr_ratio": float(get_lr_sched(self.engine.global_step, self.engine.opts))}
@@ -459,6 +483,8 @@ class Trainer:
 
     def _validate_and_save(self, step):
         self._log(self.meter.flush(step, self._host_scalars()))
+        if self.diagnostics is not None:
+            self._log_nonfinite(self.diagnostics.poll())
         self._validate(step)
         self._save(step)
 
@@ -489,7 +515,7 @@ class Trainer:
         """run to global_step >= num_train_steps; returns {'global_step', 'items', 'checkpoints': [steps], 'validations': {step: eval_log},
         'best': the metric history, 'meter': the final {key: {field: float}}}. resume=True: checkpoint.resume_run, then the trainer's
         file of that step; FileNotFoundError when that file is missing, unless allow_inexact=True."""
-        engine, meter = self.engine, self.meter
+        engine, meter, diag = self.engine, self.meter, self.diagnostics
         opts = engine.opts
         if resume:
             self._resume(allow_inexact)
@@ -521,18 +547,27 @@ class Trainer:
                 else:
                     loss_dict = engine.train_step(batch, task)
                     stepped = True
-            meter.update(name, loss_dict, {"grad_norm": opt.total_norm, "gscale": opt.gscale} if stepped else None)
+            extra = {"grad_norm": opt.total_norm, "gscale": opt.gscale} if stepped else None
+            if stepped and diag is not None and diag.fresh:
+                extra.update(diag.scalars())                     # the group rows of a step that wrote them (every `diag_every` steps)
+            meter.update(name, loss_dict, extra)
             if not stepped:
                 continue
             step = engine.global_step
             if self.rank == 0 and self.log_fn is not None:
                 if self.log_every > 0 and step % self.log_every == 0:
                     meter.snapshot(step, self._host_scalars())
+                    if diag is not None and diag.table_step is not None:
+                        diag.snapshot(step)
                 self._log(meter.poll())
+                if diag is not None:
+                    self._log_nonfinite(diag.poll())
             if self.valid_steps and (step + 1) % self.valid_steps == 0:
                 self._validate_and_save(step)
         final = meter.flush(engine.global_step, self._host_scalars())
         self._log(final)
+        if diag is not None and diag.table_step is not None:
+            self._log_nonfinite(diag.flush(engine.global_step))
         if self._handle is not None:
             self._handle.wait()
             if self.remove_before_ckpt and self.checkpoints:
