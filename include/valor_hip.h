@@ -761,6 +761,24 @@ int valor_arena_update_stats(void* stream, const float* master, const float* exp
                              const int64_t* tensor_numel, int ntensors, int64_t n, const float* lr, int ngroups, float eps,
                              const float* gscale_dev, float* scratch, float* tensor_stats, float* group_stats);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Exponential moving average of the weights (valor_amd/ema.py WeightEMA): one streaming pass over the fp32 masters, no read-back.
+ * valor_ema_update: w fp32 [n] (the masters, read only), ema fp32 [n] (updated in place), count: ONE device int32, the number of updates
+ *   applied so far; decay and warmup are host scalars. Per element, in fp32, every named operation rounded once (no FMA contraction, so
+ *   a restatement in plain fp32 tensor operations is bit-equal):
+ *     k = *count ;  d = warmup ? min(decay, (1 + k) / (10 + k)) : decay   (one IEEE division of the two integers converted to fp32)
+ *     a = 1 - d ;  t = w - ema ;  ema = ema + a * t                        (a product, then a sum)
+ *   so an element with w == ema stays exactly where it is, whatever d. Afterwards *count advances by one (a second, one-thread launch
+ *   behind the first, as valor_adamw_counted's). A non-finite *gscale_dev (the optimizer skipped the step; gscale_dev may be null)
+ *   writes nothing and leaves the count: the test valor_adamw* apply. Any n > 0 (the last n % 4 elements are a scalar tail); pads of an
+ *   arena are ordinary elements. 12 bytes of memory traffic per element. Two launches, deterministic.
+ *   VALOR_ERR_ARG before any launch: a null w / ema / count, n <= 0, decay outside [0, 1] or NaN, w or ema not 16-byte aligned, count or
+ *   gscale_dev not 4-byte aligned, w and ema overlapping. */
+int valor_ema_update(void* stream, const float* w, float* ema, int64_t n, float decay, int warmup, int32_t* count,
+                     const float* gscale_dev);
+/* non-temporal accesses of valor_ema_update (bit 0 loads, bit 1 stores; A/B hook, env VALOR_EMA_NT); returns the previous value, v < 0 queries */
+int valor_ema_set_nt(int v);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,12 +172,16 @@ def load_pretrained_components(opts, root="./pretrained_weights", load=None, jit
 # output_dir/ckpt/model_step_N.pt            model.state_dict(), the reference's keys (utils/save.py:45-49; VALOR.from_pretrained loads it)
 #                 optimizer_step_N.pt        the NATIVE optimizer.state_dict(): per-tensor {step, exp_avg, exp_avg_sq} + the fp32 masters
 #                 engine_step_N.rank{r}.pt   TrainEngine.state_dict(): step counters and every RNG stream, one file per rank
-# Rank 0 writes the first two. Every file is written under a temporary name (`tmp.<pid>.<name>`: neither latest_step nor the reference's
+#                 ema_step_N.pt              WeightEMA.state_dict() of an engine that averages its weights (valor_amd/ema.py), else no
+#                                            such file. The name starts with neither `model` nor `optimizer`: the reference's listings
+#                                            (train_utils.py:174-187, inference.py:65-66) parse every such name as model_step_N. Its
+#                                            "weights" entry is a model checkpoint in the reference's keys, fp32.
+# Rank 0 writes the first two and the average. Every file is written under a temporary name (`tmp.<pid>.<name>`: neither latest_step nor the reference's
 # `startswith('model')` / `startswith('optimizer')` listings see it) and renamed, so a killed process leaves no half-written step behind.
 # Not restored: the position of the data loader (the caller's), and -- for a checkpoint without an engine file, e.g. one the reference
 # wrote -- the RNG streams (resume_run(allow_inexact=True)).
 _STEP_FILE = {"model": re.compile(r"model_step_(\d+)\.pt"), "optimizer": re.compile(r"optimizer_step_(\d+)\.pt"),
-              "engine": re.compile(r"engine_step_(\d+)\.rank(\d+)\.pt")}
+              "engine": re.compile(r"engine_step_(\d+)\.rank(\d+)\.pt"), "ema": re.compile(r"ema_step_(\d+)\.pt")}
 
 
 def _rank():
@@ -191,6 +195,11 @@ def run_files(output_dir, step, rank=None):
     rank = _rank() if rank is None else rank
     return {"model": os.path.join(d, f"model_step_{step}.pt"), "optimizer": os.path.join(d, f"optimizer_step_{step}.pt"),
             "engine": os.path.join(d, f"engine_step_{step}.rank{rank}.pt")}
+
+
+def ema_file(output_dir, step):
+    """the weight average's file of step N beside the three of run_files: ckpt/ema_step_N.pt"""
+    return os.path.join(output_dir, "ckpt", f"ema_step_{step}.pt")
 
 
 def latest_step(output_dir, rank=None, need_engine=True):
@@ -281,6 +290,8 @@ class _Snapshotter:
     def __init__(self, engine):
         model, opt = engine.model, engine.optimizer
         self.src = dict(opt.flat_state(), flat=model.arena.flat)       # (fp32 mode: no separate master, the parameters are the masters)
+        if getattr(engine, "ema", None) is not None:
+            self.src.update(engine.ema.flat_state())                   # the average and its count: the same step boundary
         self.dev = {k: torch.empty_like(t) for k, t in self.src.items()}
         self.host = {k: torch.empty(t.shape, dtype=t.dtype, device="cpu", pin_memory=True) for k, t in self.src.items()}
         self.stream = torch.cuda.Stream(device=model.arena.flat.device)
@@ -316,6 +327,8 @@ class _Snapshotter:
                     osd = opt.state_dict(flat=self.host)
                     osd["param_groups"] = param_groups
                     _write(osd, files["optimizer"])
+                if "ema" in files:
+                    _write(engine.ema.state_dict(flat=self.host), files["ema"])
                 _write(engine_sd, files["engine"])
                 after()
                 handle._finished()
@@ -333,6 +346,8 @@ def save_run(engine, output_dir, step=None, blocking=True):
     handle's wait() (or the next save_run, or engine.close()) waits for the files. The engine state -- counters, host RNG -- is captured
     at the call in both modes. opts.remove_before_ckpt (default True, utils/save.py:33): older steps' files are removed once the new
     ones are complete."""
+    from .ema import refuse_applied
+    refuse_applied(engine.model.arena, "checkpoint.save_run")
     step = int(engine.global_step if step is None else step)
     rank = _rank()
     os.makedirs(os.path.join(output_dir, "ckpt"), exist_ok=True)
@@ -343,6 +358,8 @@ def save_run(engine, output_dir, step=None, blocking=True):
     files = run_files(output_dir, step, rank)
     if rank != 0:
         files = {"engine": files["engine"]}
+    elif getattr(engine, "ema", None) is not None:
+        files["ema"] = ema_file(output_dir, step)
     opts = engine.opts
     remove = bool(opts.get("remove_before_ckpt", True) if isinstance(opts, dict) else getattr(opts, "remove_before_ckpt", True))
 
@@ -357,6 +374,8 @@ def save_run(engine, output_dir, step=None, blocking=True):
     if "model" in files:
         _write(_host_copy(engine.model.state_dict()), files["model"])
         _write(_host_copy(engine.optimizer.state_dict()), files["optimizer"])
+    if "ema" in files:
+        _write(_host_copy(engine.ema.state_dict()), files["ema"])
     _write(engine_sd, files["engine"])
     after()
     handle._finished()
@@ -369,7 +388,9 @@ def resume_run(engine, output_dir, step=None, allow_inexact=False):
     A checkpoint without this rank's engine file -- one the reference wrote: its torch-Optimizer file goes through
     FusedAdamW.load_reference_state_dict -- is refused unless allow_inexact=True: then weights, moments and the LR schedule's step
     continue, the RNG streams (dropout masks, token masking, stochastic depth, sampling) start fresh, and the masters are re-derived
-    from the parameters."""
+    from the parameters. An engine that averages its weights (engine.ema) needs ema_step_N.pt as well: FileNotFoundError without it,
+    unless allow_inexact=True -- then the average starts over from the loaded masters with count 0. An engine without an average
+    ignores the file."""
     rank = _rank()
     if getattr(engine, "_saver", None) is not None:
         engine._saver.wait()                              # a save of this engine that is still being written
@@ -385,6 +406,11 @@ def resume_run(engine, output_dir, step=None, allow_inexact=False):
     if not exact and not allow_inexact:
         raise FileNotFoundError(f"resume_run: {files['engine']} is missing -- without it the RNG streams cannot be restored and the run "
                                 "does not continue bit-identically; pass allow_inexact=True to continue with fresh RNG state")
+    ema = getattr(engine, "ema", None)
+    ema_path = ema_file(output_dir, int(step)) if ema is not None else None
+    if ema is not None and not os.path.exists(ema_path) and not allow_inexact:
+        raise FileNotFoundError(f"resume_run: {ema_path} is missing -- the engine averages its weights and the average cannot be restored; "
+                                "pass allow_inexact=True to start it over from the loaded weights")
     engine_sd = torch.load(files["engine"], map_location="cpu", weights_only=True) if exact else None
     if engine_sd is not None:
         engine.load_state_dict(engine_sd)                 # first: it refuses a mismatching run before anything is overwritten
@@ -394,6 +420,11 @@ def resume_run(engine, output_dir, step=None, allow_inexact=False):
         engine.optimizer.load_state_dict(osd)
     else:                                                 # torch-Optimizer layout: the reference's optimizer_step_N.pt
         engine.optimizer.load_reference_state_dict(osd)
+    if ema is not None:
+        if os.path.exists(ema_path):
+            ema.load_state_dict(torch.load(ema_path, map_location="cpu", weights_only=True))
+        else:
+            ema.restart()
     if engine_sd is None:
         engine.global_step = int(step)
     return int(step)

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import dist as vdist
+from .ema import refuse_applied
 from .ops import DropoutState
 from .optim import FusedAdamW, get_lr_sched
 
@@ -70,7 +71,7 @@ def bank_slice(t, m, b):
 
 
 class TrainEngine:
-    def __init__(self, model, opts, optimizer=None, manage_gc=True, graphs=None, contra_window=None, diagnostics=None):
+    def __init__(self, model, opts, optimizer=None, manage_gc=True, graphs=None, contra_window=None, diagnostics=None, ema=None):
         # the reference clips unless grad_norm == -1 (train_utils.py:358): 0 would clip every gradient to zero, a negative value flip
         # its sign -- the fused clip treats any max_norm <= 0 as "off", so such values are refused here instead of silently meaning -1
         grad_norm = float(getattr(opts, "grad_norm", 5.0))
@@ -107,6 +108,13 @@ class TrainEngine:
             torch.distributed.broadcast(model.arena.flat, 0)
             for t in ((self.optimizer.master,) if self.optimizer.separate_master else ()) + (self.optimizer.exp_avg, self.optimizer.exp_avg_sq):
                 torch.distributed.broadcast(t, 0)
+        # ema: a valor_amd.ema.WeightEMA of this optimizer, else the options ema_decay (0 = off, the default) / ema_warmup / ema_every build
+        # one -- behind the broadcast: every rank averages the same masters, nothing is communicated. The optimizer steps with
+        # global_step % ema.every == 0 update it (the engine's counter: a resumed run keeps the phase); without one no launch is added.
+        if ema is None:
+            from .ema import from_options
+            ema = from_options(self.optimizer, opts)
+        self.ema = ema
         self.global_step = 0
         # The host needs ~45 ms to issue a step the GPU runs for ~118 ms: unthrottled it runs many steps ahead, and every tensor that
         # crosses streams (held by its record_stream event until the GPU passes it) then exists once per step in flight -- the caching
@@ -157,6 +165,7 @@ class TrainEngine:
                 raise ValueError("train_step: a list of micro-batches is one window step; accum_steps does not apply")
             return self.train_window(batch, task)
         model = self.model
+        refuse_applied(model.arena, "TrainEngine.train_step")
         if not model.arena.grads_bound():
             raise RuntimeError("parameter .grad tensors were detached from the gradient arena (p.grad = None / zero_grad(set_to_none=True) "
                                "on the raw parameters?): call model.zero_grad() (it re-binds) before the next step")
@@ -218,6 +227,7 @@ class TrainEngine:
         ValueError -- use train_step(accum_steps=M). The step is atomic: no accumulation window is open before or after it."""
         from .model.valor import WindowPass
         model = self.model
+        refuse_applied(model.arena, "TrainEngine.train_window")
         batches = list(batches)
         if not batches:
             raise ValueError("train_window: no micro-batches")
@@ -342,11 +352,14 @@ class TrainEngine:
             ratio = get_lr_sched(self.global_step, self.opts)                      # train_utils.py:344-347
             for g in opt.param_groups:
                 g["lr"] = g["init_lr"] * ratio
+        kw = {}
+        if self.ema is not None and self.global_step % self.ema.every == 0:
+            kw["ema"] = self.ema                                       # all arena tensors, active in this task or not (valor_amd/ema.py)
         if self.diagnostics is None:
-            opt.step(active_names=active, max_grad_norm=self.grad_norm, world_size=self.world)   # clip :358-360, step :362
+            opt.step(active_names=active, max_grad_norm=self.grad_norm, world_size=self.world, **kw)   # clip :358-360, step :362
         else:
             self.diagnostics.step_index = self.global_step - 1         # a resumed run keeps the phase of `every`
-            opt.step(active_names=active, max_grad_norm=self.grad_norm, world_size=self.world, diagnostics=self.diagnostics)
+            opt.step(active_names=active, max_grad_norm=self.grad_norm, world_size=self.world, diagnostics=self.diagnostics, **kw)
         if self.max_ahead > 0 and model.arena.flat.is_cuda:
             ev = torch.cuda.Event(enable_timing=tracing)
             ev.record()

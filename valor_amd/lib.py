@@ -176,6 +176,8 @@ SIGNATURES = {
     "valor_meter_update": [_vp, _vp, _i, _c.POINTER(_vp), _c.POINTER(_c.c_int32), _i, _f, _f],
     "valor_arena_grad_stats": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _vp, _vp, _vp],
     "valor_arena_update_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _c.POINTER(_f), _i, _f, _vp, _vp, _vp, _vp],
+    "valor_ema_update": [_vp, _vp, _vp, _i64, _f, _i, _vp, _vp],
+    "valor_ema_set_nt": [_i],
 }
 # a row of the diagnostics tables (VALOR_STATS_FIELDS of include/valor_hip.h)
 STATS_FIELDS = ("g_sumsq", "g_absmax", "g_nonfinite", "g_norm", "w_sumsq", "u_sumsq", "w_norm", "u_ratio")

@@ -108,6 +108,15 @@ class FusedAdamW:
             flat = self.arena.flat
             keep = self.master.to(flat.dtype) == flat
             torch.where(keep, self.master, flat.float(), out=self.master)
+        self._masters_rewritten()
+
+    def _masters_rewritten(self):
+        """tell the weight averages built on this optimizer (valor_amd.ema.WeightEMA) that the masters were rewritten wholesale: one that
+        has not started follows them. Without an average: nothing."""
+        for ref in getattr(self, "_emas", ()):
+            ema = ref()
+            if ema is not None:
+                ema.masters_rewritten()
 
     def init_master_from(self, state_dict_fp32):
         """Seed the fp32 masters from full-precision weights (instead of the rounded bf16 parameters)."""
@@ -126,6 +135,7 @@ class FusedAdamW:
                     if r in state_dict_fp32:
                         tmp_flat[o + i * rows:o + (i + 1) * rows].copy_(state_dict_fp32[r].reshape(-1))
         del saved
+        self._masters_rewritten()
 
     def zero_grad(self):
         """Gradients are zeroed by the fused update itself; an explicit call clears the whole arena."""
@@ -142,12 +152,14 @@ class FusedAdamW:
             self._tables[key] = t
         return t
 
-    def step(self, active_names=None, max_grad_norm=-1.0, world_size=1, diagnostics=None):
+    def step(self, active_names=None, max_grad_norm=-1.0, world_size=1, diagnostics=None, ema=None):
         """One optimizer step over the parameters that received a gradient (`active_names`; None = all).
         The arena holds gradients SUMMED over ranks: they are scaled by 1/world_size (DDP mean) and by the
         clip coefficient inside the update kernel. diagnostics: a valor_amd.diagnostics.Diagnostics -- on its steps the gradient
         statistics are taken between the clip and the update (which clears the gradients) and, for level='full', the weight / update
-        statistics behind the update; None: the launches are the clip and the update alone."""
+        statistics behind the update; None: the launches are the clip and the update alone. ema: a valor_amd.ema.WeightEMA to update
+        behind the update (and behind the level='full' statistics) -- the engine passes it on the steps that are due; a skipped step
+        leaves it alone, as it leaves the masters (the same device-side gscale test)."""
         a = self.arena
         names = list(a.offsets) if active_names is None else [n for n in a.offsets if n in active_names]
         table = self._table(names)
@@ -171,6 +183,8 @@ class FusedAdamW:
                  _ptr(self.gscale), 1)
         if due and diagnostics.level == "full":
             diagnostics.update_stats(table, list(lr))
+        if ema is not None:
+            ema.update(self.gscale)
         return self.total_norm
 
     # ---- the reference's optimizer checkpoint (optimizer_step_N.pt: utils/save.py:57-64 saves torch's Optimizer.state_dict() of the
@@ -285,5 +299,6 @@ class FusedAdamW:
             if sd.get("master") is not None and sd["master"].numel() == self.master.numel():
                 self.master.copy_(sd["master"])
                 self.arena.flat.copy_(self.master)     # parameters = rounded masters, exactly the state that was saved
+                self._masters_rewritten()
             else:
                 self.sync_master()

@@ -16,7 +16,10 @@ Out of scope (the caller's): datasets, file reading, tokenizers, argument parsin
 Diagnostics (valor_amd/diagnostics.py, Trainer(diagnostics=...) or the options diag_level / diag_every): per optimizer group the gradient
 norm and largest gradient and, at level 'full', the update-to-weight ratio and the weight norm, computed on the device around the fused
 update and folded into the meter like the losses; per arena tensor the same through asynchronous snapshots at the logging cadence, and one
-log record that names the tensors whose gradient was not finite when a step was skipped."""
+log record that names the tensors whose gradient was not finite when a step was skipped.
+
+Weight averaging (valor_amd/ema.py, Trainer(ema=...) or the options ema_decay / ema_warmup / ema_every / ema_eval): validation runs on the
+averaged weights, swapped into the arena in place for the round, and the checkpoint carries ckpt/ema_step_N.pt."""
 import json
 import os
 import random
@@ -360,7 +363,7 @@ class Trainer:
     lr_ratio is host-known and rides along); the default sink is JsonlSink(output_dir) when there is an output_dir."""
 
     def __init__(self, engine, train_loader, val_loaders=None, output_dir=None, annotations=None, log_fn=None, log_every=200,
-                 prefetch=True, window=0, meter=None, diagnostics=None):
+                 prefetch=True, window=0, meter=None, diagnostics=None, ema=None):
         if not isinstance(engine.optimizer, FusedAdamW):
             raise TypeError("Trainer: the engine's optimizer is not the fused AdamW (the `adam` / `adamax` choices of --optim are out of scope)")
         self.engine, self.train_loader, self.val_loaders = engine, train_loader, val_loaders
@@ -400,6 +403,18 @@ class Trainer:
         self.diagnostics = diagnostics
         if diagnostics is not None:
             engine.diagnostics = diagnostics
+        # ema: a WeightEMA of the engine's optimizer; None: the engine's own (built from the options ema_decay / ema_warmup / ema_every).
+        # ema_eval: which weights a validation round sees -- 'ema' (the default), 'live', or 'both': the averaged weights drive the
+        # best-metric bookkeeping and the live weights' numbers ride along under `live/<task>`
+        if ema is not None:
+            engine.ema = ema
+        elif getattr(engine, "ema", None) is None:
+            from .ema import from_options
+            engine.ema = from_options(engine.optimizer, opts)
+        self.ema = engine.ema
+        self.ema_eval = str(_opt(opts, "ema_eval", "ema"))
+        if self.ema_eval not in ("ema", "live", "both"):
+            raise ValueError(f"Trainer: ema_eval must be 'ema', 'live' or 'both', got {self.ema_eval!r}")
 
     # ---- logging
     def _log(self, results):
@@ -422,9 +437,21 @@ class Trainer:
         if not self.val_loaders:
             return {}
         model = self.engine.model
-        eval_log = evaluate.validate(model, self.val_loaders, annotations=self.annotations, output_dir=self.output_dir, global_step=step)
-        decode.release_sessions(model)
-        self.validations[step] = eval_log
+        live_log = None
+        if self.ema is None or self.ema_eval == "live":
+            eval_log = evaluate.validate(model, self.val_loaders, annotations=self.annotations, output_dir=self.output_dir, global_step=step)
+            decode.release_sessions(model)
+        else:
+            if self.ema_eval == "both":           # the live weights first, without result files: those hold the averaged weights' output
+                live_log = evaluate.validate(model, self.val_loaders, annotations=self.annotations, output_dir=None, global_step=step)
+                decode.release_sessions(model)
+            with self.ema.applied():
+                eval_log = evaluate.validate(model, self.val_loaders, annotations=self.annotations, output_dir=self.output_dir, global_step=step)
+                decode.release_sessions(model)
+        self.validations[step] = eval_log if live_log is None else dict(eval_log, **{"live/" + k: v for k, v in live_log.items()})
+        if live_log is not None and self.rank == 0 and self.log_fn is not None:
+            self.log_fn(step, {f"live/{task_name}_{eval_name}": metric for task_name, val_log in live_log.items()
+                               for eval_name, metric in val_log.items() if isinstance(metric, dict)})
         if self.rank == 0:
             for task_name, val_log in eval_log.items():
                 for eval_name, metric in val_log.items():
@@ -472,7 +499,9 @@ class Trainer:
                 self._prune(self.checkpoints[-1])
         checkpoint._write(self.state_dict(), trainer_file(self.output_dir, step, self.rank))
         if self.save_best and self.rank == 0 and any(self.best_indicator.values()):
-            sd = checkpoint._host_copy(self.engine.model.state_dict())
+            # the weights the best metric was measured on: the averaged ones unless validation ran on the live weights
+            averaged = self.ema is not None and self.ema_eval != "live"
+            sd = checkpoint._host_copy(self.ema.state_dict()["weights"] if averaged else self.engine.model.state_dict())
             for k, best in self.best_indicator.items():
                 if best:
                     checkpoint._write(sd, os.path.join(self.output_dir, "ckpt", f"best_{k}.pt"))
