@@ -609,6 +609,35 @@ int valor_sample_tokens_filtered(void* stream, const float* logits, int64_t ld, 
 int valor_logits_constrain(void* stream, float* logits, int64_t ld, int R, int V, const int64_t* hist, int64_t hist_stride_s,
                            int64_t hist_stride_k, int b, int t, int64_t eos, float penalty, float inv_penalty, int ngram, int min_len,
                            const int32_t* suppress, int n_suppress, const uint8_t* active);
+/* closed answer sets: decoding inside a token trie of candidates (csrc/trie.hip). In place on fp32 logits [R, V] (row pitch ld >= V),
+ * one launch between the step and the selection, with valor_logits_constrain's history addressing: row r reads t int64 ids with unit
+ * stride at hist + (r % b) * hist_stride_s + (r / b) * hist_stride_k, its sample is s = r % b.
+ *   The trie, flattened to CSR (valor_amd.decode.AnswerSet builds it): child_ptr int32 [n_nodes + 1]; the children of node i are the
+ *   edges child_ptr[i] .. child_ptr[i + 1], child_tok int32 [n_edges] ASCENDING inside a node, child_node int32 [n_edges] the node
+ *   behind the edge; terminal uint8 [n_nodes]: a candidate ends at this node; root int32 [n_roots], n_roots = 1 (one set for every
+ *   row) or b (a set per sample).
+ * Per row r where active is null or active[r] != 0:
+ *   1. node = root[n_roots == 1 ? 0 : s];
+ *   2. for each of the t history tokens in turn, node = the child of node whose token equals it (compared as int64 values: [SEP], an id
+ *      >= V or a negative id simply has no edge), or -1 once there is none;
+ *   3. a root or child index outside [0, n_nodes) counts as -1 and is never dereferenced; a child range is clamped to [0, n_edges];
+ *   4. the allowed set A = the child tokens of node, plus eos when node == -1 or terminal[node];
+ *   5. z_w = VALOR_TRIE_FLOOR for every column w < V that is not in A;
+ *   6. the columns in A, the columns >= V (the pad of the row) and the rows with active[r] == 0 keep their bits.
+ * The floor is finite: a dead continuation at -inf turns the 0/1-mask arithmetic of the beam search into NaN, and the fused selection
+ * never takes a -inf candidate, so a sample with fewer live continuations than beams -- the normal case here -- would leave it without
+ * a choice. exp(floor - max) is exactly 0 in fp32 for any row maximum above -1e30 + 104: a floored column has no mass.
+ * R == 0: no-op. VALOR_ERR_ARG, before any launch: null logits / child_ptr / terminal / root, null child_tok or child_node with
+ * n_edges > 0, null hist with t > 0, R < 0, V < 1, ld < V, t < 0 or > 512, b < 1, a negative history stride, n_roots not 1 or b,
+ * n_nodes < 1, n_edges < 0, eos outside [0, V). One 256-thread workgroup per row, 20 KiB of LDS (the history and up to 4096 child
+ * tokens; a longer child list is searched in global memory); the row is never read and every column written at most once, with
+ * 16-byte stores when logits and ld are multiples of 16 bytes; no atomics, no workspace: the result does not depend on how the threads
+ * split the row, graph replay equals eager issue. */
+#define VALOR_TRIE_FLOOR (-1e30f)      /* the fp32 nearest to -1e30 (bits 0xF149F2CA) */
+int valor_trie_constrain(void* stream, float* logits, int64_t ld, int R, int V, const int64_t* hist, int64_t hist_stride_s,
+                         int64_t hist_stride_k, int b, int t, int64_t eos, const int32_t* child_ptr, const int32_t* child_tok,
+                         const int32_t* child_node, const uint8_t* terminal, const int32_t* root, int n_nodes, int n_edges, int n_roots,
+                         const uint8_t* active);
 /* ---- the SCST caption reward on the device: CIDEr-D + BLEU-4 per hypothesis row (csrc/reward.hip; the rules are those of
  * valor_amd/scst.py: scorer/cider_scorer.py:119-200 with n = 1..4 and sigma 6, scorer/bleu_scorer.py:202-250 option 'closest').
  *   KEY of the n-gram (t_0 .. t_{n-1}): (t_i + 1) in bits [16 i, 16 i + 16) of a uint64, unused fields 0 -- exact, n = the number of

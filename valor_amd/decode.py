@@ -24,6 +24,10 @@ Generation controls (`Constraints`: repetition penalty, no repeated n-gram, mini
 valor_logits_constrain launch per step on the step's logits, between the step and the selection, in every loop below; with the controls
 off no launch is issued. `constrain_rows_host` restates the kernel's law on the host.
 
+Closed answer sets (`AnswerSet`: a token trie of candidates, shared or one per sample): `candidates=` makes every loop decode INSIDE the
+set with one valor_trie_constrain launch per step in the same place (`trie_rows_host` is its law on the host), and `score_candidates`
+returns the exact sequence log-probability of every candidate by forced decoding on a session of its own.
+
 Everything here is inference: torch.no_grad, dropout off regardless of model.training (the reference calls it under model.eval())."""
 import contextlib
 import gc
@@ -335,13 +339,16 @@ def beam_select_enabled():
     return os.environ.get("VALOR_BEAM_SELECT", "1") != "0"
 
 
-def beam_select(logits, b, cur, beam, seq_logprob, seq_mask, beam_major, lse="kernel", lse_out=None):
+def beam_select(logits, b, cur, beam, seq_logprob, seq_mask, beam_major, lse="kernel", lse_out=None, lse_rows=None):
     """candidate scores + `select` (pretrain.py:1080-1098,1156-1159) in one launch (valor_beam_select): logits fp32 [b * cur, V], rows
     beam-major (row = k * b + s) or sample-major; seq_logprob [b, cur | 1, 1], seq_mask [b, cur, 1] (1: open) -> (values, indices) [b, beam].
-    lse: 'kernel' (the rows' log-sum-exp inside the launch; left in lse_out [b * cur] if given) or 'xent' (the cross-entropy kernel's)"""
+    lse: 'kernel' (the rows' log-sum-exp inside the launch; left in lse_out [b * cur] if given) or 'xent' (the cross-entropy kernel's);
+    lse_rows fp32 [b * cur]: the rows' log-sum-exp computed by the caller (decoding inside an answer set: the row BEFORE its mask)"""
     V = logits.shape[1]
     dev = logits.device
-    if lse == "xent":
+    if lse_rows is not None:
+        lse_t, buf = lse_rows, (logits if logits.stride(1) == 1 else logits.contiguous())
+    elif lse == "xent":
         lse_t, buf = row_lse(logits)
     else:
         lse_t, buf = None, (logits if logits.stride(1) == 1 else logits.contiguous())
@@ -451,15 +458,250 @@ class _Constrainer:
         self.penalty, self.inv_penalty = c.penalty, c.inv_penalty
         self.suppress = torch.tensor(c.suppress_tokens, dtype=torch.int32, device=dev) if c.suppress_tokens else None
 
-    def __call__(self, logits, hist, t, active, b=None, hist_stride_s=None, hist_stride_k=0):
+    def __call__(self, logits, hist, t, active, b=None, hist_stride_s=None, hist_stride_k=0, group=1):
         c = self.c
         return K.logits_constrain(logits, hist if t > 0 else None, t, EOS, self.penalty, self.inv_penalty, c.no_repeat_ngram_size, c.min_length,
                                   self.suppress, active, b, hist_stride_s, hist_stride_k)
 
 
-def _constrainer(constraints, dev):
-    """None when no rule touches the logits: the loops then issue no launch and are the parent's, bit for bit"""
+def _constrainer(constraints, dev, candidates=None):
+    """None when no rule touches the logits: the loops then issue no launch and are the parent's, bit for bit. candidates: an AnswerSet
+    -> the launch is valor_trie_constrain (never both: _check_candidates)"""
+    if candidates is not None:
+        _no_logits_rules(constraints)
+        return _TrieConstrainer(candidates, dev)
     return None if constraints is None or constraints.logits_off else _Constrainer(constraints, dev)
+
+
+def _no_logits_rules(constraints):
+    if constraints is not None and not constraints.logits_off:
+        raise ValueError("candidates= together with a logits rule of Constraints (repetition_penalty / no_repeat_ngram_size / min_length "
+                         "/ suppress_tokens) can leave a row without an allowed token; only length_penalty combines with an answer set")
+
+
+TRIE_FLOOR = lib.TRIE_FLOOR              # VALOR_TRIE_FLOOR of include/valor_hip.h
+
+
+class AnswerSet:
+    """A closed set of answers as a token trie, for decoding inside it (valor_trie_constrain) and for looking answers up (index_of).
+    candidates: a list of token-id lists without [CLS] / [SEP] (per_sample=False: one set for every row), or a list with one such list
+    per decoder row-sample (per_sample=True). Duplicates are allowed; the lowest index names the answer. vocab: the vocabulary size the
+    ids are checked against (None: checked when the set meets a model, check_vocab).
+    The trie, flattened to CSR (host int32 / uint8 tensors; .device(dev) caches a device copy): child_ptr [N + 1], child_tok [E]
+    ascending inside a node, child_node [E], terminal [N], root [n_roots] (n_roots = 1, or one root per sample)."""
+
+    def __init__(self, candidates, per_sample=False, vocab=None):
+        sets = [list(s) for s in candidates] if per_sample else [list(candidates)]
+        if not sets:
+            raise ValueError("AnswerSet: no sample")
+        self.per_sample = bool(per_sample)
+        kids, term, first = [], [], []                  # per node: {token: node}, a candidate ends here, the lowest index that does
+
+        def new():
+            kids.append({}); term.append(0); first.append(-1)
+            return len(kids) - 1
+        roots, self.counts, self.max_len = [], [], 0
+        self.candidates = []
+        for s, cands in enumerate(sets):
+            where = f" of sample {s}" if per_sample else ""
+            if not cands:
+                raise ValueError(f"AnswerSet: the set{where} is empty")
+            root = new()
+            roots.append(root)
+            rows = []
+            for ci, cand in enumerate(cands):
+                cand = cand.tolist() if torch.is_tensor(cand) else list(cand)
+                if not cand:
+                    raise ValueError(f"AnswerSet: candidate {ci}{where} is empty")
+                node = root
+                for w in cand:
+                    if int(w) != w or w < 1 or w == EOS or (vocab is not None and w >= vocab):
+                        raise ValueError(f"AnswerSet: candidate {ci}{where} holds id {w!r}: ids lie in [1, V) and are not [SEP] = {EOS} "
+                                         "(id 0 is a masked key in this decoder)")
+                    w = int(w)
+                    nxt = kids[node].get(w)
+                    if nxt is None:
+                        nxt = kids[node][w] = new()
+                    node = nxt
+                if not term[node]:
+                    term[node], first[node] = 1, ci
+                rows.append([int(w) for w in cand])
+                self.max_len = max(self.max_len, len(cand))
+            self.candidates.append(rows)
+            self.counts.append(len(rows))
+        ptr, tok, nod = [0], [], []
+        for k in kids:
+            for w in sorted(k):
+                tok.append(w); nod.append(k[w])
+            ptr.append(len(tok))
+        self.child_ptr = torch.tensor(ptr, dtype=torch.int32)
+        self.child_tok = torch.tensor(tok, dtype=torch.int32)
+        self.child_node = torch.tensor(nod, dtype=torch.int32)
+        self.terminal = torch.tensor(term, dtype=torch.uint8)
+        self.root = torch.tensor(roots, dtype=torch.int32)
+        self.first = first
+        self.vocab = vocab
+        self._kids = kids
+        self._dev = {}
+
+    @classmethod
+    def from_bert_rows(cls, rows, per_sample_counts=None, vocab=None):
+        """rows: int [n, T] of '[CLS] tokens [SEP] 0...' (choice_tokens['bert_tokens']) -> the set of the n answers, or with
+        per_sample_counts = [c_0, c_1, ..] a per-sample set: the first c_0 rows belong to sample 0, the next c_1 to sample 1, ..."""
+        rows = rows.tolist() if torch.is_tensor(rows) else [list(r) for r in rows]
+        cands = []
+        for i, r in enumerate(rows):
+            if not r or r[0] != BOS or EOS not in r:
+                raise ValueError(f"AnswerSet.from_bert_rows: row {i} is not '[CLS] tokens [SEP]'")
+            cands.append(r[1:r.index(EOS)])
+        if per_sample_counts is None:
+            return cls(cands, vocab=vocab)
+        counts = [int(c) for c in per_sample_counts]
+        if sum(counts) != len(cands) or any(c < 0 for c in counts):
+            raise ValueError(f"AnswerSet.from_bert_rows: per_sample_counts {counts} do not describe {len(cands)} rows")
+        start = [sum(counts[:i]) for i in range(len(counts))]
+        return cls([cands[s:s + c] for s, c in zip(start, counts)], per_sample=True, vocab=vocab)
+
+    @property
+    def n_roots(self):
+        return int(self.root.numel())
+
+    @property
+    def n_nodes(self):
+        return int(self.terminal.numel())
+
+    def check_vocab(self, V):
+        if self.child_tok.numel() and int(self.child_tok.max()) >= V:
+            raise ValueError(f"AnswerSet: id {int(self.child_tok.max())} is outside the vocabulary [1, {V})")
+
+    def device(self, dev):
+        """the trie's arrays on `dev` (cached per device): what kernels.trie_constrain takes"""
+        import types
+        dev = torch.device(dev)
+        d = self._dev.get(dev)
+        if d is None:
+            d = self._dev[dev] = types.SimpleNamespace(**{k: getattr(self, k).to(dev) for k in
+                                                         ("child_ptr", "child_tok", "child_node", "terminal", "root")})
+        return d
+
+    def with_roots(self, samples):
+        """the same trie read by other rows: row-sample i of the result is sample samples[i] of this per-sample set (several question
+        rows per clip, num_return_sequences, the (sample, beam) rows of the re-run beam search)"""
+        import copy
+        out = copy.copy(self)
+        idx = torch.as_tensor(samples, dtype=torch.long)
+        out.root = self.root[idx].contiguous()
+        out.counts = [self.counts[i] for i in idx.tolist()]
+        out.candidates = [self.candidates[i] for i in idx.tolist()]
+        out._dev = {}
+        return out
+
+    def for_rows(self, b, groups=None):
+        """this set for b decoder row-samples: a shared set serves any b; a per-sample set of n entries serves b = n, or b = sum(groups)
+        with len(groups) = n (entry i is read by groups[i] consecutive rows), or b = n * k (k consecutive rows per entry)"""
+        n = self.n_roots
+        if not self.per_sample or n == b:
+            return self
+        if groups is not None and len(groups) == n and sum(groups) == b:
+            return self.with_roots([i for i, k in enumerate(groups) for _ in range(k)])
+        if b % n == 0 and groups is None:
+            return self.with_roots([i for i in range(n) for _ in range(b // n)])
+        raise ValueError(f"AnswerSet: a per-sample set of {n} entries does not describe {b} decoder rows")
+
+    def _step(self, node, w):
+        """the child of `node` along token w, or -1 (the host's dictionaries: the same edges as the CSR arrays)"""
+        return -1 if node < 0 else self._kids[node].get(int(w), -1)
+
+    def index_of(self, seqs):
+        """seqs int [R, L] (any device), every row cut at its first [SEP] (none: the whole row) -> int64 [R] (host): the candidate
+        index of the row (the lowest among duplicates), -1 when the row is no candidate. Row r reads sample r % n_roots."""
+        rows = seqs.tolist() if torch.is_tensor(seqs) else [list(r) for r in seqs]
+        out = []
+        for r, row in enumerate(rows):
+            if EOS in row:
+                row = row[:row.index(EOS)]
+            node = int(self.root[r % self.n_roots])
+            for w in row:
+                node = self._step(node, w)
+            out.append(self.first[node] if node >= 0 and row else -1)
+        return torch.tensor(out, dtype=torch.int64)
+
+
+def _answer_set(candidates):
+    """candidates= of the generate_* calls: an AnswerSet, or a plain list of token lists (one shared set)"""
+    if candidates is None or isinstance(candidates, AnswerSet):
+        return candidates
+    return AnswerSet(candidates)
+
+
+def trie_rows_host(logits, hist, t, answer_set, eos, b, active=None):
+    """The law of valor_trie_constrain (include/valor_hip.h) restated on the host from the CSR arrays: logits [R, V] (any device; not
+    modified), hist int64 [R, >= t] in ROW order (row r's own tokens; None while t == 0), b: row r reads root r % b of a per-sample
+    set, active [R] or None -> a new fp32 host tensor [R, V]. Only floor writes: bit-identical to the kernel."""
+    a = answer_set
+    out = logits.detach().to(device="cpu", dtype=torch.float32).clone()
+    R, V = out.shape
+    ptr, tok, nod, term, root = (x.tolist() for x in (a.child_ptr, a.child_tok, a.child_node, a.terminal, a.root))
+    N, E = len(term), len(tok)
+    if len(root) not in (1, b):
+        raise ValueError(f"trie_rows_host: {len(root)} roots for b = {b}")
+    floor = torch.tensor(TRIE_FLOOR, dtype=torch.float32)
+    for r in range(R):
+        if active is not None and not bool(active[r]):
+            continue
+        node = root[0 if len(root) == 1 else r % b]
+        if not 0 <= node < N:
+            node = -1
+        for w in ([] if t == 0 else hist[r, :t].tolist()):
+            if node < 0:
+                break
+            lo = min(max(ptr[node], 0), E)
+            hi = min(max(ptr[node + 1], lo), E)
+            nxt = -1
+            for e in range(lo, hi):
+                if tok[e] == w:
+                    nxt = nod[e]
+                    break
+            node = nxt if 0 <= nxt < N else -1
+        allowed = set()
+        if node >= 0:
+            lo = min(max(ptr[node], 0), E)
+            allowed = {w for w in tok[lo:min(max(ptr[node + 1], lo), E)] if 0 <= w < V}
+        if node < 0 or term[node]:
+            allowed.add(int(eos))
+        keep = torch.zeros(V, dtype=torch.bool)
+        keep[torch.tensor(sorted(allowed), dtype=torch.long)] = True
+        out[r] = torch.where(keep, out[r], floor)
+    return out
+
+
+class _TrieConstrainer:
+    """the per-step valor_trie_constrain launch of a decode loop inside an AnswerSet: _Constrainer's call. group: the rows of one sample
+    are `group` CONSECUTIVE rows (the (sample, beam) order of the re-run beam search): a per-sample set is re-rooted per row."""
+
+    def __init__(self, answer_set, dev):
+        self.a, self.dev, self._grouped = answer_set, dev, {}
+
+    def __call__(self, logits, hist, t, active, b=None, hist_stride_s=None, hist_stride_k=0, group=1):
+        a = self.a
+        if group > 1 and a.per_sample:
+            a = self._grouped.get(group)
+            if a is None:
+                a = self._grouped[group] = self.a.with_roots([i for i in range(self.a.n_roots) for _ in range(group)])
+        return K.trie_constrain(logits, hist if t > 0 else None, t, EOS, a.device(self.dev), active, b, hist_stride_s, hist_stride_k)
+
+
+def _check_candidates(model, candidates, constraints, max_len):
+    """the AnswerSet of a generate_* call, or None; raises where the combination cannot work (for_rows(b) then fits it to the rows)"""
+    a = _answer_set(candidates)
+    if a is None:
+        return None
+    _no_logits_rules(constraints)
+    if a.max_len > max_len - 1:
+        raise ValueError(f"candidates: the longest answer has {a.max_len} tokens; with its [SEP] it does not fit in max_generation_len - 1 = "
+                         f"{max_len - 1} tokens")
+    a.check_vocab(model.spec.vocab)
+    return a
 
 
 def _final_beam_order(seq_logprob, outputs, max_len, constraints):
@@ -475,14 +717,14 @@ def _final_beam_order(seq_logprob, outputs, max_len, constraints):
     return torch.sort(score, dim=1, descending=True, stable=True)[1].unsqueeze(-1)
 
 
-def decode_greedy(step, b, max_len, constraints=None):
+def decode_greedy(step, b, max_len, constraints=None, candidates=None):
     """VALOR.decode_greedy, model/pretrain.py:988-1028, mode 'greedy' (its logprobs are zeros in that mode)."""
     dev = step.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
     logprobs = torch.zeros((b, max_len), device=dev)
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     state = None
-    con = _constrainer(constraints, dev)
+    con = _constrainer(constraints, dev, candidates)
     for t in range(max_len):
         logits = step.logits(state, b)
         if con is not None:
@@ -498,23 +740,26 @@ def decode_greedy(step, b, max_len, constraints=None):
     return sents, logprobs
 
 
-def decode_beam(step, b, beam, max_len, constraints=None):
+def decode_beam(step, b, beam, max_len, constraints=None, candidates=None):
     """VALOR.decode_beam / select / _adjust_tensor, model/pretrain.py:1054-1180. A beam that produced [SEP] keeps its score for every
     candidate word (:1091-1094), so its V candidates tie and the reference's sort picks among them arbitrarily: sequences are only
     defined up to that choice once a beam has ended (the tokens behind [SEP] are dropped by decode_sequence :146-164 anyway).
-    constraints: the rows here are (sample, beam) ordered, and so is the history the launch reads; an ended beam's row is left alone."""
+    constraints: the rows here are (sample, beam) ordered, and so is the history the launch reads; an ended beam's row is left alone.
+    candidates: an AnswerSet -- the open rows are masked to the set's continuations; the log-sum-exp of a row is taken BEFORE the mask, so
+    a hypothesis keeps the model's sequence log-probability (score_candidates' law) and the candidates are ranked by it."""
     dev = step.m.device
     seq_logprob = torch.zeros((b, 1, 1), device=dev)
     seq_mask = torch.ones((b, beam, 1), device=dev)
     outputs, selected_words, state = [], None, None
-    con = _constrainer(constraints, dev)
+    con = _constrainer(constraints, dev, candidates)
     for t in range(max_len):
         cur = 1 if t == 0 else beam
         logits = step.logits(state, b * cur)
+        lse_pre = row_lse(logits)[0] if candidates is not None else None      # an answer set masks the row, the scores stay the model's logP
         if con is not None:
             active = None if t == 0 else ((seq_mask[:, :, 0] != 0) & (selected_words.view(b, cur) != EOS)).reshape(-1)
-            logits = con(logits.contiguous(), None if t == 0 else torch.cat(outputs, -1).reshape(b * cur, t), t, active)
-        word_logprob = log_softmax_rows(logits).view(b, cur, -1)
+            logits = con(logits.contiguous(), None if t == 0 else torch.cat(outputs, -1).reshape(b * cur, t), t, active, group=cur)
+        word_logprob = (log_softmax_rows(logits) if lse_pre is None else logits - lse_pre[:, None]).view(b, cur, -1)
         cand = seq_logprob + word_logprob
         if t > 0:
             mask = (selected_words.view(b, cur) != EOS).float().unsqueeze(-1)
@@ -540,7 +785,7 @@ def decode_beam(step, b, beam, max_len, constraints=None):
     return outputs.contiguous()[:, 0]
 
 
-def decode_greedy_cached(sess, b, max_len, constraints=None):
+def decode_greedy_cached(sess, b, max_len, constraints=None, candidates=None):
     """decode_greedy on a DecodeSession: the tokens stay on the device (the next step's input is this step's argmax); whether every row
     has ended is asked every eighth step (a finished row keeps producing [SEP], pretrain.py:1005-1010: the result is the same).
     constraints: one valor_logits_constrain launch on the step's logits, outside the captured step (history: sents, active: unfinished)."""
@@ -549,7 +794,7 @@ def decode_greedy_cached(sess, b, max_len, constraints=None):
     logprobs = torch.zeros((b, max_len), device=dev)
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     tok = None
-    con = _constrainer(constraints, dev)
+    con = _constrainer(constraints, dev, candidates)
     for t in range(max_len):
         logits = sess.step(tok)
         if con is not None:
@@ -563,11 +808,12 @@ def decode_greedy_cached(sess, b, max_len, constraints=None):
     return sents, logprobs
 
 
-def decode_beam_cached(sess, b, beam, max_len, constraints=None):
+def decode_beam_cached(sess, b, beam, max_len, constraints=None, candidates=None):
     """decode_beam on a DecodeSession (rows beam-major): the selection arithmetic of pretrain.py:1054-1180 on the device, the chosen
     beams as the next step's `parent` rows. Step 0 runs `beam` identical copies of every sequence and reads the first.
     constraints: one valor_logits_constrain launch per step on the open beams' rows (the history follows the beams: `outputs`), and
-    length_penalty at the final pick; in-search ranking stays the reference's."""
+    length_penalty at the final pick; in-search ranking stays the reference's. candidates: as in decode_beam (one valor_trie_constrain
+    launch per step; the rows' log-sum-exp is the cross-entropy kernel's on the unmasked row, which beam_select takes in any case)."""
     dev = sess.m.device
     seq_logprob = torch.zeros((b, 1, 1), device=dev)
     seq_mask = torch.ones((b, beam, 1), device=dev)
@@ -575,7 +821,7 @@ def decode_beam_cached(sess, b, beam, max_len, constraints=None):
     outputs = torch.zeros((b, beam, max_len), dtype=torch.int64, device=dev)
     selected_words, tok, parent = None, None, None
     fused = beam_select_enabled() and beam <= 8
-    con = _constrainer(constraints, dev)
+    con = _constrainer(constraints, dev, candidates)
     open_rows = torch.empty((beam, b), dtype=torch.bool, device=dev) if con is not None else None
     for t in range(max_len):
         cur = 1 if t == 0 else beam
@@ -584,15 +830,18 @@ def decode_beam_cached(sess, b, beam, max_len, constraints=None):
         if t > 0:
             mask = (selected_words.view(b, cur) != EOS).float().unsqueeze(-1)
             seq_mask = seq_mask * mask
+        lse_pre = row_lse(logits[:b * cur])[0] if candidates is not None else None
         if con is not None:                                          # the words so far sit in `outputs` as (sample, beam); the rows are beam-major
             if t > 0:
                 torch.ne(seq_mask.view(b, beam).t(), 0, out=open_rows)
             con(logits[:b * cur], outputs, t, open_rows.view(-1) if t > 0 else None, b, beam * max_len, max_len)
         if fused:
             # (lse='kernel' -- the log-sum-exp inside the launch -- measured equal: 64 workgroups make three more passes over their rows)
-            sel_logprob, sel_idx = beam_select(logits[:b * cur], b, cur, beam, seq_logprob, seq_mask, beam_major=True, lse="xent")
+            sel_logprob, sel_idx = beam_select(logits[:b * cur], b, cur, beam, seq_logprob, seq_mask, beam_major=True, lse="xent",
+                                               lse_rows=lse_pre)
         else:
-            word_logprob = log_softmax_rows(logits[:b * cur]).view(cur, b, -1).transpose(0, 1)
+            word_logprob = (log_softmax_rows(logits[:b * cur]) if lse_pre is None else logits[:b * cur] - lse_pre[:, None])
+            word_logprob = word_logprob.view(cur, b, -1).transpose(0, 1)
             cand = seq_logprob + word_logprob
             if t > 0:
                 cand = seq_mask * cand + seq_logprob.expand_as(cand) * (1 - seq_mask)
@@ -743,7 +992,16 @@ def _draw_step(logits, stream, sampling, unfinished, tok, sents_t, logprobs_t):
                                  sampling.top_p)
 
 
-def decode_sample_cached(sess, b, max_len, stream, sampling=None, constraints=None):
+def _skip_windows(stream, candidates, R, V, steps):
+    """inside an answer set every row ends after a few tokens and the two sampled loops leave at different steps (every eighth / at
+    once): the call still consumes its max_len counter windows, so the next group draws the same numbers on either route. Without an
+    answer set nothing is skipped: the stream is the parent's."""
+    if candidates is not None:
+        for _ in range(steps):
+            stream.take(R, V)
+
+
+def decode_sample_cached(sess, b, max_len, stream, sampling=None, constraints=None, candidates=None):
     """VALOR.decode_greedy mode 'sample' (pretrain.py:1005-1020) on a DecodeSession: one step, then one valor_sample_tokens launch that draws
     from softmax(logits), writes the logP of the draw and does the [SEP] bookkeeping. The tokens stay on the device; whether every row has
     ended is asked every eighth step, as in decode_greedy_cached. -> (sents int64 [b, max_len], logprobs fp32 [b, max_len]); after a row's
@@ -755,7 +1013,7 @@ def decode_sample_cached(sess, b, max_len, stream, sampling=None, constraints=No
     logprobs = torch.zeros((b, max_len), device=dev)
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     tok = torch.empty(b, dtype=torch.long, device=dev)
-    con = _constrainer(constraints, dev)
+    con = _constrainer(constraints, dev, candidates)
     for t in range(max_len):
         logits = sess.step(None if t == 0 else tok)
         if con is not None:
@@ -763,10 +1021,11 @@ def decode_sample_cached(sess, b, max_len, stream, sampling=None, constraints=No
         _draw_step(logits, stream, sampling, unfinished, tok, sents[:, t], logprobs[:, t])
         if t % 8 == 7 and t + 1 < max_len and not bool(unfinished.any()):
             break
+    _skip_windows(stream, candidates, b, logits.shape[1], max_len - t - 1)
     return sents, logprobs
 
 
-def decode_sample(step, b, max_len, stream, sampling=None, constraints=None):
+def decode_sample(step, b, max_len, stream, sampling=None, constraints=None, candidates=None):
     """decode_sample_cached on the re-run path (_Stepper: VALOR_KV_CACHE=0, a cross-attention block per modality); the same draws"""
     dev = step.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
@@ -774,7 +1033,7 @@ def decode_sample(step, b, max_len, stream, sampling=None, constraints=None):
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     tok = torch.empty(b, dtype=torch.long, device=dev)
     state = None
-    con = _constrainer(constraints, dev)
+    con = _constrainer(constraints, dev, candidates)
     for t in range(max_len):
         logits = step.logits(state, b).contiguous()
         if con is not None:
@@ -784,14 +1043,15 @@ def decode_sample(step, b, max_len, stream, sampling=None, constraints=None):
         state = w_host if state is None else torch.cat((state, w_host), dim=1)
         if not bool(unfinished.any()):
             break
+    _skip_windows(stream, candidates, b, logits.shape[1], max_len - t - 1)
     return sents, logprobs
 
 
-def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None, sampling=None, constraints=None):
+def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None, sampling=None, constraints=None, candidates=None):
     """{group: (sequences, logprobs | None)} for the query groups present, through the K|V-cached session or the re-run path.
     stream: a SampleStream (after begin_call) -> sampled decoding (beam 1) under `sampling` (a Sampling or None). constraints: a
-    Constraints or None, for every mode"""
-    c = constraints
+    Constraints or None, for every mode; candidates: an AnswerSet fitted to the b rows (for_rows) or None"""
+    c, a = constraints, candidates
     if isinstance(prompt, str):
         prompt = model.get_task_prompt(PROMPTS[prompt], b) if model.use_task_prompt else None
     if stream is not None:
@@ -807,15 +1067,15 @@ def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, s
         if sess is not None:
             sess.begin_group(ranges[g] if kv_layers is not None else None, prompt)
             if stream is not None:
-                out[g] = decode_sample_cached(sess, b, max_len, stream, sampling, c)
+                out[g] = decode_sample_cached(sess, b, max_len, stream, sampling, c, a)
             else:
-                out[g] = (decode_beam_cached(sess, b, beam, max_len, c), None) if beam > 1 else decode_greedy_cached(sess, b, max_len, c)
+                out[g] = (decode_beam_cached(sess, b, beam, max_len, c, a), None) if beam > 1 else decode_greedy_cached(sess, b, max_len, c, a)
         else:
             step = _Stepper(model, g, kv_layers, ranges, prompt, b)
             if stream is not None:
-                out[g] = decode_sample(step, b, max_len, stream, sampling, c)
+                out[g] = decode_sample(step, b, max_len, stream, sampling, c, a)
             else:
-                out[g] = (decode_beam(step, b, beam, max_len, c), None) if beam > 1 else decode_greedy(step, b, max_len, c)
+                out[g] = (decode_beam(step, b, beam, max_len, c, a), None) if beam > 1 else decode_greedy(step, b, max_len, c, a)
     return out
 
 
@@ -843,11 +1103,11 @@ def _sample_stream(model, seed):
 
 
 def _repeat_clips(model, kv_layers, b, n):
-    """every clip's per-layer K|V rows n times, clip-major (rows i * n .. i * n + n - 1 are clip i): one row gather per layer, the
-    way generate_qa serves sample_num"""
+    """every clip's per-layer K|V rows n times (n: an int, or one count per clip: generate_qa's sample_num), clip-major (rows
+    i * n .. i * n + n - 1 are clip i): one row gather per layer"""
     if kv_layers is None:
         return None
-    idx = model._dev(torch.arange(b, dtype=torch.long).repeat_interleave(n))
+    idx = model._dev(torch.arange(b, dtype=torch.long).repeat_interleave(n if isinstance(n, int) else torch.tensor(n, dtype=torch.long)))
     rows_of = lambda kvs: None if kvs is None else [ops.gather_rows(kv.reshape(b, -1), idx).view(idx.numel(), *kv.shape[1:]) for kv in kvs]
     return _BlockKV(rows_of(kv_layers.v), rows_of(kv_layers.a)) if isinstance(kv_layers, _BlockKV) else rows_of(kv_layers)
 
@@ -871,7 +1131,7 @@ def _sampling_of(model, temperature, top_k, top_p):
 @torch.no_grad()
 def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None, top_k=None,
                  top_p=None, num_return_sequences=1, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None,
-                 suppress_tokens=None, length_penalty=None):
+                 suppress_tokens=None, length_penalty=None, candidates=None):
     """VALOR.generate_cap, model/pretrain.py:914-985 -> {'generated_sequences_t_v' | '_t_va' | '_t_a' (+ 'logprobs_*' when greedy or
     sampled)}. mode: None (beam search when beam_size > 1, else greedy), 'greedy' (whatever beam_size says) or 'sample' (decode_greedy's
     sample mode, :1007-1011: a draw from softmax(logits) per step, logprobs_* = the logP of the draws). seed: the sampled draws' seed
@@ -882,7 +1142,11 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
     rows, and every output is [b * n, L] clip-major (rows i * n .. i * n + n - 1 belong to clip i).
     Every mode: repetition_penalty / no_repeat_ngram_size / min_length / suppress_tokens (Constraints; None: the model's options
     generation_<name>, absent = off) rewrite each step's logits on the device before the selection -- before temperature / top-k / top-p
-    too, and the log-probabilities are those of what is left; length_penalty ranks the final hypotheses of a beam search."""
+    too, and the log-probabilities are those of what is left; length_penalty ranks the final hypotheses of a beam search.
+    candidates: an AnswerSet (or a plain list of token lists: one shared set) -> every mode decodes INSIDE the set (one valor_trie_constrain
+    launch per step): each output row is one of the candidates, AnswerSet.index_of names it; a per-sample set has one entry per clip
+    (num_return_sequences rows read their clip's entry) or one per output row. It excludes the logits rules above (ValueError);
+    length_penalty stays. In sample mode the logprobs are those of the masked row: a column outside the set has mass exactly 0."""
     if mode not in (None, "greedy", "sample"):
         raise ValueError(f"generate_cap: mode {mode!r} (None, 'greedy' or 'sample')")
     n = int(num_return_sequences)
@@ -898,6 +1162,7 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
     if mode is not None:
         beam = 1
     max_len = model.max_generation_len if max_generation_len is None else max_generation_len
+    aset = _check_candidates(model, candidates, constraints, max_len)
     was_training = model.training
     model.eval()
     try:
@@ -905,10 +1170,12 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
         if n > 1:
             kv_layers = _repeat_clips(model, kv_layers, b, n)
             b *= n
+        if aset is not None:
+            aset = aset.for_rows(b)
         out = {}
         stream = _sample_stream(model, seed) if mode == "sample" else None
         for g, (seq, lp) in _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, stream, sampling,
-                                                constraints).items():
+                                                constraints, aset).items():
             key = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]
             out["generated_sequences_" + key] = seq
             if lp is not None:
@@ -921,14 +1188,16 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
 @torch.no_grad()
 def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None,
                 top_k=None, top_p=None, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None, suppress_tokens=None,
-                length_penalty=None):
+                length_penalty=None, candidates=None):
     """VALOR.generate_qa, model/pretrain.py:1366-1459: the caption decoders with the question rows as the prompt ->
     {'generated_answers_t_v' | '_t_va' | '_t_a'}. mode, seed, temperature / top_k / top_p and the Constraints arguments are
     generate_cap's: None (beam search when beam_size_qa > 1, else greedy), 'greedy', or 'sample' -- one sampled answer per question, with
     'logprobs_*' (the logP of the draws) beside the answers; the question tokens are no part of the history the constraints read.
     sample_num[i] consecutive question rows belong to clip i (:1378-1390): the reference
     expands the [video | audio] token rows per question; here the per-layer K|V projections are computed once per CLIP and their rows
-    gathered per question (valor_gather_rows), so the projection GEMMs do not grow with the question count."""
+    gathered per question (valor_gather_rows), so the projection GEMMs do not grow with the question count.
+    candidates: generate_cap's -- closed-vocabulary QA: the answer is always one of the candidates (AnswerSet.index_of). A per-sample set
+    has one entry per question row, or one per clip (its sample_num question rows read it)."""
     if mode not in (None, "greedy", "sample"):
         raise ValueError(f"generate_qa: mode {mode!r} (None, 'greedy' or 'sample')")
     sampling = None
@@ -944,24 +1213,122 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
     if mode is not None:
         beam = 1
     max_len = model.max_generation_len if max_generation_len is None else max_generation_len
+    aset = _check_candidates(model, candidates, constraints, max_len)
     was_training = model.training
     model.eval()
     try:
         b, kv_layers, ranges = encode_for_generation(model, batch, groups)
+        clips = b
         if any(n != 1 for n in sample_num):
             if len(sample_num) != b or sum(sample_num) != prompt_cpu.shape[0]:
                 raise ValueError(f"sample_num {sample_num} does not describe {b} clips / {prompt_cpu.shape[0]} questions")
-            from . import ops
-            idx = model._dev(torch.tensor([i for i, n in enumerate(sample_num) for _ in range(n)], dtype=torch.long))
-            rows_of = lambda kvs: None if kvs is None else [ops.gather_rows(kv.reshape(b, -1), idx).view(idx.numel(), *kv.shape[1:]) for kv in kvs]
-            kv_layers = _BlockKV(rows_of(kv_layers.v), rows_of(kv_layers.a)) if isinstance(kv_layers, _BlockKV) else rows_of(kv_layers)
-            b = int(idx.numel())
+            kv_layers = _repeat_clips(model, kv_layers, b, sample_num)
+            b = sum(sample_num)
+        if aset is not None:
+            aset = aset.for_rows(b, sample_num if b != clips and aset.n_roots == clips else None)
         stream = _sample_stream(model, seed) if mode == "sample" else None
-        res = _decode_groups(model, groups, b, kv_layers, ranges, prompt_cpu, beam, max_len, stream, sampling, constraints)
+        res = _decode_groups(model, groups, b, kv_layers, ranges, prompt_cpu, beam, max_len, stream, sampling, constraints, aset)
         keys = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}
         out = {"generated_answers_" + keys[g]: seq for g, (seq, _lp) in res.items()}
         if mode == "sample":
             out.update({"logprobs_" + keys[g]: lp for g, (_seq, lp) in res.items()})
+        return out
+    finally:
+        model.train(was_training)
+
+
+def _forced_terms(logits, labels):
+    """z[label] - lse(z) per fp32 row: the negated row loss of valor_xent_fwd (rows outside the session's padded buffer are copied once)"""
+    n, V = logits.shape
+    Vpad = (V + 31) // 32 * 32
+    if logits.stride() == (Vpad, 1) and logits.data_ptr() % 16 == 0:
+        buf = logits
+    else:
+        buf = torch.zeros((n, Vpad), dtype=torch.float32, device=logits.device)
+        buf[:, :V] = logits
+    lse = torch.empty(n, dtype=torch.float32, device=logits.device)
+    loss = torch.empty(n, dtype=torch.float32, device=logits.device)
+    lib.call("valor_xent_fwd", _st(), lib.DT_F32, buf.data_ptr(), labels.data_ptr(), loss.data_ptr(), lse.data_ptr(), n, V, Vpad)
+    return -loss
+
+
+@torch.no_grad()
+def score_candidates(model, batch, groups, candidates, prompt_cpu=None, max_rows=512):
+    """The exact sequence log-probability of every candidate under the decoder -> {group: fp32 [b, Cmax]} on the device (slots beyond a
+    sample's own count: -inf). For the candidate a_0 .. a_{L-1}, a_L = [SEP]:
+        score = sum_{t = 0 .. L} (z_t[a_t] - lse(z_t)),   z_t = the decoding step's logits after the forced prefix a_<t,
+    the terms added in fp32 in ascending t: what beam search assigns to that answer. candidates: an AnswerSet (shared: every sample scores
+    the same C answers; per-sample: one entry per sample) or a plain list of token lists. prompt_cpu: the QA prompt rows [b, P] (host;
+    model.qa_prompt of the questions), None: the caption prompt.
+    Forced decoding on a DecodeSession of its own (beam 1, rows = sample x candidate through _repeat_clips, the prompt rows repeated the
+    same way): every step's input is the previous forced token, a row past its end is fed [SEP] and left out of the sum, the per-step
+    term is valor_xent_fwd's row loss with the forced tokens as labels. The candidates go in chunks of max(1, max_rows // b) per sample
+    so that at most max(b, max_rows) decoder rows exist at once (a memory cap); every chunk has the same row count (the last is padded),
+    so one session and one captured step serve the call. The session is the call's own: nothing stays in the model's pool. A model
+    with a cross-attention block per modality (_BlockKV) and VALOR_KV_CACHE=0 take the re-run path (_Stepper), teacher-forced."""
+    a = _answer_set(candidates)
+    if a is None:
+        raise ValueError("score_candidates: no candidates")
+    a.check_vocab(model.spec.vocab)
+    if a.max_len + 2 > model.spec.max_pos:
+        raise ValueError(f"score_candidates: an answer of {a.max_len} tokens does not fit the decoder's {model.spec.max_pos} positions")
+    was_training = model.training
+    model.eval()
+    try:
+        b, kv_layers, ranges = encode_for_generation(model, batch, groups)
+        sample_num = [int(n) for n in batch.get("sample_num", [])]
+        if torch.is_tensor(prompt_cpu) and any(n != 1 for n in sample_num):      # several question rows per clip, as in generate_qa
+            if len(sample_num) != b or sum(sample_num) != prompt_cpu.shape[0]:
+                raise ValueError(f"sample_num {sample_num} does not describe {b} clips / {prompt_cpu.shape[0]} questions")
+            kv_layers = _repeat_clips(model, kv_layers, b, sample_num)
+            b = sum(sample_num)
+        a = a.for_rows(b)
+        dev = model.device
+        per = [a.candidates[s % a.n_roots] for s in range(b)]
+        Cmax = max(len(p) for p in per)
+        chunk = min(Cmax, max(1, int(max_rows) // b))
+        rows = b * chunk
+        kv_rep = _repeat_clips(model, kv_layers, b, chunk)
+        if isinstance(prompt_cpu, str) or prompt_cpu is None:
+            prompt = model.get_task_prompt(PROMPTS[prompt_cpu or "caption"], rows) if model.use_task_prompt else None
+        else:
+            if prompt_cpu.shape[0] != b:
+                raise ValueError(f"score_candidates: {prompt_cpu.shape[0]} prompt rows for {b} samples")
+            prompt = prompt_cpu.repeat_interleave(chunk, 0)
+        T = a.max_len + 1
+        cached = kv_cache_enabled() and not isinstance(kv_layers, _BlockKV)
+        sess = None
+        if cached:
+            sess = DecodeSession(model, rows, 1, 0 if prompt is None else prompt.shape[1], T, kv_rep)
+            sess.begin_batch(kv_rep)
+        out = {g: torch.full((b, Cmax), -float("inf"), dtype=torch.float32, device=dev) for g in ("tv", "tva", "ta") if g in groups}
+        for c0 in range(0, Cmax, chunk):
+            forced = torch.full((rows, T), EOS, dtype=torch.long)
+            length = torch.zeros(rows, dtype=torch.long)
+            real = torch.zeros((b, chunk), dtype=torch.bool)
+            for s in range(b):
+                for j in range(chunk):
+                    cand = per[s][c0 + j] if c0 + j < len(per[s]) else per[s][0]      # (a padding row repeats a real candidate)
+                    forced[s * chunk + j, :len(cand)] = torch.tensor(cand, dtype=torch.long)
+                    length[s * chunk + j] = len(cand)
+                    real[s, j] = c0 + j < len(per[s])
+            steps = int(length.max()) + 1
+            forced_d, length_d, real_d = model._dev(forced), model._dev(length), model._dev(real)
+            for g in out:
+                score = torch.zeros(rows, dtype=torch.float32, device=dev)
+                if sess is not None:
+                    sess.begin_group(ranges[g] if kv_layers is not None else None, prompt)
+                else:
+                    step = _Stepper(model, g, kv_rep, ranges, prompt, rows)
+                for t in range(steps):
+                    if sess is not None:
+                        logits = sess.step(None if t == 0 else forced_d[:, t - 1].contiguous())
+                    else:
+                        logits = step.logits(None if t == 0 else forced[:, :t], rows)
+                    term = _forced_terms(logits, forced_d[:, t].contiguous())
+                    score = torch.where(length_d >= t, score + term, score)
+                n = min(chunk, Cmax - c0)
+                out[g][:, c0:c0 + n] = torch.where(real_d, score.view(b, chunk), -float("inf"))[:, :n]
         return out
     finally:
         model.train(was_training)

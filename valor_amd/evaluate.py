@@ -522,24 +522,80 @@ def _answer_strings(batch, dec):
     return list(gt)
 
 
+def _answer_indices(batch):
+    """the ground truth of a multiple-choice batch: integer answers in batch['answers'], or in txt_tokens (data/vqa.py:169-172)"""
+    gt = batch.get("answers")
+    if gt is None:
+        gt = batch["txt_tokens"]
+    if isinstance(gt, dict):
+        raise ValueError("validate_qa(multiple_choice=True): the answers are token rows; multiple choice needs integer answers")
+    gt = gt.reshape(-1).tolist() if torch.is_tensor(gt) else list(gt)
+    if any(isinstance(a, (str, bytes)) or int(a) != a for a in gt):
+        raise ValueError("validate_qa(multiple_choice=True): the answers must be integers (the index of the right choice)")
+    return [int(a) for a in gt]
+
+
+def _choice_sets(batch, n_questions):
+    """the choices of a multiple-choice batch as a per-question AnswerSet: choice_tokens['bert_tokens'] holds the '[CLS] choice [SEP]' rows
+    of all questions back to back (data/vqa.py:161-167), the same number for every question of the batch"""
+    from . import decode as D
+    rows = batch["choice_tokens"]["bert_tokens"]
+    n = int(rows.shape[0])
+    nums = batch.get("choice_nums")
+    if nums is not None and len(set(int(c) for c in nums)) > 1:
+        raise ValueError(f"validate_qa(multiple_choice=True): choice counts {list(nums)} differ inside a batch")
+    if n_questions < 1 or n % n_questions or n == 0:
+        raise ValueError(f"validate_qa(multiple_choice=True): {n} choice rows for {n_questions} questions: every question of a batch needs the "
+                         "same number of choices")
+    return D.AnswerSet.from_bert_rows(rows.cpu(), per_sample_counts=[n // n_questions] * n_questions)
+
+
 @torch.no_grad()
-def validate_qa(model, loader, task, *, decode=None, output_dir=None, global_step=0, dset_name=""):
+def validate_qa(model, loader, task, *, decode=None, output_dir=None, global_step=0, dset_name="", candidates=None, multiple_choice=False):
     """test.py::validate_qa (:44-130): the generated answers of every group, decoded to strings, are compared with the ground truth
     (exact string equality); answers and ground truth are gathered across ranks. Returns {'tv': {'accuracy': round(acc * 100, 2)}, ..}
     on every rank. With output_dir, rank 0 writes predict_answers/step{global_step}_gt.json, step{..}_tv_pred.json and the question_ids
-    submission list step{..}_tv_pred_submited_{dset_name}.json (batch['question_ids'], group tv only: :79-81, :112-114)."""
+    submission list step{..}_tv_pred_submited_{dset_name}.json (batch['question_ids'], group tv only: :79-81, :112-114).
+    candidates: a decode.AnswerSet or a list of token lists (default: the model's option qa_answer_candidates) -- the same flow with the
+    generation constrained to that closed set: every prediction is one of the candidates.
+    multiple_choice (default: the model's option qa_multiple_choice): the choices of every question come from
+    batch['choice_tokens']['bert_tokens'] (the same count per question inside a batch), the ground truth is the integer index in
+    batch['answers'] (or txt_tokens), the prediction is the arg max of decode.score_candidates (the exact sequence log-probability of
+    every choice; ties to the lower index); the dumps hold indices. A call that passes neither, on a model without the options, is the
+    reference's flow unchanged."""
     import json
     import os
+    from .model.valor import _opt
+    from . import decode as D
+    core = _unwrapped(model)
+    opts = getattr(core, "opts", None)
+    multiple_choice = bool(multiple_choice) or bool(_opt(opts, "qa_multiple_choice", False))
+    if candidates is None:
+        candidates = _opt(opts, "qa_answer_candidates", None)
+    if multiple_choice and candidates is not None:
+        raise ValueError("validate_qa: multiple_choice scores the batch's own choices; candidates= (qa_answer_candidates) is the other mode")
+    candidates = D._answer_set(candidates)
     groups = task.split("%")[1:]
     dec = _decoder(model, decode)
     model.eval()
     gt, submit = [], []
     answers = {g: [] for g in ("tv", "tva", "ta") if g in groups}
     for batch in loader:
-        gt += _answer_strings(batch, dec)
-        ev = model(batch, task=task, compute_loss=False)
+        if multiple_choice:
+            gt += _answer_indices(batch)
+            prompt = core.qa_prompt(batch["question_tokens"]["bert_tokens"].cpu())
+            scores = D.score_candidates(core, batch, list(answers), _choice_sets(batch, prompt.shape[0]), prompt_cpu=prompt)
+            cols = torch.arange(next(iter(scores.values())).shape[1], device=core.device)
+            # the first column that holds the row maximum: ties go to the lower index
+            ev = {"generated_answers_" + _GROUP_KEY[g]: torch.where(sc == sc.max(1, keepdim=True).values, cols, cols.numel()).min(1).values.cpu()
+                  for g, sc in scores.items()}
+            pick = lambda x: [int(i) for i in x]
+        else:
+            gt += _answer_strings(batch, dec)
+            ev = model(batch, task=task, compute_loss=False, **({} if candidates is None else {"candidates": candidates}))
+            pick = dec
         for g in answers:
-            a = dec(ev["generated_answers_" + _GROUP_KEY[g]])
+            a = pick(ev["generated_answers_" + _GROUP_KEY[g]])
             answers[g] += a
             if g == "tv" and batch.get("question_ids") is not None:
                 submit += [{"question_id": q, "answer": s} for q, s in zip(batch["question_ids"], a)]
@@ -582,7 +638,8 @@ def validate_single(model, loader, task, *, annotations=None, dset_name="", outp
             raise ValueError(f"task {task!r}: caption evaluation needs annotations (or loader.dataset.annfile)")
         return validate_cap(model, loader, task, annotations, output_dir=output_dir, global_step=global_step, dset_name=dset_name, **kw)
     if task.startswith("qa"):
-        return validate_qa(model, loader, task, decode=kw.get("decode"), output_dir=output_dir, global_step=global_step, dset_name=dset_name)
+        return validate_qa(model, loader, task, decode=kw.get("decode"), output_dir=output_dir, global_step=global_step, dset_name=dset_name,
+                           candidates=kw.get("candidates"), multiple_choice=kw.get("multiple_choice", False))
     raise NotImplementedError(f"task {task!r}: 'pt', 'ret', 'cap' and 'qa' are the reference's evaluation families (test.py:33-40)")
 
 

@@ -166,6 +166,7 @@ SIGNATURES = {
     "valor_sample_tokens": [_vp, _vp, _i64, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _i64, _vp, _i64],
     "valor_sample_tokens_filtered": [_vp, _vp, _i64, _i, _i, _u64, _u64, _i64, _f, _i, _f, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
     "valor_logits_constrain": [_vp, _vp, _i64, _i, _i, _vp, _i64, _i64, _i, _i, _i64, _f, _f, _i, _i, _vp, _i, _vp],
+    "valor_trie_constrain": [_vp, _vp, _i64, _i, _i, _vp, _i64, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "valor_caption_reward": [_vp, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp],
     "valor_caption_metrics": [_vp, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "valor_rowdot_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i],
@@ -183,6 +184,7 @@ SIGNATURES = {
 STATS_FIELDS = ("g_sumsq", "g_absmax", "g_nonfinite", "g_norm", "w_sumsq", "u_sumsq", "w_norm", "u_ratio")
 METER_FIELDS = ("last", "ema", "sum", "count", "min", "max", "nonfinite", "reserved")      # VALOR_METER_FIELDS of include/valor_hip.h
 METER_MAX_SRC = 32
+TRIE_FLOOR = _c.c_float(-1e30).value      # VALOR_TRIE_FLOOR of include/valor_hip.h: the fp32 nearest to -1e30, as a Python float
 
 _lib = None
 

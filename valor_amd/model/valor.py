@@ -1303,8 +1303,11 @@ class VALOR(nn.Module):
         return out
 
     # ------------------------------------------------------------------ the hot path
-    def forward(self, batch, task, compute_loss=True, window=None):
-        """VALOR.forward, model/pretrain.py:125-135. window: a WindowPass (TrainEngine.train_window; 'pt_*' / 'ret%*' tasks only)"""
+    def forward(self, batch, task, compute_loss=True, window=None, candidates=None):
+        """VALOR.forward, model/pretrain.py:125-135. window: a WindowPass (TrainEngine.train_window; 'pt_*' / 'ret%*' tasks only).
+        candidates: a decode.AnswerSet for the generation branch of 'cap%*' / 'qa%*' (compute_loss=False): decoding inside the set"""
+        if candidates is not None and not (task.startswith(("cap", "qa")) and not compute_loss):
+            raise ValueError(f"task {task!r}, compute_loss={compute_loss}: candidates= belongs to the generation branch of 'cap%*' / 'qa%*'")
         if task.startswith("pt"):
             return self.forward_pt(batch, task, compute_loss=compute_loss, window=window)
         if task.startswith("ret"):
@@ -1312,9 +1315,9 @@ class VALOR(nn.Module):
         if window is not None:
             raise ValueError(f"task {task!r} has no contrastive groups: a window pass is for 'pt_*' / 'ret%*' tasks")
         if task.startswith("cap"):
-            return self.forward_cap(batch, task, compute_loss=compute_loss)
+            return self.forward_cap(batch, task, compute_loss=compute_loss, candidates=candidates)
         if task.startswith("qa"):
-            return self.forward_qa(batch, task, compute_loss=compute_loss)
+            return self.forward_qa(batch, task, compute_loss=compute_loss, candidates=candidates)
         raise NotImplementedError(f"task {task!r}: 'pt_*', 'ret%*', 'cap%*' and 'qa%*' are the reference's task families (pretrain.py:125-135)")
 
     def forward_ret(self, batch, task, compute_loss=True, window=None):
@@ -1324,11 +1327,14 @@ class VALOR(nn.Module):
         feat_t / feat_v / feat_a / txt_tokens (:708-715), what evaluate.compute_fine_matrix consumes."""
         return self._forward_groups(batch, [], [], task.split("%")[1:], compute_loss, contra_ratio=1.0, window=window)
 
-    def forward_cap(self, batch, task, compute_loss=True):
+    def forward_cap(self, batch, task, compute_loss=True, candidates=None):
         """VALOR.forward_cap, model/pretrain.py:713-725 (config/caption-*.json: 'cap%tva%tv'; caption_type 'unimlm', no label smoothing /
         scst / full_masker -- the shipped settings). Loss: forward_cap_single :802-880 = the caption passes of forward_pt. Otherwise
-        generate_cap :914-985 -> valor_amd.decode (greedy for beam_size 1, beam search above)."""
+        generate_cap :914-985 -> valor_amd.decode (greedy for beam_size 1, beam search above), inside `candidates` (a decode.AnswerSet)
+        when given."""
         groups = task.split("%")[1:]
+        if compute_loss and candidates is not None:
+            raise ValueError("forward_cap: candidates= belongs to compute_loss=False")
         if compute_loss and self.scst_finetuning:
             return self.forward_cap_scst(batch, groups)
         if compute_loss:
@@ -1338,7 +1344,7 @@ class VALOR(nn.Module):
             finally:
                 self._smoothing, self._full_attn = 0.0, False
         from .. import decode
-        return decode.generate_cap(self, batch, groups)
+        return decode.generate_cap(self, batch, groups, candidates=candidates)
 
     def decode_sequence(self, seq):
         """VALOR.decode_sequence, model/pretrain.py:146-163 (BERT branch): int [N, T] generated ids -> N strings: every row cut at its
@@ -1361,17 +1367,19 @@ class VALOR(nn.Module):
         tp = self.get_task_prompt(PROMPTS["qa"], question_cpu.shape[0])[:, 1:-1]
         return torch.cat((question_cpu[:, 0:1], tp, question_cpu[:, 1:]), dim=1)
 
-    def forward_qa(self, batch, task, compute_loss=True):
+    def forward_qa(self, batch, task, compute_loss=True, candidates=None):
         """VALOR.forward_qa, model/pretrain.py:1191-1459 (config/VQA-*.json: 'qa%tva%tv'). Loss: forward_qa_single :1212-1345 --
         TokenMasker p = 0.99 on the answer rows, causal decoder with the question as prompt rows, per-row-normalised CE; one answer per
         question (video QA: the mean over samples) or several weighted candidates (image QA, `answer_nums` / `answer_weights`: weighted
         rows summed over the question count). Otherwise generate_qa :1366-1459 -> valor_amd.decode with beam_size_qa (one question per
-        clip)."""
+        clip), inside `candidates` (a decode.AnswerSet: closed-vocabulary QA) when given."""
         groups = [g for g in ("tva", "tv", "ta") if g in task.split("%")[1:]]
+        if compute_loss and candidates is not None:
+            raise ValueError("forward_qa: candidates= belongs to compute_loss=False")
         prompt = self.qa_prompt(batch["question_tokens"]["bert_tokens"].cpu())
         if not compute_loss:
             from .. import decode
-            return decode.generate_qa(self, batch, groups, prompt)
+            return decode.generate_qa(self, batch, groups, prompt, candidates=candidates)
         self.stage.begin_step()
         txt = batch["txt_tokens"]["bert_tokens"].cpu()
         nums = [int(n) for n in batch.get("answer_nums", [1] * txt.shape[0])]
