@@ -252,8 +252,8 @@ def test_generate_and_validate_argument_errors_and_signatures():
             gen(candidates=[[7, 0]])
         with pytest.raises(ValueError, match="empty"):
             gen(candidates=[[7], []])
-    for fn in (decode.generate_cap, decode.generate_qa, decode.decode_greedy, decode.decode_greedy_cached, decode.decode_beam,
-               decode.decode_beam_cached, decode.decode_sample, decode.decode_sample_cached, decode._decode_groups):
+    for fn in (decode.generate_cap, decode.generate_qa, decode.decode_greedy, decode.decode_beam, decode.decode_sample,
+               decode._decode_groups):
         assert inspect.signature(fn).parameters["candidates"].default is None
     p = inspect.signature(decode.score_candidates).parameters
     assert list(p)[:4] == ["model", "batch", "groups", "candidates"] and p["prompt_cpu"].default is None and p["max_rows"].default == 512

@@ -31,7 +31,8 @@ def same_bits(a, b):
 
 # ------------------------------------------------------------------------------------------------ scripted steps
 class StubSession:
-    """what the cached loops use of a DecodeSession: .m.device and .step(tok, parent) -> this step's prepared logits [rows, V]"""
+    """what the loops use of a DecodeSession: .m.device, .poll and .step(tok, parent) -> this step's prepared logits [rows, V]"""
+    poll = 8
 
     def __init__(self, script, dev):
         self.m = types.SimpleNamespace(device=dev)
@@ -45,19 +46,26 @@ class StubSession:
 
 
 class StubStepper:
-    """what the re-run loops use of a _Stepper: .m.device and .logits(state, rows); rows arrive (sample, beam) ordered while the script
-    is beam-major like the session's"""
+    """what the re-run source uses of a _Stepper: .m.device, .b and .logits(state, rows); the rows are beam-major like the script's and
+    the session's. Keeps the states it was handed."""
 
     def __init__(self, script, dev, b):
         self.m = types.SimpleNamespace(device=dev)
         self.script = [s.to(dev) for s in script]
         self.b = b
+        self.states = []
 
     def logits(self, state, rows):
+        self.states.append(None if state is None else state.clone())
+        assert state is None or (state.shape[0] == rows and state.dtype == torch.int64 and state.device.type == "cpu")
         t = 0 if state is None else state.shape[1]
-        cur = rows // self.b
-        z = self.script[t][:rows]
-        return z.view(cur, self.b, -1).transpose(0, 1).reshape(rows, -1).clone()
+        return self.script[t][:rows].clone()
+
+
+def rerun_source(script, dev):
+    """the re-run step source over the script: its host-state bookkeeping runs, the decoder is the stub"""
+    from valor_amd import decode
+    return decode._Rerun(StubStepper(script, dev, B))
 
 
 @pytest.fixture
@@ -97,22 +105,22 @@ def test_scripted_greedy_equals_the_host_law_loop(dev, sep):
     from valor_amd import decode
     for seed in (0, 1):
         script = script_of(seed, rows=B)
-        plain = decode.decode_greedy_cached(StubSession(script, dev), B, L)[0].cpu()
+        plain = decode.decode_greedy(StubSession(script, dev), B, L)[0].cpu()
         for a in scripted_sets():
             want = host_greedy(script, a, sep)
-            got = decode.decode_greedy_cached(StubSession(script, dev), B, L, None, a)[0].cpu()
-            rerun = decode.decode_greedy(StubStepper(script, dev, B), B, L, None, a)[0].cpu()
+            got = decode.decode_greedy(StubSession(script, dev), B, L, None, a)[0].cpu()
+            rerun = decode.decode_greedy(rerun_source(script, dev), B, L, None, a)[0].cpu()
             assert torch.equal(got, want) and torch.equal(rerun, want), (seed, got, want)
             assert (a.index_of(got) >= 0).all() and not torch.equal(got, plain)
     # length_penalty is no logits rule: it may stay; a logits rule may not
     a = scripted_sets()[0]
-    decode.decode_greedy_cached(StubSession(script, dev), B, L, decode.Constraints(length_penalty=1.0), a)
+    decode.decode_greedy(StubSession(script, dev), B, L, decode.Constraints(length_penalty=1.0), a)
     with pytest.raises(ValueError, match="candidates"):
-        decode.decode_greedy_cached(StubSession(script, dev), B, L, decode.Constraints(min_length=2), a)
+        decode.decode_greedy(StubSession(script, dev), B, L, decode.Constraints(min_length=2), a)
 
 
 def local_beam(script, dev, beam, a, eos):
-    """decode_beam_cached's loop with the launch replaced: the device logits go to the host law and come back for the existing
+    """decode_beam's loop with the launch replaced: the device logits go to the host law and come back for the existing
     beam_select (which is given the log-sum-exp of the rows before the mask: a hypothesis' score is the model's sequence logP); rows
     beam-major, the history of row k * b + s = the words of beam k of sample s. -> (best sequences, their logP)"""
     from valor_amd import decode
@@ -154,11 +162,11 @@ def test_scripted_beam_equals_host_law_plus_beam_select(dev, sep, monkeypatch):
         script = script_of(seed)
         for a in scripted_sets():
             want, logp = local_beam(script, dev, beam, a, sep)
-            got = decode.decode_beam_cached(StubSession(script, dev), B, beam, L, None, a).cpu()
+            got = decode.decode_beam(StubSession(script, dev), B, beam, L, None, a).cpu()
             assert cut(got, sep) == cut(want, sep), (seed, got, want)
             assert (a.index_of(got) >= 0).all() and torch.isfinite(logp).all() and (logp > -1e3).all()
-            rerun = decode.decode_beam(StubStepper(script, dev, B), B, beam, L, None, a).cpu()
-            assert cut(rerun, sep) == cut(want, sep), (seed, rerun, want)
+            rerun = decode.decode_beam(rerun_source(script, dev), B, beam, L, None, a).cpu()
+            assert cut(rerun, sep) == cut(want, sep) and torch.equal(rerun, got), (seed, rerun, want)
 
 
 def test_one_candidate_per_sample_under_beam_3(dev, sep, monkeypatch):
@@ -176,14 +184,14 @@ def test_one_candidate_per_sample_under_beam_3(dev, sep, monkeypatch):
         assert abs(float(logp[s]) - ref) < 1e-4 * (len(c) + 1), (s, float(logp[s]), ref)
     for flag in ("1", "0"):
         monkeypatch.setenv("VALOR_BEAM_SELECT", flag)
-        got = decode.decode_beam_cached(StubSession(script, dev), B, 3, L, None, one).cpu()
+        got = decode.decode_beam(StubSession(script, dev), B, 3, L, None, one).cpu()
         assert cut(got, sep) == cut(want, sep), flag
-        rerun = decode.decode_beam(StubStepper(script, dev, B), B, 3, L, None, one).cpu()
+        rerun = decode.decode_beam(rerun_source(script, dev), B, 3, L, None, one).cpu()
         assert cut(rerun, sep) == cut(want, sep), flag
 
 
 def host_sample(script, dev, a, eos, seed, sampling):
-    """decode_sample_cached's loop: the host law, then the unchanged sampler launch"""
+    """decode_sample's loop: the host law, then the unchanged sampler launch"""
     from valor_amd import decode, kernels as K
     stream = decode.SampleStream(seed).begin_call()
     sents = torch.full((B, L), eos, dtype=torch.long, device=dev)
@@ -208,9 +216,9 @@ def test_scripted_sampling_equals_the_host_law_loop_and_stays_inside_the_set(dev
         for sampling in (None, decode.Sampling(top_k=2, top_p=0.9), decode.Sampling(temperature=1.7)):
             for seed in range(6):
                 want, want_lp = host_sample(script, dev, a, sep, seed, sampling)
-                got, lp = decode.decode_sample_cached(StubSession(script, dev), B, L, decode.SampleStream(seed).begin_call(), sampling, None, a)
+                got, lp = decode.decode_sample(StubSession(script, dev), B, L, decode.SampleStream(seed).begin_call(), sampling, None, a)
                 assert torch.equal(got.cpu(), want) and same_bits(lp.cpu(), want_lp), (seed, sampling)
-                rr, rlp = decode.decode_sample(StubStepper(script, dev, B), B, L, decode.SampleStream(seed).begin_call(), sampling, None, a)
+                rr, rlp = decode.decode_sample(rerun_source(script, dev), B, L, decode.SampleStream(seed).begin_call(), sampling, None, a)
                 assert torch.equal(rr.cpu(), want) and same_bits(rlp.cpu(), want_lp), (seed, sampling)
                 idx = a.index_of(want)
                 assert (idx >= 0).all(), (seed, sampling, want)                           # every draw lay in the allowed set

@@ -267,6 +267,5 @@ def test_generate_argument_errors_and_signatures():
     for fn in (decode.generate_cap, decode.generate_qa):
         p = inspect.signature(fn).parameters
         assert all(p[k].default is None for k in names)
-    for fn in (decode.decode_greedy, decode.decode_greedy_cached, decode.decode_beam, decode.decode_beam_cached, decode.decode_sample,
-               decode.decode_sample_cached, decode._decode_groups):
+    for fn in (decode.decode_greedy, decode.decode_beam, decode.decode_sample, decode._decode_groups):
         assert inspect.signature(fn).parameters["constraints"].default is None

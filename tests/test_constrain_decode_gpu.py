@@ -29,7 +29,8 @@ def same_bits(a, b):
 
 # ------------------------------------------------------------------------------------------------ scripted steps
 class StubSession:
-    """what the cached loops use of a DecodeSession: .m.device and .step(tok, parent) -> this step's prepared logits [rows, V]"""
+    """what the loops use of a DecodeSession: .m.device, .poll and .step(tok, parent) -> this step's prepared logits [rows, V]"""
+    poll = 8
 
     def __init__(self, script, dev):
         self.m = types.SimpleNamespace(device=dev)
@@ -45,19 +46,26 @@ class StubSession:
 
 
 class StubStepper:
-    """what the re-run loops use of a _Stepper: .m.device and .logits(state, rows); rows arrive (sample, beam) ordered while the script
-    is beam-major like the session's"""
+    """what the re-run source uses of a _Stepper: .m.device, .b and .logits(state, rows); the rows are beam-major like the script's and
+    the session's. Keeps the states it was handed."""
 
     def __init__(self, script, dev, b):
         self.m = types.SimpleNamespace(device=dev)
         self.script = [s.to(dev) for s in script]
         self.b = b
+        self.states = []
 
     def logits(self, state, rows):
+        self.states.append(None if state is None else state.clone())
+        assert state is None or (state.shape[0] == rows and state.dtype == torch.int64 and state.device.type == "cpu")
         t = 0 if state is None else state.shape[1]
-        cur = rows // self.b
-        z = self.script[t][:rows]
-        return z.view(cur, self.b, -1).transpose(0, 1).reshape(rows, -1).clone()
+        return self.script[t][:rows].clone()
+
+
+def rerun_source(script, dev):
+    """the re-run step source over the script: its host-state bookkeeping runs, the decoder is the stub"""
+    from valor_amd import decode
+    return decode._Rerun(StubStepper(script, dev, B))
 
 
 @pytest.fixture
@@ -104,8 +112,8 @@ def repeated_ngrams(row, n, eos):
 
 def both_greedy(script, dev, c):
     from valor_amd import decode
-    a = decode.decode_greedy_cached(StubSession(script, dev), B, L, c)[0].cpu()
-    b = decode.decode_greedy(StubStepper(script, dev, B), B, L, c)[0].cpu()
+    a = decode.decode_greedy(StubSession(script, dev), B, L, c)[0].cpu()
+    b = decode.decode_greedy(rerun_source(script, dev), B, L, c)[0].cpu()
     assert torch.equal(a, b)
     return a
 
@@ -143,7 +151,7 @@ def test_scripted_greedy_min_length_and_suppress(dev, sep):
 
 
 def local_beam(script, dev, beam, c, eos):
-    """decode_beam_cached's loop with the launch replaced: the device logits go to the host law and come back for the existing
+    """decode_beam's loop with the launch replaced: the device logits go to the host law and come back for the existing
     beam_select; rows beam-major, the history of row k * b + s = the words of beam k of sample s"""
     from valor_amd import decode
     seq_logprob = torch.zeros((B, 1, 1), device=dev)
@@ -186,19 +194,19 @@ def test_scripted_beam_equals_host_law_plus_beam_select(dev, sep):
         z[:, 8] += 3.0 if t % 2 == 0 else 4.0
         z[:, sep] += 2.5 if t >= 4 else -4.0
         script.append(z)
-    plain = decode.decode_beam_cached(StubSession(script, dev), B, beam, L).cpu()
+    plain = decode.decode_beam(StubSession(script, dev), B, beam, L).cpu()
     assert torch.equal(plain, local_beam(script, dev, beam, decode.Constraints(), sep))
     assert any(repeated_ngrams(r, 2, sep) > 0 for r in plain)                                    # the condition: the plain search repeats
     for c in (decode.Constraints(no_repeat_ngram_size=2), decode.Constraints(no_repeat_ngram_size=2, min_length=6, suppress_tokens=(9, 7)),
               decode.Constraints(no_repeat_ngram_size=3, repetition_penalty=1.3), decode.Constraints(no_repeat_ngram_size=1)):
         want = local_beam(script, dev, beam, c, sep)
-        got = decode.decode_beam_cached(StubSession(script, dev), B, beam, L, c).cpu()
+        got = decode.decode_beam(StubSession(script, dev), B, beam, L, c).cpu()
         assert torch.equal(got, want), c
-        rerun = decode.decode_beam(StubStepper(script, dev, B), B, beam, L, c).cpu()
-        assert cut(rerun, sep) == cut(want, sep), c                                               # (behind [SEP] a beam's words are arbitrary ties)
+        rerun = decode.decode_beam(rerun_source(script, dev), B, beam, L, c).cpu()
+        assert torch.equal(rerun, want), c                                                        # one loop, one selection: the ties behind [SEP] too
         n = c.no_repeat_ngram_size
         assert all(repeated_ngrams(r, n, sep) == 0 for r in got) and not torch.equal(got, plain)
-    got = decode.decode_beam_cached(StubSession(script, dev), B, beam, L, decode.Constraints(min_length=6, suppress_tokens=(9, 7))).cpu()
+    got = decode.decode_beam(StubSession(script, dev), B, beam, L, decode.Constraints(min_length=6, suppress_tokens=(9, 7))).cpu()
     assert all(len(r) >= 6 for r in cut(got, sep)) and not (got == 7).any() and not (got == 9).any()
 
 
@@ -235,10 +243,49 @@ def test_scripted_length_penalty_at_the_final_pick(dev, sep):
     assert score(.36, 8, 0.0) > score(.3, 2, 0.0) and score(.36, 8, 1.0) > score(.3, 2, 1.0) and score(.36, 8, -1.0) < score(.3, 2, -1.0)
     for alpha, want in ((None, long_h), (0.0, long_h), (1.0, long_h), (-1.0, short_h)):
         c = None if alpha is None else decode.Constraints(length_penalty=alpha)
-        got = decode.decode_beam_cached(StubSession(script, dev), B, 3, L, c).cpu()
+        got = decode.decode_beam(StubSession(script, dev), B, 3, L, c).cpu()
         assert cut(got, sep) == [want] * B, (alpha, got)
-        got = decode.decode_beam(StubStepper(script, dev, B), B, 3, L, c).cpu()
+        got = decode.decode_beam(rerun_source(script, dev), B, 3, L, c).cpu()
         assert cut(got, sep) == [want] * B, (alpha, got)
+
+
+def test_rerun_source_reorders_its_host_state_by_parent(dev):
+    """decode._Rerun driven like decode_beam drives a source: the state the stepper is handed at step t == the words so far of a
+    [b, beam, L] history gathered along the chosen beams, read beam-major. The chosen beams are fixed, never the identity for a whole
+    step, and twice rows of a sample share a parent (once all three)."""
+    from valor_amd import decode
+    beam, R = 3, B * 3
+    gen = torch.Generator().manual_seed(7)
+    script = [torch.randn((R, V), generator=gen) for _ in range(L)]
+    stub = StubStepper(script, dev, B)
+    src = decode._Rerun(stub)
+    assert src.poll == 1 and src.m is stub.m
+    picks = ([1, 0, 2], [2, 0, 1], [0, 0, 1], [2, 1, 0], [1, 1, 1], [0, 2, 1])
+    words = torch.randint(3, V, (L - 1, B, beam), generator=gen)
+    base = torch.arange(B)
+    outputs = torch.zeros((B, beam, L), dtype=torch.int64)
+    z = src.step()
+    assert stub.states == [None] and same_bits(z.cpu(), script[0][:B])                            # the first step: b rows of [CLS]
+    for t in range(1, L):
+        # selection t - 1, as in decode_beam: the first one continues the single row of every sample
+        sel_beam = torch.zeros((B, beam), dtype=torch.long) if t == 1 else torch.tensor([picks[(t + s) % len(picks)] for s in range(B)])
+        if t > 1:
+            outputs = torch.gather(outputs, 1, sel_beam.unsqueeze(-1).expand(B, beam, L))
+        outputs[:, :, t - 1] = words[t - 1]
+        parent = (sel_beam.t() * B + base[None]).reshape(-1)
+        assert t == 1 or not torch.equal(parent, torch.arange(R))
+        z = src.step(words[t - 1].t().reshape(-1).to(dev), parent.to(dev))
+        want = outputs.transpose(0, 1).reshape(R, L)[:, :t]                                      # row k * B + s: the words of beam k of sample s
+        assert torch.equal(stub.states[t], want), t
+        assert same_bits(z.cpu(), script[t])
+    assert len(stub.states) == L
+    # without `parent` (greedy, sampling) the rows stay where they are
+    stub = StubStepper(script, dev, B)
+    src = decode._Rerun(stub)
+    src.step()
+    for t in range(1, 4):
+        src.step(words[t - 1, :, 0].to(dev))
+    assert torch.equal(stub.states[3], words[:3, :, 0].t())
 
 
 # ------------------------------------------------------------------------------------------------ the small synthetic model
@@ -388,6 +435,29 @@ def test_rerun_path_with_a_block_per_modality_equals_a_host_law_loop(dev):
         for kw in MODES[1:]:
             out = _cap(m, batch, ("tva",), **kw, **ctl)["generated_sequences_t_va"]
             check_rows(out, 2, 5, (100, 103))
+    finally:
+        decode.release_sessions(m)
+
+
+def test_lm_greedy_is_the_same_through_both_sources(dev):
+    """caption_type 'lm' (one new row per step, no [MASK]): decode_greedy over the session and over the re-run source, token for token"""
+    from valor_amd import decode
+    m, spec = _model(dev, caption_type="lm")
+    batch = _batch(spec)
+    c = decode.Constraints(no_repeat_ngram_size=2, min_length=4)
+    try:
+        with torch.no_grad():
+            m.eval()
+            b, kv_layers, ranges = decode.encode_for_generation(m, batch, ["tva"])
+            sess = decode.session(m, b, 1, 0, 10, kv_layers)
+            assert sess.J == 1 and sess.poll == 8
+            sess.begin_batch(kv_layers)
+            for con in (None, c):
+                sess.begin_group(ranges["tva"], None)
+                cached = decode.decode_greedy(sess, b, 10, con)[0].cpu()
+                rerun = decode.decode_greedy(decode._Rerun(decode.stepper(m, "tva", b, kv_layers, ranges)), b, 10, con)[0].cpu()
+                assert torch.equal(cached, rerun), (con, cached, rerun)
+            check_rows(cached, 2, 4)
     finally:
         decode.release_sessions(m)
 

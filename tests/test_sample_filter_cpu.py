@@ -90,8 +90,7 @@ def test_generate_cap_argument_errors():
 
 def test_sampling_signatures_keep_their_defaults():
     import inspect
-    for fn in (decode.decode_sample_cached, decode.decode_sample):
-        assert inspect.signature(fn).parameters["sampling"].default is None
+    assert inspect.signature(decode.decode_sample).parameters["sampling"].default is None
     p = inspect.signature(decode.generate_cap).parameters
     assert p["temperature"].default is None and p["top_k"].default is None and p["top_p"].default is None
     assert p["num_return_sequences"].default == 1

@@ -2,7 +2,7 @@
 8 frames + 2 audio slices, group 'tva', greedy and beam-3 decoding to max_generation_len (random weights never emit [SEP]: every row runs
 the full length). Prints where the time goes: the encoders + K|V projections (once per clip) and the decoding loop (re-runs the text rows
 each step like the reference with VALOR_KV_CACHE=0; two rows per sequence against the K|V cache otherwise, decode.py).
-Mode 'sample' is the sampled decode of SCST (decode.decode_sample_cached); mode 'scst' times one self-critical training step at the
+Mode 'sample' is the sampled decode of SCST (decode.decode_sample on the session); mode 'scst' times one self-critical training step at the
 caption-msrvtt shape (task cap%tva%tv, a CaptionScorer of 20 synthetic references per clip) split into greedy baseline, encoders +
 sampled decoding, scoring and the loss pass (forward + backward), and one scorer call of B hypotheses. GEN_SCORER=host (default) scores
 with scst.CaptionScorer on the host, GEN_SCORER=device with scst.DeviceCaptionScorer (valor_caption_reward: one launch for the sample and

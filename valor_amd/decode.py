@@ -16,9 +16,17 @@ decoder has cross-attention, pretrain.py:890-896, bert.py:848-850, and broken be
     VALOR_KV_CACHE=0 selects the re-run-everything path (`_Stepper`, also the teacher-forced logits the parity tests use);
     VALOR_DECODE_GRAPH=0 runs the cached step eagerly.
 
-Beam rows are kept in the reference's (sample, beam) order on the host side; the decoder sees them beam-major (row = beam * b + sample)
-so that a row's cross-attention K|V is row % b -- the kv_bmod addressing the training passes use -- instead of beam copies of K|V
-(pretrain.py:1133-1139 expands video_input / audio_input beam_size times).
+There is ONE greedy, ONE beam and ONE sampled loop (`decode_greedy`, `decode_beam`, `decode_sample`), written against a step source:
+  source.m                            the model (its .device)
+  source.step(tok=None, parent=None)  fp32 logits [>= rows, V] with unit column stride of the step that follows the tokens `tok` (int64
+                                      [rows] on the device; None: [CLS], the first step) on the sequences `parent` (int64 [rows]: beam
+                                      search, row r continues row parent[r] of the previous step)
+  source.poll                         every how many steps a loop asks (one host synchronisation) whether every row has ended
+The sources are `DecodeSession` (poll 8: nothing else of a step waits for the device) and `_Rerun`, which keeps the tokens so far on the
+host for a `_Stepper` (poll 1: it synchronises every step to fetch the tokens, and a step it need not run is a whole decoder).
+Rows are beam-major everywhere (row = beam * b + sample), so that a row's cross-attention K|V is row % b -- the kv_bmod addressing the
+training passes use -- instead of beam copies of K|V (pretrain.py:1133-1139 expands video_input / audio_input beam_size times); the
+reference's (sample, beam) order is only that of the loop's own [b, beam, ...] bookkeeping.
 
 Generation controls (`Constraints`: repetition penalty, no repeated n-gram, minimum length, suppressed tokens) are one
 valor_logits_constrain launch per step on the step's logits, between the step and the selection, in every loop below; with the controls
@@ -26,7 +34,7 @@ off no launch is issued. `constrain_rows_host` restates the kernel's law on the 
 
 Closed answer sets (`AnswerSet`: a token trie of candidates, shared or one per sample): `candidates=` makes every loop decode INSIDE the
 set with one valor_trie_constrain launch per step in the same place (`trie_rows_host` is its law on the host), and `score_candidates`
-returns the exact sequence log-probability of every candidate by forced decoding on a session of its own.
+returns the exact sequence log-probability of every candidate by forced decoding through the same step sources.
 
 Everything here is inference: torch.no_grad, dropout off regardless of model.training (the reference calls it under model.eval())."""
 import contextlib
@@ -54,7 +62,7 @@ class _Stepper:
         self.blocks = isinstance(kv_layers, _BlockKV)
 
     def logits(self, state, rows):
-        """state: host int64 [rows, t] in (sample, beam) order (None at t = 0) -> fp32 logits [rows, vocab] of the last text position:
+        """state: host int64 [rows, t], rows beam-major (None at t = 0) -> fp32 logits [rows, vocab] of the last text position:
         the appended [MASK] (caption_type 'unimlm') or the last token itself ('lm': [CLS] + the tokens so far, pretrain.py:1038-1040).
         full_masker does not reach this path in the reference either (forward_cap_single's generation branch, :878-900, drops the flag)."""
         m, b = self.m, self.b
@@ -65,9 +73,6 @@ class _Stepper:
         else:
             mask_col = torch.full((rows, 1), MASK, dtype=torch.long)
             txt = torch.cat((bos, mask_col), dim=1) if state is None else torch.cat((bos, state, mask_col), dim=1)
-        if beam > 1:                                                # (sample, beam) -> beam-major
-            perm = torch.arange(rows).view(b, beam).t().reshape(-1)
-            txt = txt[perm]
         prompt = None
         if self.prompt is not None:                                 # one prompt row per SAMPLE (a QA question differs per clip): beam-major copies
             prompt = self.prompt.repeat(beam, 1) if beam > 1 else self.prompt
@@ -86,12 +91,25 @@ class _Stepper:
         idx = m._dev(torch.arange(rows, dtype=torch.int64) * Ttot + (T - 1))
         h = m.cls_transform(ops.gather_rows(hidden.reshape(-1, hidden.shape[-1]), idx))
         P = m.P
-        logits = K.gemm(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], bias=P["cls.decoder.bias"], out_dtype=torch.float32)
-        if beam > 1:                                                # back to (sample, beam)
-            inv = torch.empty_like(perm)
-            inv[perm] = torch.arange(rows)
-            logits = logits[m._dev(inv)]
-        return logits
+        return K.gemm(h, P["multimodal_encoder.embeddings.word_embeddings.weight"], bias=P["cls.decoder.bias"], out_dtype=torch.float32)
+
+
+class _Rerun:
+    """A _Stepper as a step source: the tokens so far live on the host, [rows, t] beam-major, and every step runs all of them again.
+    The first step runs b rows; a later one as many as `tok` has."""
+    poll = 1
+
+    def __init__(self, stepper):
+        self.m, self.stepper, self.state = stepper.m, stepper, None
+
+    def step(self, tok=None, parent=None):
+        if tok is None:
+            return self.stepper.logits(None, self.stepper.b)
+        if parent is not None and self.state is not None:          # every sequence continues the row `parent` of the previous step
+            self.state = self.state[parent.cpu()]
+        w = tok.cpu().unsqueeze(1)
+        self.state = w if self.state is None else torch.cat((self.state, w), dim=1)
+        return self.stepper.logits(self.state, tok.numel())
 
 
 NEG = -10000.0                           # the additive mask value of BertModel.forward (bert.py:885)
@@ -111,6 +129,7 @@ class DecodeSession:
     generated id 0), the step's attention mask opens slots <= P + t for the token row and P + t + 1 besides for the [MASK] row.
     Rows are beam-major (row = beam * b + sample); a beam step first moves every sequence's slots to the row that continues it
     (`parent`)."""
+    poll = 8                                           # a finished row keeps producing [SEP] (pretrain.py:1005-1010): asking late costs a few cheap steps
 
     def __init__(self, model, b, beam, P, max_len, kv_layers):
         m = self.m = model
@@ -314,8 +333,8 @@ def release_sessions(model):
     model.__dict__.pop("_decode_sessions", None)
 
 
-def row_lse(logits):
-    """log-sum-exp of fp32 rows (the cross-entropy kernel's) and the zero-padded buffer the rows sit in"""
+def _xent_rows(logits, labels=None):
+    """valor_xent_fwd on fp32 rows -> (row loss lse(z) - z[label], lse, the zero-padded buffer the rows sit in); labels None: column 0"""
     n, V = logits.shape
     Vpad = (V + 31) // 32 * 32
     if logits.stride() == (Vpad, 1) and logits.data_ptr() % 16 == 0:       # the decoding session's rows already sit in a zero-padded buffer
@@ -324,10 +343,16 @@ def row_lse(logits):
         buf = torch.zeros((n, Vpad), dtype=torch.float32, device=logits.device)
         buf[:, :V] = logits
     lse = torch.empty(n, dtype=torch.float32, device=logits.device)
-    rows = torch.empty(n, dtype=torch.float32, device=logits.device)
-    labels = torch.zeros(n, dtype=torch.int64, device=logits.device)
-    lib.call("valor_xent_fwd", _st(), lib.DT_F32, buf.data_ptr(), labels.data_ptr(), rows.data_ptr(), lse.data_ptr(), n, V, Vpad)
-    return lse, buf
+    loss = torch.empty(n, dtype=torch.float32, device=logits.device)
+    if labels is None:
+        labels = torch.zeros(n, dtype=torch.int64, device=logits.device)
+    lib.call("valor_xent_fwd", _st(), lib.DT_F32, buf.data_ptr(), labels.data_ptr(), loss.data_ptr(), lse.data_ptr(), n, V, Vpad)
+    return loss, lse, buf
+
+
+def row_lse(logits):
+    """log-sum-exp of fp32 rows (the cross-entropy kernel's) and the zero-padded buffer the rows sit in"""
+    return _xent_rows(logits)[1:]
 
 
 def log_softmax_rows(logits):
@@ -458,7 +483,7 @@ class _Constrainer:
         self.penalty, self.inv_penalty = c.penalty, c.inv_penalty
         self.suppress = torch.tensor(c.suppress_tokens, dtype=torch.int32, device=dev) if c.suppress_tokens else None
 
-    def __call__(self, logits, hist, t, active, b=None, hist_stride_s=None, hist_stride_k=0, group=1):
+    def __call__(self, logits, hist, t, active, b=None, hist_stride_s=None, hist_stride_k=0):
         c = self.c
         return K.logits_constrain(logits, hist if t > 0 else None, t, EOS, self.penalty, self.inv_penalty, c.no_repeat_ngram_size, c.min_length,
                                   self.suppress, active, b, hist_stride_s, hist_stride_k)
@@ -586,7 +611,7 @@ class AnswerSet:
 
     def with_roots(self, samples):
         """the same trie read by other rows: row-sample i of the result is sample samples[i] of this per-sample set (several question
-        rows per clip, num_return_sequences, the (sample, beam) rows of the re-run beam search)"""
+        rows per clip, num_return_sequences)"""
         import copy
         out = copy.copy(self)
         idx = torch.as_tensor(samples, dtype=torch.long)
@@ -676,19 +701,13 @@ def trie_rows_host(logits, hist, t, answer_set, eos, b, active=None):
 
 
 class _TrieConstrainer:
-    """the per-step valor_trie_constrain launch of a decode loop inside an AnswerSet: _Constrainer's call. group: the rows of one sample
-    are `group` CONSECUTIVE rows (the (sample, beam) order of the re-run beam search): a per-sample set is re-rooted per row."""
+    """the per-step valor_trie_constrain launch of a decode loop inside an AnswerSet: _Constrainer's call"""
 
     def __init__(self, answer_set, dev):
-        self.a, self.dev, self._grouped = answer_set, dev, {}
+        self.trie = answer_set.device(dev)
 
-    def __call__(self, logits, hist, t, active, b=None, hist_stride_s=None, hist_stride_k=0, group=1):
-        a = self.a
-        if group > 1 and a.per_sample:
-            a = self._grouped.get(group)
-            if a is None:
-                a = self._grouped[group] = self.a.with_roots([i for i in range(self.a.n_roots) for _ in range(group)])
-        return K.trie_constrain(logits, hist if t > 0 else None, t, EOS, a.device(self.dev), active, b, hist_stride_s, hist_stride_k)
+    def __call__(self, logits, hist, t, active, b=None, hist_stride_s=None, hist_stride_k=0):
+        return K.trie_constrain(logits, hist if t > 0 else None, t, EOS, self.trie, active, b, hist_stride_s, hist_stride_k)
 
 
 def _check_candidates(model, candidates, constraints, max_len):
@@ -717,104 +736,47 @@ def _final_beam_order(seq_logprob, outputs, max_len, constraints):
     return torch.sort(score, dim=1, descending=True, stable=True)[1].unsqueeze(-1)
 
 
-def decode_greedy(step, b, max_len, constraints=None, candidates=None):
-    """VALOR.decode_greedy, model/pretrain.py:988-1028, mode 'greedy' (its logprobs are zeros in that mode)."""
-    dev = step.m.device
-    sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
-    logprobs = torch.zeros((b, max_len), device=dev)
-    unfinished = torch.ones(b, dtype=torch.bool, device=dev)
-    state = None
-    con = _constrainer(constraints, dev, candidates)
-    for t in range(max_len):
-        logits = step.logits(state, b)
-        if con is not None:
-            logits = con(logits.contiguous(), sents, t, unfinished)
-        wt = logits.max(1)[1].view(-1).long()
-        unfinished = unfinished & (wt != EOS)
-        wt = torch.where(unfinished, wt, torch.full_like(wt, EOS))
-        sents[:, t] = wt
-        w_host = wt.cpu().unsqueeze(1)                              # the next step's token ids are built on the host
-        state = w_host if state is None else torch.cat((state, w_host), dim=1)
-        if not bool(unfinished.any()):
-            break
-    return sents, logprobs
+def _all_ended(source, t, max_len, unfinished):
+    """asked every source.poll steps (a host synchronisation), never after the last step: has every row produced its [SEP]?"""
+    return (t + 1) % source.poll == 0 and t + 1 < max_len and not bool(unfinished.any())
 
 
-def decode_beam(step, b, beam, max_len, constraints=None, candidates=None):
-    """VALOR.decode_beam / select / _adjust_tensor, model/pretrain.py:1054-1180. A beam that produced [SEP] keeps its score for every
-    candidate word (:1091-1094), so its V candidates tie and the reference's sort picks among them arbitrarily: sequences are only
-    defined up to that choice once a beam has ended (the tokens behind [SEP] are dropped by decode_sequence :146-164 anyway).
-    constraints: the rows here are (sample, beam) ordered, and so is the history the launch reads; an ended beam's row is left alone.
-    candidates: an AnswerSet -- the open rows are masked to the set's continuations; the log-sum-exp of a row is taken BEFORE the mask, so
-    a hypothesis keeps the model's sequence log-probability (score_candidates' law) and the candidates are ranked by it."""
-    dev = step.m.device
-    seq_logprob = torch.zeros((b, 1, 1), device=dev)
-    seq_mask = torch.ones((b, beam, 1), device=dev)
-    outputs, selected_words, state = [], None, None
-    con = _constrainer(constraints, dev, candidates)
-    for t in range(max_len):
-        cur = 1 if t == 0 else beam
-        logits = step.logits(state, b * cur)
-        lse_pre = row_lse(logits)[0] if candidates is not None else None      # an answer set masks the row, the scores stay the model's logP
-        if con is not None:
-            active = None if t == 0 else ((seq_mask[:, :, 0] != 0) & (selected_words.view(b, cur) != EOS)).reshape(-1)
-            logits = con(logits.contiguous(), None if t == 0 else torch.cat(outputs, -1).reshape(b * cur, t), t, active, group=cur)
-        word_logprob = (log_softmax_rows(logits) if lse_pre is None else logits - lse_pre[:, None]).view(b, cur, -1)
-        cand = seq_logprob + word_logprob
-        if t > 0:
-            mask = (selected_words.view(b, cur) != EOS).float().unsqueeze(-1)
-            seq_mask = seq_mask * mask
-            cand = seq_mask * cand + seq_logprob.expand_as(cand) * (1 - seq_mask)
-        V = cand.shape[-1]
-        sel_logprob, sel_idx = torch.topk(cand.view(b, -1), beam, dim=-1, largest=True, sorted=True)     # select :1156-1159
-        sel_beam = sel_idx // V
-        selected_words = sel_idx - sel_beam * V
-        seq_logprob = sel_logprob.unsqueeze(-1)
-        seq_mask = torch.gather(seq_mask, 1, sel_beam.unsqueeze(-1))
-        outputs = [torch.gather(o, 1, sel_beam.unsqueeze(-1)) for o in outputs]
-        outputs.append(selected_words.unsqueeze(-1))
-        w_host, beam_host = selected_words.reshape(-1, 1).cpu(), sel_beam.cpu()
-        if state is not None:
-            state = torch.gather(state.view(b, beam, -1), 1, beam_host.unsqueeze(-1).expand(b, beam, state.shape[1])).reshape(b * beam, -1)
-            state = torch.cat((state, w_host), dim=1)
-        else:
-            state = w_host
-    outputs = torch.cat(outputs, -1)
-    sort_idx = _final_beam_order(seq_logprob, outputs, max_len, constraints)
-    outputs = torch.gather(outputs, 1, sort_idx.expand(b, beam, max_len))
-    return outputs.contiguous()[:, 0]
-
-
-def decode_greedy_cached(sess, b, max_len, constraints=None, candidates=None):
-    """decode_greedy on a DecodeSession: the tokens stay on the device (the next step's input is this step's argmax); whether every row
-    has ended is asked every eighth step (a finished row keeps producing [SEP], pretrain.py:1005-1010: the result is the same).
+def decode_greedy(source, b, max_len, constraints=None, candidates=None):
+    """VALOR.decode_greedy, model/pretrain.py:988-1028, mode 'greedy' (its logprobs are zeros in that mode) over a step source: the
+    tokens stay on the device (the next step's input is this step's argmax); a finished row keeps producing [SEP] (:1005-1010), so
+    the result does not depend on the step at which the loop leaves.
     constraints: one valor_logits_constrain launch on the step's logits, outside the captured step (history: sents, active: unfinished)."""
-    dev = sess.m.device
+    dev = source.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
     logprobs = torch.zeros((b, max_len), device=dev)
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     tok = None
     con = _constrainer(constraints, dev, candidates)
     for t in range(max_len):
-        logits = sess.step(tok)
+        logits = source.step(tok)
         if con is not None:
             con(logits, sents, t, unfinished)
         wt = logits.max(1)[1]
         unfinished = unfinished & (wt != EOS)
         tok = torch.where(unfinished, wt, EOS)
         sents[:, t] = tok
-        if t % 8 == 7 and t + 1 < max_len and not bool(unfinished.any()):
+        if _all_ended(source, t, max_len, unfinished):
             break
     return sents, logprobs
 
 
-def decode_beam_cached(sess, b, beam, max_len, constraints=None, candidates=None):
-    """decode_beam on a DecodeSession (rows beam-major): the selection arithmetic of pretrain.py:1054-1180 on the device, the chosen
-    beams as the next step's `parent` rows. Step 0 runs `beam` identical copies of every sequence and reads the first.
+def decode_beam(source, b, beam, max_len, constraints=None, candidates=None):
+    """VALOR.decode_beam / select / _adjust_tensor, model/pretrain.py:1054-1180, over a step source (rows beam-major): the selection
+    arithmetic on the device, the chosen beams as the next step's `parent` rows. Step 0 reads the first b rows (a session runs `beam`
+    identical copies of every sequence). A beam that produced [SEP] keeps its score for every candidate word (:1091-1094), so its V
+    candidates tie and the reference's sort picks among them arbitrarily: sequences are only defined up to that choice once a beam has
+    ended (the tokens behind [SEP] are dropped by decode_sequence :146-164 anyway).
     constraints: one valor_logits_constrain launch per step on the open beams' rows (the history follows the beams: `outputs`), and
-    length_penalty at the final pick; in-search ranking stays the reference's. candidates: as in decode_beam (one valor_trie_constrain
-    launch per step; the rows' log-sum-exp is the cross-entropy kernel's on the unmasked row, which beam_select takes in any case)."""
-    dev = sess.m.device
+    length_penalty at the final pick; in-search ranking stays the reference's. candidates: an AnswerSet -- the open rows are masked to
+    the set's continuations (one valor_trie_constrain launch per step); the log-sum-exp of a row is the cross-entropy kernel's on the
+    row BEFORE the mask, so a hypothesis keeps the model's sequence log-probability (score_candidates' law) and the candidates are
+    ranked by it."""
+    dev = source.m.device
     seq_logprob = torch.zeros((b, 1, 1), device=dev)
     seq_mask = torch.ones((b, beam, 1), device=dev)
     base = torch.arange(b, device=dev)
@@ -825,7 +787,7 @@ def decode_beam_cached(sess, b, beam, max_len, constraints=None, candidates=None
     open_rows = torch.empty((beam, b), dtype=torch.bool, device=dev) if con is not None else None
     for t in range(max_len):
         cur = 1 if t == 0 else beam
-        logits = sess.step(tok, parent)
+        logits = source.step(tok, parent)
         V = logits.shape[-1]
         if t > 0:
             mask = (selected_words.view(b, cur) != EOS).float().unsqueeze(-1)
@@ -993,55 +955,33 @@ def _draw_step(logits, stream, sampling, unfinished, tok, sents_t, logprobs_t):
 
 
 def _skip_windows(stream, candidates, R, V, steps):
-    """inside an answer set every row ends after a few tokens and the two sampled loops leave at different steps (every eighth / at
-    once): the call still consumes its max_len counter windows, so the next group draws the same numbers on either route. Without an
-    answer set nothing is skipped: the stream is the parent's."""
+    """inside an answer set every row ends after a few tokens and the two step sources leave the sampled loop at different steps
+    (`poll`): the call still consumes its max_len counter windows, so the next group draws the same numbers on either source. Without
+    an answer set nothing is skipped: the stream stays what it was before answer sets existed."""
     if candidates is not None:
         for _ in range(steps):
             stream.take(R, V)
 
 
-def decode_sample_cached(sess, b, max_len, stream, sampling=None, constraints=None, candidates=None):
-    """VALOR.decode_greedy mode 'sample' (pretrain.py:1005-1020) on a DecodeSession: one step, then one valor_sample_tokens launch that draws
-    from softmax(logits), writes the logP of the draw and does the [SEP] bookkeeping. The tokens stay on the device; whether every row has
-    ended is asked every eighth step, as in decode_greedy_cached. -> (sents int64 [b, max_len], logprobs fp32 [b, max_len]); after a row's
-    first [SEP] its tokens are [SEP] and its logprobs 0. sampling: a Sampling (None or all off: the unmodified softmax); the sampler
+def decode_sample(source, b, max_len, stream, sampling=None, constraints=None, candidates=None):
+    """VALOR.decode_greedy mode 'sample' (pretrain.py:1005-1020) over a step source: one step, then one valor_sample_tokens launch that
+    draws from softmax(logits), writes the logP of the draw and does the [SEP] bookkeeping. The tokens stay on the device, as in
+    decode_greedy. -> (sents int64 [b, max_len], logprobs fp32 [b, max_len]); after a row's first [SEP] its tokens are [SEP] and its
+    logprobs 0. sampling: a Sampling (None or all off: the unmodified softmax); the sampler
     launch sits outside the captured step and takes its parameters by value, so a kept session serves any setting. constraints come
     first (valor_logits_constrain on the step's logits): temperature / top-k / top-p and the logP see what the constraints left."""
-    dev = sess.m.device
+    dev = source.m.device
     sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
     logprobs = torch.zeros((b, max_len), device=dev)
     unfinished = torch.ones(b, dtype=torch.bool, device=dev)
     tok = torch.empty(b, dtype=torch.long, device=dev)
     con = _constrainer(constraints, dev, candidates)
     for t in range(max_len):
-        logits = sess.step(None if t == 0 else tok)
+        logits = source.step(None if t == 0 else tok)
         if con is not None:
             con(logits, sents, t, unfinished)
         _draw_step(logits, stream, sampling, unfinished, tok, sents[:, t], logprobs[:, t])
-        if t % 8 == 7 and t + 1 < max_len and not bool(unfinished.any()):
-            break
-    _skip_windows(stream, candidates, b, logits.shape[1], max_len - t - 1)
-    return sents, logprobs
-
-
-def decode_sample(step, b, max_len, stream, sampling=None, constraints=None, candidates=None):
-    """decode_sample_cached on the re-run path (_Stepper: VALOR_KV_CACHE=0, a cross-attention block per modality); the same draws"""
-    dev = step.m.device
-    sents = torch.full((b, max_len), EOS, dtype=torch.long, device=dev)
-    logprobs = torch.zeros((b, max_len), device=dev)
-    unfinished = torch.ones(b, dtype=torch.bool, device=dev)
-    tok = torch.empty(b, dtype=torch.long, device=dev)
-    state = None
-    con = _constrainer(constraints, dev, candidates)
-    for t in range(max_len):
-        logits = step.logits(state, b).contiguous()
-        if con is not None:
-            con(logits, sents, t, unfinished)
-        _draw_step(logits, stream, sampling, unfinished, tok, sents[:, t], logprobs[:, t])
-        w_host = tok.cpu().unsqueeze(1)
-        state = w_host if state is None else torch.cat((state, w_host), dim=1)
-        if not bool(unfinished.any()):
+        if _all_ended(source, t, max_len, unfinished):
             break
     _skip_windows(stream, candidates, b, logits.shape[1], max_len - t - 1)
     return sents, logprobs
@@ -1052,31 +992,45 @@ def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, s
     stream: a SampleStream (after begin_call) -> sampled decoding (beam 1) under `sampling` (a Sampling or None). constraints: a
     Constraints or None, for every mode; candidates: an AnswerSet fitted to the b rows (for_rows) or None"""
     c, a = constraints, candidates
-    if isinstance(prompt, str):
-        prompt = model.get_task_prompt(PROMPTS[prompt], b) if model.use_task_prompt else None
+    prompt = _prompt_rows(model, prompt, b)
     if stream is not None:
         beam = 1
     out = {}
-    sess = None
-    if kv_cache_enabled() and not isinstance(kv_layers, _BlockKV):      # (a block per modality, bert.py:459-496: the re-run path)
-        sess = session(model, b, beam, 0 if prompt is None else prompt.shape[1], max_len, kv_layers)
-        sess.begin_batch(kv_layers)
+    sess = _batch_session(model, b, beam, kv_layers, prompt, max_len, session)
     for g in ("tv", "tva", "ta"):
         if g not in groups:
             continue
-        if sess is not None:
-            sess.begin_group(ranges[g] if kv_layers is not None else None, prompt)
-            if stream is not None:
-                out[g] = decode_sample_cached(sess, b, max_len, stream, sampling, c, a)
-            else:
-                out[g] = (decode_beam_cached(sess, b, beam, max_len, c, a), None) if beam > 1 else decode_greedy_cached(sess, b, max_len, c, a)
+        source = _group_source(sess, model, g, b, kv_layers, ranges, prompt)
+        if stream is not None:
+            out[g] = decode_sample(source, b, max_len, stream, sampling, c, a)
         else:
-            step = _Stepper(model, g, kv_layers, ranges, prompt, b)
-            if stream is not None:
-                out[g] = decode_sample(step, b, max_len, stream, sampling, c, a)
-            else:
-                out[g] = (decode_beam(step, b, beam, max_len, c, a), None) if beam > 1 else decode_greedy(step, b, max_len, c, a)
+            out[g] = (decode_beam(source, b, beam, max_len, c, a), None) if beam > 1 else decode_greedy(source, b, max_len, c, a)
     return out
+
+
+def _prompt_rows(model, prompt, b):
+    """prompt: 'caption' (-> the task prompt's b rows when the model uses one, else None) or host rows [b, L] as they are (QA: the questions)"""
+    if isinstance(prompt, str):
+        return model.get_task_prompt(PROMPTS[prompt], b) if model.use_task_prompt else None
+    return prompt
+
+
+def _batch_session(model, b, beam, kv_layers, prompt, max_len, make):
+    """the K|V-cached session of a batch, holding the clips' K|V (make: `session`, the model's kept one of the geometry, or DecodeSession,
+    the caller's own), or None: VALOR_KV_CACHE=0 and a cross-attention block per modality (bert.py:459-496) take the re-run path"""
+    if not kv_cache_enabled() or isinstance(kv_layers, _BlockKV):
+        return None
+    sess = make(model, b, beam, 0 if prompt is None else prompt.shape[1], max_len, kv_layers)
+    sess.begin_batch(kv_layers)
+    return sess
+
+
+def _group_source(sess, model, g, b, kv_layers, ranges, prompt):
+    """the step source of query group g at its first step: the batch's session, reset, or a re-run source"""
+    if sess is None:
+        return _Rerun(_Stepper(model, g, kv_layers, ranges, prompt, b))
+    sess.begin_group(ranges[g] if kv_layers is not None else None, prompt)
+    return sess
 
 
 def encode_for_generation(model, batch, groups):
@@ -1093,9 +1047,7 @@ def encode_for_generation(model, batch, groups):
 def stepper(model, group, b, kv_layers, ranges, prompt="caption"):
     """the per-step logits function of one query group ('tv' | 'tva' | 'ta'): stepper(...).logits(tokens so far or None, rows).
     prompt: 'caption' (the task prompt when the model uses one) or a host [b, L] tensor of prompt rows (QA: the questions)."""
-    if isinstance(prompt, str):
-        prompt = model.get_task_prompt(PROMPTS[prompt], b) if model.use_task_prompt else None
-    return _Stepper(model, group, kv_layers, ranges, prompt, b)
+    return _Stepper(model, group, kv_layers, ranges, _prompt_rows(model, prompt, b), b)
 
 
 def _sample_stream(model, seed):
@@ -1128,6 +1080,34 @@ def _sampling_of(model, temperature, top_k, top_p):
                     _opt(model.opts, "sample_top_p", 1.0) if top_p is None else top_p)
 
 
+def _resolve(who, model, mode, beam, max_generation_len, sample_only, controls, candidates):
+    """what a generate_* call makes of its arguments -> (Sampling | None, Constraints, beam width, max_len, AnswerSet | None). who: the
+    caller's name, for the error texts; beam: the width when mode is None; sample_only: {name: value} of the arguments that need
+    mode='sample' (None: not given), temperature / top_k / top_p first; controls: the five arguments of _constraints_of"""
+    if mode not in (None, "greedy", "sample"):
+        raise ValueError(f"{who}: mode {mode!r} (None, 'greedy' or 'sample')")
+    sampling = None
+    if mode == "sample":
+        sampling = _sampling_of(model, sample_only["temperature"], sample_only["top_k"], sample_only["top_p"])
+    elif any(v is not None for v in sample_only.values()):
+        raise ValueError(f"{who}: {' / '.join(sample_only)} need mode='sample'")
+    constraints = _constraints_of(model, *controls)
+    max_len = model.max_generation_len if max_generation_len is None else max_generation_len
+    return sampling, constraints, beam if mode is None else 1, max_len, _check_candidates(model, candidates, constraints, max_len)
+
+
+def _named(name, res, logprobs):
+    """the result of a generate_* call from _decode_groups': name + 't_v' | 't_va' | 't_a' per group, and with `logprobs` 'logprobs_*'
+    beside them where the decoder gave some (beam search gives none)"""
+    out = {}
+    for g, (seq, lp) in res.items():
+        key = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]
+        out[name + key] = seq
+        if logprobs and lp is not None:
+            out["logprobs_" + key] = lp
+    return out
+
+
 @torch.no_grad()
 def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None, top_k=None,
                  top_p=None, num_return_sequences=1, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None,
@@ -1147,22 +1127,13 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
     launch per step): each output row is one of the candidates, AnswerSet.index_of names it; a per-sample set has one entry per clip
     (num_return_sequences rows read their clip's entry) or one per output row. It excludes the logits rules above (ValueError);
     length_penalty stays. In sample mode the logprobs are those of the masked row: a column outside the set has mass exactly 0."""
-    if mode not in (None, "greedy", "sample"):
-        raise ValueError(f"generate_cap: mode {mode!r} (None, 'greedy' or 'sample')")
     n = int(num_return_sequences)
     if n != num_return_sequences or n < 1:
         raise ValueError(f"generate_cap: num_return_sequences {num_return_sequences!r} must be an integer >= 1")
-    sampling = None
-    if mode == "sample":
-        sampling = _sampling_of(model, temperature, top_k, top_p)
-    elif temperature is not None or top_k is not None or top_p is not None or n != 1:
-        raise ValueError("generate_cap: temperature / top_k / top_p / num_return_sequences need mode='sample'")
-    constraints = _constraints_of(model, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty)
-    beam = model.beam_size if beam_size is None else beam_size
-    if mode is not None:
-        beam = 1
-    max_len = model.max_generation_len if max_generation_len is None else max_generation_len
-    aset = _check_candidates(model, candidates, constraints, max_len)
+    sampling, constraints, beam, max_len, aset = _resolve(
+        "generate_cap", model, mode, model.beam_size if beam_size is None else beam_size, max_generation_len,
+        dict(temperature=temperature, top_k=top_k, top_p=top_p, num_return_sequences=None if n == 1 else n),
+        (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty), candidates)
     was_training = model.training
     model.eval()
     try:
@@ -1172,15 +1143,9 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
             b *= n
         if aset is not None:
             aset = aset.for_rows(b)
-        out = {}
         stream = _sample_stream(model, seed) if mode == "sample" else None
-        for g, (seq, lp) in _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, stream, sampling,
-                                                constraints, aset).items():
-            key = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]
-            out["generated_sequences_" + key] = seq
-            if lp is not None:
-                out["logprobs_" + key] = lp
-        return out
+        res = _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, stream, sampling, constraints, aset)
+        return _named("generated_sequences_", res, True)
     finally:
         model.train(was_training)
 
@@ -1198,22 +1163,13 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
     gathered per question (valor_gather_rows), so the projection GEMMs do not grow with the question count.
     candidates: generate_cap's -- closed-vocabulary QA: the answer is always one of the candidates (AnswerSet.index_of). A per-sample set
     has one entry per question row, or one per clip (its sample_num question rows read it)."""
-    if mode not in (None, "greedy", "sample"):
-        raise ValueError(f"generate_qa: mode {mode!r} (None, 'greedy' or 'sample')")
-    sampling = None
-    if mode == "sample":
-        sampling = _sampling_of(model, temperature, top_k, top_p)
-    elif temperature is not None or top_k is not None or top_p is not None:
-        raise ValueError("generate_qa: temperature / top_k / top_p need mode='sample'")
-    constraints = _constraints_of(model, repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty)
-    sample_num = [int(n) for n in batch.get("sample_num", [])]
     # the reference switches to beam search when beam_size_qa > 1 but decode_beam always searches with self.beam_size, task 'qa'
     # included (pretrain.py:1061): beam_size_qa is the switch, beam_size the width
-    beam = (model.beam_size if model.beam_size_qa > 1 else 1) if beam_size is None else beam_size
-    if mode is not None:
-        beam = 1
-    max_len = model.max_generation_len if max_generation_len is None else max_generation_len
-    aset = _check_candidates(model, candidates, constraints, max_len)
+    sampling, constraints, beam, max_len, aset = _resolve(
+        "generate_qa", model, mode, (model.beam_size if model.beam_size_qa > 1 else 1) if beam_size is None else beam_size,
+        max_generation_len, dict(temperature=temperature, top_k=top_k, top_p=top_p),
+        (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty), candidates)
+    sample_num = [int(n) for n in batch.get("sample_num", [])]
     was_training = model.training
     model.eval()
     try:
@@ -1228,28 +1184,14 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
             aset = aset.for_rows(b, sample_num if b != clips and aset.n_roots == clips else None)
         stream = _sample_stream(model, seed) if mode == "sample" else None
         res = _decode_groups(model, groups, b, kv_layers, ranges, prompt_cpu, beam, max_len, stream, sampling, constraints, aset)
-        keys = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}
-        out = {"generated_answers_" + keys[g]: seq for g, (seq, _lp) in res.items()}
-        if mode == "sample":
-            out.update({"logprobs_" + keys[g]: lp for g, (_seq, lp) in res.items()})
-        return out
+        return _named("generated_answers_", res, mode == "sample")
     finally:
         model.train(was_training)
 
 
 def _forced_terms(logits, labels):
     """z[label] - lse(z) per fp32 row: the negated row loss of valor_xent_fwd (rows outside the session's padded buffer are copied once)"""
-    n, V = logits.shape
-    Vpad = (V + 31) // 32 * 32
-    if logits.stride() == (Vpad, 1) and logits.data_ptr() % 16 == 0:
-        buf = logits
-    else:
-        buf = torch.zeros((n, Vpad), dtype=torch.float32, device=logits.device)
-        buf[:, :V] = logits
-    lse = torch.empty(n, dtype=torch.float32, device=logits.device)
-    loss = torch.empty(n, dtype=torch.float32, device=logits.device)
-    lib.call("valor_xent_fwd", _st(), lib.DT_F32, buf.data_ptr(), labels.data_ptr(), loss.data_ptr(), lse.data_ptr(), n, V, Vpad)
-    return -loss
+    return -_xent_rows(logits, labels)[0]
 
 
 @torch.no_grad()
@@ -1290,17 +1232,13 @@ def score_candidates(model, batch, groups, candidates, prompt_cpu=None, max_rows
         rows = b * chunk
         kv_rep = _repeat_clips(model, kv_layers, b, chunk)
         if isinstance(prompt_cpu, str) or prompt_cpu is None:
-            prompt = model.get_task_prompt(PROMPTS[prompt_cpu or "caption"], rows) if model.use_task_prompt else None
+            prompt = _prompt_rows(model, prompt_cpu or "caption", rows)
         else:
             if prompt_cpu.shape[0] != b:
                 raise ValueError(f"score_candidates: {prompt_cpu.shape[0]} prompt rows for {b} samples")
             prompt = prompt_cpu.repeat_interleave(chunk, 0)
         T = a.max_len + 1
-        cached = kv_cache_enabled() and not isinstance(kv_layers, _BlockKV)
-        sess = None
-        if cached:
-            sess = DecodeSession(model, rows, 1, 0 if prompt is None else prompt.shape[1], T, kv_rep)
-            sess.begin_batch(kv_rep)
+        sess = _batch_session(model, rows, 1, kv_rep, prompt, T, DecodeSession)
         out = {g: torch.full((b, Cmax), -float("inf"), dtype=torch.float32, device=dev) for g in ("tv", "tva", "ta") if g in groups}
         for c0 in range(0, Cmax, chunk):
             forced = torch.full((rows, T), EOS, dtype=torch.long)
@@ -1316,15 +1254,9 @@ def score_candidates(model, batch, groups, candidates, prompt_cpu=None, max_rows
             forced_d, length_d, real_d = model._dev(forced), model._dev(length), model._dev(real)
             for g in out:
                 score = torch.zeros(rows, dtype=torch.float32, device=dev)
-                if sess is not None:
-                    sess.begin_group(ranges[g] if kv_layers is not None else None, prompt)
-                else:
-                    step = _Stepper(model, g, kv_rep, ranges, prompt, rows)
+                source = _group_source(sess, model, g, rows, kv_rep, ranges, prompt)
                 for t in range(steps):
-                    if sess is not None:
-                        logits = sess.step(None if t == 0 else forced_d[:, t - 1].contiguous())
-                    else:
-                        logits = step.logits(None if t == 0 else forced[:, :t], rows)
+                    logits = source.step(None if t == 0 else forced_d[:, t - 1].contiguous())
                     term = _forced_terms(logits, forced_d[:, t].contiguous())
                     score = torch.where(length_d >= t, score + term, score)
                 n = min(chunk, Cmax - c0)

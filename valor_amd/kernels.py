@@ -613,13 +613,8 @@ def sample_tokens_filtered(logits, seed, offset, eos, unfinished, tok, sents, lo
              logprobs.stride(0), None if kept is None else _ptr(kept), None if cut is None else _ptr(cut))
 
 
-def logits_constrain(logits, hist, t, eos, penalty=1.0, inv_penalty=1.0, ngram=0, min_len=0, suppress=None, active=None, b=None,
-                     hist_stride_s=None, hist_stride_k=0):
-    """generation controls of one decoding step, in place (valor_logits_constrain; the law: include/valor_hip.h): logits fp32 [R, V]
-    (row pitch = stride(0)); hist int64, unit stride along the tokens (None while t == 0); suppress int32 [n] or None; active bool /
-    uint8 [R] or None. Row r reads its t tokens at hist.data_ptr + (r % b) * hist_stride_s + (r / b) * hist_stride_k (elements). The
-    default is a row-ordered history [R, >= t]: b = R, hist_stride_s = hist.stride(0). Returns logits."""
-    _check_gpu(logits, hist, suppress, active)
+def _constrain_rows(logits, hist, t, active, b, hist_stride_s, hist_stride_k):
+    """the checks logits_constrain and trie_constrain share -> (R, V, t, b, hist_stride_s) as the launch takes them"""
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     R, V = logits.shape
     t = int(t)
@@ -634,10 +629,21 @@ def logits_constrain(logits, hist, t, eos, penalty=1.0, inv_penalty=1.0, ngram=0
     if hist is not None and t > 0 and R > 0:            # the furthest token a row reads lies inside the tensor's storage
         last = ((min(R, b) - 1) * int(hist_stride_s) + ((R - 1) // b) * int(hist_stride_k) + t - 1) if b >= 1 else 0
         assert hist.storage_offset() + last < hist.untyped_storage().nbytes() // 8
-    assert suppress is None or (suppress.dtype == torch.int32 and suppress.dim() == 1 and suppress.is_contiguous())
     assert active is None or (active.dtype in (torch.bool, torch.uint8) and active.is_contiguous() and active.numel() == R)
+    return R, V, t, b, int(hist_stride_s or 0)
+
+
+def logits_constrain(logits, hist, t, eos, penalty=1.0, inv_penalty=1.0, ngram=0, min_len=0, suppress=None, active=None, b=None,
+                     hist_stride_s=None, hist_stride_k=0):
+    """generation controls of one decoding step, in place (valor_logits_constrain; the law: include/valor_hip.h): logits fp32 [R, V]
+    (row pitch = stride(0)); hist int64, unit stride along the tokens (None while t == 0); suppress int32 [n] or None; active bool /
+    uint8 [R] or None. Row r reads its t tokens at hist.data_ptr + (r % b) * hist_stride_s + (r / b) * hist_stride_k (elements). The
+    default is a row-ordered history [R, >= t]: b = R, hist_stride_s = hist.stride(0). Returns logits."""
+    _check_gpu(logits, hist, suppress, active)
+    R, V, t, b, hist_stride_s = _constrain_rows(logits, hist, t, active, b, hist_stride_s, hist_stride_k)
+    assert suppress is None or (suppress.dtype == torch.int32 and suppress.dim() == 1 and suppress.is_contiguous())
     lib.call("valor_logits_constrain", _stream(), _ptr(logits), logits.stride(0), R, V, None if hist is None else _ptr(hist),
-             int(hist_stride_s or 0), int(hist_stride_k), b, t, int(eos), float(penalty), float(inv_penalty),
+             hist_stride_s, int(hist_stride_k), b, t, int(eos), float(penalty), float(inv_penalty),
              int(ngram), int(min_len), None if suppress is None else _ptr(suppress), 0 if suppress is None else suppress.numel(),
              None if active is None else _ptr(active))
     return logits
@@ -649,28 +655,14 @@ def trie_constrain(logits, hist, t, eos, trie, active=None, b=None, hist_stride_
     form of a decode.AnswerSet (child_ptr / child_tok / child_node int32, terminal uint8, root int32 [1 | b]); active bool / uint8 [R]
     or None. Every column that continues no candidate becomes lib.TRIE_FLOOR. Returns logits."""
     _check_gpu(logits, hist, active, trie.child_ptr, trie.child_tok, trie.child_node, trie.terminal, trie.root)
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
-    R, V = logits.shape
-    t = int(t)
-    if hist is not None:
-        assert hist.dtype == torch.int64 and hist.stride(-1) == 1 and hist.shape[-1] >= t
-        if hist_stride_s is None:
-            assert hist.dim() == 2 and hist.shape[0] >= R
-            hist_stride_s = hist.stride(0)
-    else:
-        assert t == 0
-    b = R if b is None else int(b)
-    if hist is not None and t > 0 and R > 0:            # the furthest token a row reads lies inside the tensor's storage
-        last = ((min(R, b) - 1) * int(hist_stride_s) + ((R - 1) // b) * int(hist_stride_k) + t - 1) if b >= 1 else 0
-        assert hist.storage_offset() + last < hist.untyped_storage().nbytes() // 8
+    R, V, t, b, hist_stride_s = _constrain_rows(logits, hist, t, active, b, hist_stride_s, hist_stride_k)
     for a in (trie.child_ptr, trie.child_tok, trie.child_node, trie.root):
         assert a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()
     n_nodes, n_edges = trie.child_ptr.numel() - 1, trie.child_tok.numel()
     assert trie.terminal.dtype == torch.uint8 and trie.terminal.is_contiguous() and trie.terminal.numel() == n_nodes
     assert trie.child_node.numel() == n_edges
-    assert active is None or (active.dtype in (torch.bool, torch.uint8) and active.is_contiguous() and active.numel() == R)
     lib.call("valor_trie_constrain", _stream(), _ptr(logits), logits.stride(0), R, V, None if hist is None else _ptr(hist),
-             int(hist_stride_s or 0), int(hist_stride_k), b, t, int(eos), _ptr(trie.child_ptr), _ptr(trie.child_tok) if n_edges else None,
+             hist_stride_s, int(hist_stride_k), b, t, int(eos), _ptr(trie.child_ptr), _ptr(trie.child_tok) if n_edges else None,
              _ptr(trie.child_node) if n_edges else None, _ptr(trie.terminal), _ptr(trie.root), n_nodes, n_edges, trie.root.numel(),
              None if active is None else _ptr(active))
     return logits

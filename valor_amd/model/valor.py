@@ -1433,7 +1433,7 @@ class VALOR(nn.Module):
         DESIGN 1). Per query group g of 'cap%..':
           1. baseline: greedy decoding (whatever beam_size says) with the encoders in eval mode, no grad;
           2. sample: the encoders ONCE in train mode with autograd; from their K|V (detached) one draw per clip through the cached decoding
-             session (valor_amd.decode.decode_sample_cached), no grad;
+             session (valor_amd.decode.decode_sample), no grad;
           3. reward r = scorer(ids, sample) - scorer(ids, greedy) (alpha_type 0: alpha = 1, :1461-1507), hypotheses cut at the first [SEP];
           4. loss: ONE teacher-forced decoder pass over the sampled sequences on the same encoder outputs, with grad, decoder dropout off:
              caption_loss_<g> = reward_loss (:166-173) = mean over the positions up to and including the first [SEP] of -r_i logP."""
