@@ -638,6 +638,29 @@ int valor_trie_constrain(void* stream, float* logits, int64_t ld, int R, int V, 
                          int64_t hist_stride_k, int b, int t, int64_t eos, const int32_t* child_ptr, const int32_t* child_tok,
                          const int32_t* child_node, const uint8_t* terminal, const int32_t* root, int n_nodes, int n_edges, int n_roots,
                          const uint8_t* active);
+/* exact scores of a whole closed answer set, one trie LEVEL (or a chunk of one) per launch (csrc/trie.hip): row r = i * b + s of the
+ * fp32 logits [rows, V] (row pitch ld >= V, rows = n_level * b) is the decoding step's output after the forced prefix of node
+ * level_node[i] (int32 [rows / b], device) for sample s. The trie is valor_trie_constrain's CSR form. In fp32, per row:
+ *   1. lse_r = lse[r] when lse is not null (valor_xent_fwd's value); otherwise the row's log-sum-exp computed here while the row is read
+ *      once, left in lse_out[r] when that is not null;
+ *   2. for every edge e of the node: node_score[child_node[e] * b + s] = node_score[node * b + s] + (z[r, child_tok[e]] - lse_r);
+ *   3. if terminal[node]: final[node * b + s] = node_score[node * b + s] + (z[r, eos] - lse_r).
+ * The subtraction is rounded first, then the addition. With node_score of the root = 0 (the caller's), levels issued root first,
+ * final[node] is the ascending-t fp32 sum of the per-step log-probabilities of the candidate that ends at node: what
+ * score_candidates and the beam search assign to it. node_score / final: fp32 [n_nodes * b]; elements the level does not own keep
+ * their bits.
+ *   A level_node or child_node outside [0, n_nodes) and a child token outside [0, V) are never dereferenced (the arrays live on the
+ *   device: they cannot be read before the launch): such a row / edge writes nothing. A child range is clamped to [0, n_edges].
+ * rows == 0: no-op. VALOR_ERR_ARG, before any launch: null logits / level_node / child_ptr / terminal / node_score / final, null
+ * child_tok or child_node with n_edges > 0, rows < 0 or no multiple of b, more level nodes than n_nodes, V < 1, ld < V, b < 1,
+ * n_nodes < 1, n_edges < 0, eos outside [0, V). One 256-thread workgroup per row; 16-byte loads when logits and ld are multiples of 16
+ * bytes, 4-byte loads otherwise; the threads stride over the node's edges; every output element is written once, with ordinary
+ * vector stores; no atomics, no workspace, the logits are never written: the result does not depend on how the threads split the
+ * work. */
+int valor_trie_score_level(void* stream, const float* logits, int64_t ld, int64_t rows, int V, int b, const int32_t* level_node,
+                           const float* lse, float* lse_out, int64_t eos, const int32_t* child_ptr, const int32_t* child_tok,
+                           const int32_t* child_node, const uint8_t* terminal, int n_nodes, int n_edges, float* node_score,
+                           float* final);
 /* ---- the SCST caption reward on the device: CIDEr-D + BLEU-4 per hypothesis row (csrc/reward.hip; the rules are those of
  * valor_amd/scst.py: scorer/cider_scorer.py:119-200 with n = 1..4 and sigma 6, scorer/bleu_scorer.py:202-250 option 'closest').
  *   KEY of the n-gram (t_0 .. t_{n-1}): (t_i + 1) in bits [16 i, 16 i + 16) of a uint64, unused fields 0 -- exact, n = the number of

@@ -139,3 +139,118 @@ extern "C" int valor_trie_constrain(void* stream, float* logits, int64_t ld, int
                        hist_stride_k, b, t, (int)eos, child_ptr, child_tok, child_node, terminal, root, n_nodes, n_edges, n_roots, active, vec);
     return valor_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------
+// Exact ranking of a whole closed answer set, one trie level per launch (valor_trie_score_level; the law: include/valor_hip.h). Row
+// r = i * b + s of the fp32 logits is the decoder's output for node level_node[i] and sample s: the row scores ALL of the node's children
+// and its own end-of-answer term, so a candidate's sequence log-probability costs one decoder row per trie NODE instead of one per
+// (candidate, step).
+//   One 256-thread workgroup per row.
+//   1. lse given: the row is not streamed at all, only the node's columns are gathered. lse null: one pass over the row's V floats --
+//      16-byte loads (four in flight per thread) when the base and the pitch allow, 4-byte loads otherwise -- with a running
+//      (maximum, sum of exp) pair per thread; the 256 pairs meet in fp64 (wave shuffles, four LDS words) and the logarithm is taken in
+//      fp64, so lse_r carries one fp32 rounding besides the error of the fp32 partial sums.
+//   2. the threads stride over the node's edges: node_score[child] = node_score[node] + (z[tok] - lse_r), the subtraction rounded first;
+//      thread 0 adds the [SEP] term of a terminal node into final[node]. The gathered columns were just streamed: they come out of L2.
+//   Every output element is written once by the thread that owns its edge: no atomics, no workspace, no LDS beyond the reduction words;
+//   the logits are read-only. A level_node / child_node outside [0, n_nodes) or a child token outside [0, V) is never dereferenced: the
+//   row / edge writes nothing. A child range is clamped to [0, n_edges].
+DEVINL double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+    return v;
+}
+
+DEVINL void tsl_fold(float& m, float& s, float z) {
+    if (z > m) { s *= expf(m - z); m = z; }                                  // (m = -inf: s is 0 and stays 0)
+    s += expf(z - m);
+}
+
+DEVINL void tsl_fold4(float& m, float& s, const f32x4_t v) {
+    const float vm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+    if (vm > m) { s *= expf(m - vm); m = vm; }
+    s += (expf(v[0] - m) + expf(v[1] - m)) + (expf(v[2] - m) + expf(v[3] - m));
+}
+
+__global__ __launch_bounds__(TRIE_THREADS) void trie_score_level_kernel(const float* __restrict__ logits, int64_t ld, int V, int b,
+                                                                       const int32_t* __restrict__ level_node,
+                                                                       const float* __restrict__ lse, float* __restrict__ lse_out, int eos,
+                                                                       const int32_t* __restrict__ child_ptr,
+                                                                       const int32_t* __restrict__ child_tok,
+                                                                       const int32_t* __restrict__ child_node,
+                                                                       const uint8_t* __restrict__ terminal, int n_nodes, int n_edges,
+                                                                       float* __restrict__ node_score, float* __restrict__ final, int vec) {
+    __shared__ float red_m[4];
+    __shared__ double red_s[4];
+    __shared__ float row_lse;
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = (int)(r % b);
+    const float* z = logits + r * ld;
+    float l;
+    if (lse) {
+        l = lse[r];
+    } else {
+        float m = -INFINITY, acc = 0.f;
+        if (vec) {
+            const int V4 = V & ~3;
+            for (int j0 = tid * 4; j0 < V4; j0 += 4 * 4 * TRIE_THREADS) {
+                f32x4_t v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int j = j0 + u * 4 * TRIE_THREADS;
+                    if (j < V4) v[u] = *(const f32x4_t*)(z + j);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (j0 + u * 4 * TRIE_THREADS < V4) tsl_fold4(m, acc, v[u]);
+            }
+            if (V4 + tid < V) tsl_fold(m, acc, z[V4 + tid]);
+        } else {
+            for (int j = tid; j < V; j += TRIE_THREADS) tsl_fold(m, acc, z[j]);
+        }
+        const float wm = wave_max(m);
+        if (lane == 0) red_m[wave] = wm;
+        __syncthreads();
+        const float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+        const double part = wave_sum_f64(m == -INFINITY ? 0.0 : (double)acc * (double)expf(m - M));
+        if (lane == 0) red_s[wave] = part;
+        __syncthreads();
+        if (tid == 0) {
+            const float v = (float)((double)M + log((red_s[0] + red_s[1]) + (red_s[2] + red_s[3])));
+            row_lse = v;
+            if (lse_out) lse_out[r] = v;
+        }
+        __syncthreads();
+        l = row_lse;
+    }
+    const int node = level_node[r / b];
+    if (node < 0 || node >= n_nodes) return;                                 // (workgroup-uniform)
+    const float own = node_score[(int64_t)node * b + s];
+    const int lo = min(max(child_ptr[node], 0), n_edges);
+    const int hi = min(max(child_ptr[node + 1], lo), n_edges);
+    for (int e = lo + tid; e < hi; e += TRIE_THREADS) {
+        const int w = child_tok[e], c = child_node[e];
+        if (w < 0 || w >= V || c < 0 || c >= n_nodes) continue;
+        const float term = z[w] - l;
+        node_score[(int64_t)c * b + s] = own + term;
+    }
+    if (tid == 0 && terminal[node]) {
+        const float term = z[eos] - l;
+        final[(int64_t)node * b + s] = own + term;
+    }
+}
+
+extern "C" int valor_trie_score_level(void* stream, const float* logits, int64_t ld, int64_t rows, int V, int b, const int32_t* level_node,
+                                      const float* lse, float* lse_out, int64_t eos, const int32_t* child_ptr, const int32_t* child_tok,
+                                      const int32_t* child_node, const uint8_t* terminal, int n_nodes, int n_edges, float* node_score,
+                                      float* final) {
+    if (rows == 0) return VALOR_OK;
+    if (!logits || !level_node || !child_ptr || !terminal || !node_score || !final) return VALOR_ERR_ARG;
+    if (rows < 0 || rows > 0x7fffffffll || V < 1 || ld < V || b < 1 || rows % b != 0 || eos < 0 || eos >= V) return VALOR_ERR_ARG;
+    if (n_nodes < 1 || n_edges < 0 || rows / b > n_nodes || ((!child_tok || !child_node) && n_edges > 0)) return VALOR_ERR_ARG;
+    const int vec = ((uintptr_t)logits % 16 == 0 && ld % 4 == 0) ? 1 : 0;
+    hipLaunchKernelGGL(trie_score_level_kernel, dim3((unsigned)rows), dim3(TRIE_THREADS), 0, (hipStream_t)stream, logits, ld, V, b, level_node,
+                       lse, lse_out, (int)eos, child_ptr, child_tok, child_node, terminal, n_nodes, n_edges, node_score, final, vec);
+    return valor_launch_status();
+}

@@ -34,7 +34,9 @@ off no launch is issued. `constrain_rows_host` restates the kernel's law on the 
 
 Closed answer sets (`AnswerSet`: a token trie of candidates, shared or one per sample): `candidates=` makes every loop decode INSIDE the
 set with one valor_trie_constrain launch per step in the same place (`trie_rows_host` is its law on the host), and `score_candidates`
-returns the exact sequence log-probability of every candidate by forced decoding through the same step sources.
+returns the exact sequence log-probability of every candidate by forced decoding through the same step sources. `rank_candidates` ranks
+a whole shared set exactly, level by level over the trie: one decoder row per trie node, a node's logits row scoring all its children
+(valor_trie_score_level; `trie_level_host` is its law on the host).
 
 Everything here is inference: torch.no_grad, dropout off regardless of model.training (the reference calls it under model.eval())."""
 import contextlib
@@ -609,6 +611,60 @@ class AnswerSet:
                                                          ("child_ptr", "child_tok", "child_node", "terminal", "root")})
         return d
 
+    def levels(self, dev=None):
+        """the trie of a shared set in breadth-first order, for the level-batched exact ranking (`rank_candidates`): host tensors, cached
+        on the set; with `dev` their copy on that device, cached like .device(dev).
+          order int32 [N]: the node ids, level by level (level 0 = the root alone, parents before children, a node's children in
+          ascending token order); level_ptr (a list, depth_max + 2 entries): level d = order[level_ptr[d] : level_ptr[d + 1]];
+          depth / token / parent int32 [N], indexed by node id (the root: depth 0, token [CLS], parent -1);
+          anc int32 [N, depth_max + 1]: anc[n, j] = the ancestor of n at depth j (j = depth[n]: n itself; deeper: -1);
+          cand_node int64 [C]: the node where candidate c ends (duplicates share it); depth_max = the longest answer; width = the
+          widest level."""
+        import types
+        if self.per_sample:
+            raise ValueError("AnswerSet.levels: a per-sample set has one trie per sample; the level plan is that of a shared set")
+        lv = self.__dict__.get("_levels")
+        if lv is None:
+            N = self.n_nodes
+            ptr, tok, nod = self.child_ptr.tolist(), self.child_tok.tolist(), self.child_node.tolist()
+            depth, token, parent = [0] * N, [BOS] * N, [-1] * N
+            order, level_ptr, level = [], [0], [int(self.root[0])]
+            while level:
+                order += level
+                level_ptr.append(len(order))
+                nxt = []
+                for n in level:
+                    for e in range(ptr[n], ptr[n + 1]):
+                        c = nod[e]
+                        depth[c], token[c], parent[c] = depth[n] + 1, tok[e], n
+                        nxt.append(c)
+                level = nxt
+            D = len(level_ptr) - 2
+            anc = [[-1] * (D + 1) for _ in range(N)]
+            for n in order:                                              # parents first: a node's row is its parent's plus itself
+                if parent[n] >= 0:
+                    anc[n][:depth[n]] = anc[parent[n]][:depth[n]]
+                anc[n][depth[n]] = n
+            cand_node = []
+            for cand in self.candidates[0]:
+                n = int(self.root[0])
+                for w in cand:
+                    n = self._kids[n][w]
+                cand_node.append(n)
+            i32 = lambda x: torch.tensor(x, dtype=torch.int32)
+            lv = self._levels = types.SimpleNamespace(
+                order=i32(order), level_ptr=level_ptr, depth=i32(depth), token=i32(token), parent=i32(parent), anc=i32(anc),
+                cand_node=torch.tensor(cand_node, dtype=torch.int64), depth_max=D,
+                width=max(level_ptr[d + 1] - level_ptr[d] for d in range(D + 1)))
+            self._levels_dev = {}
+        if dev is None:
+            return lv
+        dev = torch.device(dev)
+        d = self._levels_dev.get(dev)
+        if d is None:
+            d = self._levels_dev[dev] = types.SimpleNamespace(**{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in vars(lv).items()})
+        return d
+
     def with_roots(self, samples):
         """the same trie read by other rows: row-sample i of the result is sample samples[i] of this per-sample set (several question
         rows per clip, num_return_sequences)"""
@@ -698,6 +754,38 @@ def trie_rows_host(logits, hist, t, answer_set, eos, b, active=None):
         keep[torch.tensor(sorted(allowed), dtype=torch.long)] = True
         out[r] = torch.where(keep, out[r], floor)
     return out
+
+
+def trie_level_host(logits, lse, level_node, b, answer_set, eos, node_score, final):
+    """The law of valor_trie_score_level (include/valor_hip.h) restated on the host from the CSR arrays: logits [n_level * b, V] (any
+    device; row i * b + s = node level_node[i], sample s), lse fp32 [rows] (the rows' log-sum-exp as the caller has it; None: torch's,
+    which is not the kernel's bit for bit), node_score / final fp32 [n_nodes * b] (not modified) -> new host tensors (node_score,
+    final). fp32 throughout, the subtraction rounded before the addition: bit-identical to the kernel for the same lse."""
+    a = answer_set
+    z = logits.detach().to(device="cpu", dtype=torch.float32)
+    rows, V = z.shape
+    ptr, tok, nod, term = (x.tolist() for x in (a.child_ptr, a.child_tok, a.child_node, a.terminal))
+    N, E = len(term), len(tok)
+    nodes = level_node.tolist() if torch.is_tensor(level_node) else list(level_node)
+    if b < 1 or rows != len(nodes) * b:
+        raise ValueError(f"trie_level_host: {rows} rows for {len(nodes)} nodes x b = {b}")
+    l = torch.logsumexp(z, 1) if lse is None else lse.detach().to(device="cpu", dtype=torch.float32)
+    ns = node_score.detach().to(device="cpu", dtype=torch.float32).clone().view(N, b)
+    fin = final.detach().to(device="cpu", dtype=torch.float32).clone().view(N, b)
+    for i, node in enumerate(nodes):
+        if not 0 <= node < N:
+            continue
+        zr, lr, own = z[i * b:(i + 1) * b], l[i * b:(i + 1) * b], ns[node].clone()
+        lo = min(max(ptr[node], 0), E)
+        hi = min(max(ptr[node + 1], lo), E)
+        edges = [e for e in range(lo, hi) if 0 <= tok[e] < V and 0 <= nod[e] < N]
+        if edges:
+            cols = torch.tensor([tok[e] for e in edges], dtype=torch.long)
+            kids = torch.tensor([nod[e] for e in edges], dtype=torch.long)
+            ns[kids] = own[None, :] + (zr[:, cols].t() - lr[None, :])
+        if term[node]:
+            fin[node] = own + (zr[:, int(eos)] - lr)
+    return ns.reshape(-1), fin.reshape(-1)
 
 
 class _TrieConstrainer:
@@ -1262,5 +1350,169 @@ def score_candidates(model, batch, groups, candidates, prompt_cpu=None, max_rows
                 n = min(chunk, Cmax - c0)
                 out[g][:, c0:c0 + n] = torch.where(real_d, score.view(b, chunk), -float("inf"))[:, :n]
         return out
+    finally:
+        model.train(was_training)
+
+
+RANK_STORE_BYTES = 16 << 30              # rank_candidates' default cap on its self-attention slot store
+
+
+def _rank_tree(model, g, b, kv_layers, ranges, prompt, a, max_rows):
+    """rank_candidates for one query group and one sub-batch of b samples -> fp32 [b, C] on the device. kv_layers: the b clips' own
+    per-layer K|V (rows are node-major, row = i * b + s: cross-attention reads clip row % b), prompt: their host prompt rows or None."""
+    m, P_, dev, dt = model, model.P, model.device, model.dtype
+    E, H, layers = m.spec.hidden, m.spec.heads, m.spec.layers
+    e = "multimodal_encoder.embeddings."
+    trie, lv = a.device(dev), a.levels(dev)
+    N, D = a.n_nodes, lv.depth_max
+    J = 1 if m.caption_type == "lm" else 2
+    P = 0 if prompt is None else prompt.shape[1]
+    Skv = P + D + 2                                                  # [prompt | text positions 0 .. D | the [MASK] behind the deepest]
+    cn = min(lv.width, max(1, int(max_rows) // b))                   # nodes per launch of the layer stack
+    max_r = cn * b
+    tok0, mask0 = b * P, b * P + N * b                               # slots: P per sample, one per (node, sample), one [MASK] per chunk row
+    slots = mask0 + (max_r if J == 2 else 0)
+    store = torch.zeros((layers, slots, 2 * E), dtype=dt, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    cross = m._dev(torch.tensor([list(ranges[g])] * max_r, dtype=torch.int32)) if kv_layers is not None else None
+    bmod = b if kv_layers is not None else 0
+    s_idx = torch.arange(b, **i32)
+    pm = None
+    if P:                                                            # the prompt rows, once per sample: DecodeSession.begin_group's prefill
+        pm = (1.0 - m._dev((prompt != 0).to(torch.float32))) * NEG                              # [b, P]: a zero-id key is masked
+        pmask = pm[:, None, :].expand(b, P, P).contiguous()
+        xp = m._bert_embed(m._dev(prompt), P, "prompt")
+
+        def prefill(i, qkv):
+            store[i, :tok0] = qkv[:, :, E:].reshape(tok0, 2 * E)
+            return ops.self_attention(qkv, H, pmask, 0.0)
+        m.bert_encoder(xp, pmask, kv_layers, cross[:b] if cross is not None else None, bmod, self_attn=prefill)
+    Wd, Pe, Ty = P_[e + "word_embeddings.weight"], P_[e + "position_embeddings.weight"], P_[e + "token_type_embeddings.weight"]
+    V = Wd.shape[0]
+    logits_pad = torch.zeros((max_r, (V + 31) // 32 * 32), dtype=torch.float32, device=dev)
+    node_score = torch.zeros(N * b, dtype=torch.float32, device=dev)          # the root's prefix score is 0
+    final = torch.zeros(N * b, dtype=torch.float32, device=dev)
+    col = torch.arange(Skv, device=dev)
+    prompt_keys = (s_idx[:, None] * P + torch.arange(P, **i32)[None, :]) if P else None        # [b, P]
+    for d in range(D + 1):
+        for p0 in range(lv.level_ptr[d], lv.level_ptr[d + 1], cn):
+            nodes = lv.order[p0:min(p0 + cn, lv.level_ptr[d + 1])].contiguous()
+            c = nodes.numel()
+            rows = c * b
+            nl = nodes.long()
+            # BertEmbeddings (bert.py:190-218) of the node's token at position d and of [MASK] at d + 1: DecodeSession._body's arithmetic
+            ids = torch.full((rows, J), MASK, dtype=torch.int64, device=dev)
+            ids[:, 0] = lv.token[nl].long().repeat_interleave(b)
+            pos = torch.arange(d, d + J, device=dev)
+            x = (Wd[ids].float() + Pe[pos].float()[None] + Ty[0].float()).to(dt)
+            x = ops.layer_norm(x, P_[e + "LayerNorm.weight"], P_[e + "LayerNorm.bias"], 1e-12)
+            # the key table: [the sample's prompt slots | the ancestors' and the row's own token slot | its [MASK] slot | slot 0, masked]
+            anc = lv.anc[nl]                                                                     # [c, D + 1]
+            table = torch.zeros((c, b, Skv), **i32)
+            if P:
+                table[:, :, :P] = prompt_keys[None]
+            table[:, :, P:P + D + 1] = torch.where(anc[:, None, :] >= 0, tok0 + anc[:, None, :] * b + s_idx[None, :, None], 0)
+            own = (tok0 + nodes[:, None] * b + s_idx[None, :]).reshape(rows, 1).long()
+            new_slots = own
+            if J == 2:
+                mslot = mask0 + torch.arange(rows, **i32)
+                table[:, :, P + d + 1] = mslot.view(c, b)
+                new_slots = torch.cat((own, mslot.long()[:, None]), dim=1)
+            new_slots = new_slots.reshape(-1)
+            table = table.view(rows, Skv)
+            amask = torch.where(col <= P + d, 0.0, NEG).to(torch.float32).expand(c, b, 1, Skv).repeat(1, 1, J, 1)
+            if P:
+                amask[:, :, :, :P] = pm[None, :, None, :]
+            if J == 2:
+                amask[:, :, 1, P + d + 1] = 0.0
+            amask = amask.view(rows, J, Skv)
+
+            def self_attn(i, qkv):
+                st = store[i]
+                st.index_copy_(0, new_slots, qkv[:, :, E:].reshape(rows * J, 2 * E))
+                k = torch.as_strided(st, (slots, Skv, E), (2 * E, 0, 1), st.storage_offset())      # flat slots: the table names the row
+                v = torch.as_strided(st, (slots, Skv, E), (2 * E, 0, 1), st.storage_offset() + E)
+                return K.attn_decode(qkv[:, :, :E], k, v, H, mask=amask, key_row=table, scale=0.125)
+            hidden = m.bert_encoder(x, None, kv_layers, cross[:rows] if cross is not None else None, bmod, self_attn=self_attn)
+            h = m.cls_transform(hidden[:, J - 1].contiguous())
+            logits = logits_pad[:rows, :V]
+            K.gemm(h, Wd, bias=P_["cls.decoder.bias"], out=logits, out_dtype=torch.float32, policy=K.infer_policy())
+            K.trie_score_level(logits, nodes, b, EOS, trie, node_score, final)
+    return final.view(N, b)[lv.cand_node].t().contiguous()
+
+
+@torch.no_grad()
+def rank_candidates(model, batch, groups, candidates, prompt_cpu=None, k=None, max_rows=8192, max_store_bytes=RANK_STORE_BYTES):
+    """The exact sequence log-probability of EVERY answer of a shared closed set, for every sample: score_candidates' inputs and output
+    ({group: fp32 [b, C]} on the device, duplicates carry equal scores; sample_num, the caption prompt, 'unimlm' and 'lm' as there), by
+    level-batched trie scoring: one decoder row per trie NODE and sample instead of one per (candidate, step). A node's logits row
+    scores all its children and its own end-of-answer term in one valor_trie_score_level launch, prefixes are computed once, and the
+    whole set is ranked in depth + 1 passes over the layer stack (b * n_nodes rows in all, against b * C * (Lmax + 1)).
+    k (1 .. min(256, C)): -> {group: (values fp32 [b, k], indices int64 [b, k])} through valor_topk_rows: scores descending, equal
+    scores in index order (the lowest duplicate first).
+    The rows of a pass are node-major (row = i * b + s), so cross-attention reads clip row % b: the clips' K|V are not copied.
+    Self-attention K|V lives in a flat slot store [layers, slots, 2E]: P prompt slots per sample (one prefill, zero-id keys masked),
+    one token slot per (node, sample), one transient [MASK] slot per row of the current chunk ('unimlm'); an int32 key table
+    [rows, P + depth + 2] names, per row, its sample's prompt slots, its ancestors' token slots, its own, and its [MASK] slot, and
+    valor_attn_decode_fwd reads the keys where they were written (zero key row stride): nothing moves from parent to child.
+    max_rows: a level wider than max_rows // b nodes runs in chunks of nodes; max_store_bytes: when the slot store of b samples
+    would be larger, the samples go in sub-batches (halved until it fits). Chunking changes a score only through the GEMM kernel the
+    row count selects. Issued eagerly: depth + 1 wide passes, nothing to capture. Nothing stays in the model's session pool; the
+    model is in eval mode for the call and gets its mode back.
+    A per-sample set raises ValueError: score_candidates is the tool for a handful of choices per question. A model with a
+    cross-attention block per modality (_BlockKV) and VALOR_KV_CACHE=0 have no tree pass: they delegate to score_candidates."""
+    a = _answer_set(candidates)
+    if a is None:
+        raise ValueError("rank_candidates: no candidates")
+    if a.per_sample:
+        raise ValueError("rank_candidates: a per-sample set has no shared trie to batch by level; score_candidates scores a handful of "
+                         "choices per question")
+    C = a.counts[0]
+    if k is not None and (int(k) != k or not 1 <= k <= min(256, C)):
+        raise ValueError(f"rank_candidates: k = {k!r} outside 1 .. min(256, {C} candidates) (valor_topk_rows)")
+    a.check_vocab(model.spec.vocab)
+    if a.max_len + 2 > model.spec.max_pos:
+        raise ValueError(f"rank_candidates: an answer of {a.max_len} tokens does not fit the decoder's {model.spec.max_pos} positions")
+
+    def best(out):
+        if k is None:
+            return out
+        from .search import topk_rows
+        return {g: topk_rows(sc.contiguous(), int(k)) for g, sc in out.items()}
+    if not kv_cache_enabled() or model.spec.cross_attn_type != "va_concate":
+        return best(score_candidates(model, batch, groups, a, prompt_cpu=prompt_cpu))
+    was_training = model.training
+    model.eval()
+    try:
+        b, kv_layers, ranges = encode_for_generation(model, batch, groups)
+        sample_num = [int(n) for n in batch.get("sample_num", [])]
+        if torch.is_tensor(prompt_cpu) and any(n != 1 for n in sample_num):      # several question rows per clip, as in generate_qa
+            if len(sample_num) != b or sum(sample_num) != prompt_cpu.shape[0]:
+                raise ValueError(f"sample_num {sample_num} does not describe {b} clips / {prompt_cpu.shape[0]} questions")
+            kv_layers = _repeat_clips(model, kv_layers, b, sample_num)
+            b = sum(sample_num)
+        if isinstance(prompt_cpu, str) or prompt_cpu is None:
+            prompt = _prompt_rows(model, prompt_cpu or "caption", b)
+        else:
+            if prompt_cpu.shape[0] != b:
+                raise ValueError(f"rank_candidates: {prompt_cpu.shape[0]} prompt rows for {b} samples")
+            prompt = prompt_cpu
+        lv = a.levels()
+        P = 0 if prompt is None else prompt.shape[1]
+        if P + lv.depth_max + 2 > 256:
+            raise ValueError(f"rank_candidates: {P} prompt slots + {lv.depth_max + 2} text slots exceed the 256 keys of valor_attn_decode_fwd")
+        J = 1 if model.caption_type == "lm" else 2
+        slot_bytes = model.spec.layers * 2 * model.spec.hidden * torch.empty((), dtype=model.dtype).element_size()
+        need = lambda n: (n * (P + a.n_nodes) + (J - 1) * min(lv.width, max(1, int(max_rows) // n)) * n) * slot_bytes
+        bs = b
+        while bs > 1 and need(bs) > max_store_bytes:
+            bs = (bs + 1) // 2
+        out = {g: torch.empty((b, C), dtype=torch.float32, device=model.device) for g in ("tv", "tva", "ta") if g in groups}
+        for s0 in range(0, b, bs):
+            s1 = min(b, s0 + bs)
+            kv_sub = kv_layers if kv_layers is None or (s0 == 0 and s1 == b) else [kv[s0:s1] for kv in kv_layers]
+            for g in out:
+                out[g][s0:s1] = _rank_tree(model, g, s1 - s0, kv_sub, ranges, None if prompt is None else prompt[s0:s1], a, max_rows)
+        return best(out)
     finally:
         model.train(was_training)

@@ -551,7 +551,8 @@ def _choice_sets(batch, n_questions):
 
 
 @torch.no_grad()
-def validate_qa(model, loader, task, *, decode=None, output_dir=None, global_step=0, dset_name="", candidates=None, multiple_choice=False):
+def validate_qa(model, loader, task, *, decode=None, output_dir=None, global_step=0, dset_name="", candidates=None, multiple_choice=False,
+                answer_ranking=None):
     """test.py::validate_qa (:44-130): the generated answers of every group, decoded to strings, are compared with the ground truth
     (exact string equality); answers and ground truth are gathered across ranks. Returns {'tv': {'accuracy': round(acc * 100, 2)}, ..}
     on every rank. With output_dir, rank 0 writes predict_answers/step{global_step}_gt.json, step{..}_tv_pred.json and the question_ids
@@ -562,7 +563,12 @@ def validate_qa(model, loader, task, *, decode=None, output_dir=None, global_ste
     batch['choice_tokens']['bert_tokens'] (the same count per question inside a batch), the ground truth is the integer index in
     batch['answers'] (or txt_tokens), the prediction is the arg max of decode.score_candidates (the exact sequence log-probability of
     every choice; ties to the lower index); the dumps hold indices. A call that passes neither, on a model without the options, is the
-    reference's flow unchanged."""
+    reference's flow unchanged.
+    answer_ranking (default: the model's option qa_answer_ranking, absent = 'decode'): 'decode' -- the constrained generation above;
+    'exact' -- with candidates (a shared set): the prediction of every question is the arg max of decode.rank_candidates over the whole
+    set (the exact sequence log-probability of every answer; ties to the lower index) instead of what the beam reaches; the rest of the
+    flow, the dumps and the accuracy bookkeeping are those of the candidates= mode. 'exact' without candidates, or with
+    multiple_choice, raises ValueError."""
     import json
     import os
     from .model.valor import _opt
@@ -572,9 +578,26 @@ def validate_qa(model, loader, task, *, decode=None, output_dir=None, global_ste
     multiple_choice = bool(multiple_choice) or bool(_opt(opts, "qa_multiple_choice", False))
     if candidates is None:
         candidates = _opt(opts, "qa_answer_candidates", None)
+    if answer_ranking is None:
+        answer_ranking = _opt(opts, "qa_answer_ranking", "decode")
+    if answer_ranking not in ("decode", "exact"):
+        raise ValueError(f"validate_qa: answer_ranking {answer_ranking!r} ('decode' or 'exact')")
     if multiple_choice and candidates is not None:
         raise ValueError("validate_qa: multiple_choice scores the batch's own choices; candidates= (qa_answer_candidates) is the other mode")
+    exact = answer_ranking == "exact"
+    if exact and multiple_choice:
+        raise ValueError("validate_qa: answer_ranking='exact' ranks a shared candidate set; multiple_choice already scores every choice exactly")
+    if exact and candidates is None:
+        raise ValueError("validate_qa: answer_ranking='exact' needs candidates= (or the option qa_answer_candidates): the set to rank")
     candidates = D._answer_set(candidates)
+    if exact and candidates.per_sample:
+        raise ValueError("validate_qa: answer_ranking='exact' ranks one shared set; a per-sample set goes through decode.score_candidates")
+    if exact:                                   # the answers as '[tokens] [SEP] 0..' rows: what the decoder hands to `dec`
+        rows = candidates.candidates[0]
+        answer_rows = torch.zeros((len(rows), candidates.max_len + 1), dtype=torch.long)
+        for i, r in enumerate(rows):
+            answer_rows[i, :len(r)] = torch.tensor(r, dtype=torch.long)
+            answer_rows[i, len(r)] = D.EOS
     groups = task.split("%")[1:]
     dec = _decoder(model, decode)
     model.eval()
@@ -590,6 +613,12 @@ def validate_qa(model, loader, task, *, decode=None, output_dir=None, global_ste
             ev = {"generated_answers_" + _GROUP_KEY[g]: torch.where(sc == sc.max(1, keepdim=True).values, cols, cols.numel()).min(1).values.cpu()
                   for g, sc in scores.items()}
             pick = lambda x: [int(i) for i in x]
+        elif exact:
+            gt += _answer_strings(batch, dec)
+            prompt = core.qa_prompt(batch["question_tokens"]["bert_tokens"].cpu())
+            top = D.rank_candidates(core, batch, list(answers), candidates, prompt_cpu=prompt, k=1)
+            ev = {"generated_answers_" + _GROUP_KEY[g]: answer_rows[idx[:, 0].cpu()] for g, (_, idx) in top.items()}
+            pick = dec
         else:
             gt += _answer_strings(batch, dec)
             ev = model(batch, task=task, compute_loss=False, **({} if candidates is None else {"candidates": candidates}))
@@ -639,7 +668,8 @@ def validate_single(model, loader, task, *, annotations=None, dset_name="", outp
         return validate_cap(model, loader, task, annotations, output_dir=output_dir, global_step=global_step, dset_name=dset_name, **kw)
     if task.startswith("qa"):
         return validate_qa(model, loader, task, decode=kw.get("decode"), output_dir=output_dir, global_step=global_step, dset_name=dset_name,
-                           candidates=kw.get("candidates"), multiple_choice=kw.get("multiple_choice", False))
+                           candidates=kw.get("candidates"), multiple_choice=kw.get("multiple_choice", False),
+                           answer_ranking=kw.get("answer_ranking"))
     raise NotImplementedError(f"task {task!r}: 'pt', 'ret', 'cap' and 'qa' are the reference's evaluation families (test.py:33-40)")
 
 

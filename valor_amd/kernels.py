@@ -668,6 +668,30 @@ def trie_constrain(logits, hist, t, eos, trie, active=None, b=None, hist_stride_
     return logits
 
 
+def trie_score_level(logits, level_node, b, eos, trie, node_score, final, lse=None, lse_out=None):
+    """one trie level (or a chunk of one) of the exact ranking of a closed answer set (valor_trie_score_level; the law:
+    include/valor_hip.h): logits fp32 [n_level * b, V] (row pitch = stride(0)), row i * b + s = node level_node[i] (int32 [n_level]),
+    sample s; trie = the device form of a decode.AnswerSet; node_score / final fp32 [n_nodes * b], written in place (the children's
+    prefix scores, the level's own end-of-answer scores). lse fp32 [rows]: the rows' log-sum-exp (valor_xent_fwd's); None: computed in
+    the launch and left in lse_out [rows] when given."""
+    _check_gpu(logits, level_node, lse, lse_out, node_score, final, trie.child_ptr, trie.child_tok, trie.child_node, trie.terminal)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    rows, V = logits.shape
+    for a in (level_node, trie.child_ptr, trie.child_tok, trie.child_node):
+        assert a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()
+    n_nodes, n_edges = trie.child_ptr.numel() - 1, trie.child_tok.numel()
+    assert trie.terminal.dtype == torch.uint8 and trie.terminal.is_contiguous() and trie.terminal.numel() == n_nodes
+    assert trie.child_node.numel() == n_edges and level_node.numel() * int(b) == rows
+    for a in (node_score, final):
+        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == n_nodes * int(b)
+    for a in (lse, lse_out):
+        assert a is None or (a.dtype == torch.float32 and a.is_contiguous() and a.numel() == rows)
+    lib.call("valor_trie_score_level", _stream(), _ptr(logits), logits.stride(0) if rows > 1 else max(logits.stride(0), V), rows, V, int(b),
+             _ptr(level_node), None if lse is None else _ptr(lse), None if lse_out is None else _ptr(lse_out), int(eos),
+             _ptr(trie.child_ptr), _ptr(trie.child_tok) if n_edges else None, _ptr(trie.child_node) if n_edges else None,
+             _ptr(trie.terminal), n_nodes, n_edges, _ptr(node_score), _ptr(final))
+
+
 def fbank(wave, offsets, slice_idx, tables, melbins, T, mean, std, out=None):
     """log-mel filterbank of the selected slices in the model's layout (valor_fbank): wave = the clips packed back to back, fp32 or int16
     PCM [n]; offsets int64 [B + 1]; slice_idx int32 [B, A] (-1: no audio); tables = preprocess.fbank_tables(...).to_device() (window,

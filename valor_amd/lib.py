@@ -167,6 +167,7 @@ SIGNATURES = {
     "valor_sample_tokens_filtered": [_vp, _vp, _i64, _i, _i, _u64, _u64, _i64, _f, _i, _f, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
     "valor_logits_constrain": [_vp, _vp, _i64, _i, _i, _vp, _i64, _i64, _i, _i, _i64, _f, _f, _i, _i, _vp, _i, _vp],
     "valor_trie_constrain": [_vp, _vp, _i64, _i, _i, _vp, _i64, _i64, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "valor_trie_score_level": [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
     "valor_caption_reward": [_vp, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp],
     "valor_caption_metrics": [_vp, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "valor_rowdot_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i],

@@ -386,6 +386,29 @@ def make_batch(spec: ValorSpec, batch: int, frames: int = 8, audio_slices: int =
     return out
 
 
+def make_answer_set(n: int, vocab: int, seed: int = 50, max_len: int = 4, extend: float = 0.6):
+    """n DISTINCT synthetic answers (token-id lists of 1..max_len ids in [min(1000, vocab // 2), vocab)) with common prefixes, the way
+    a closed QA vocabulary has them ('new york', 'new york city'): with probability `extend` an answer continues an earlier, shorter
+    one by one or two fresh tokens, otherwise it starts with a token of its own. Seeded; the order is the draw order."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    lo = min(1000, vocab // 2)
+    draw = lambda hi: int(torch.randint(0, hi, (1,), generator=g))
+    out, seen, short = [], set(), []                     # short: indices of the answers that can still grow
+    while len(out) < n:
+        if short and float(torch.rand((1,), generator=g)) < extend:
+            base = out[short[draw(len(short))]]
+            cand = base + [lo + draw(vocab - lo) for _ in range(min(1 + draw(2), max_len - len(base)))]
+        else:
+            cand = [lo + draw(vocab - lo)]
+        if tuple(cand) in seen:
+            continue
+        seen.add(tuple(cand))
+        if len(cand) < max_len:
+            short.append(len(out))
+        out.append(cand)
+    return out
+
+
 PROMPT_WORDS = ("describe the video with natural language predict masked tokens visual and audio cues project "
                 "in common space answer question").split()
 
