@@ -160,8 +160,16 @@ int valor_gemm_set_fast_epilogue(int v);
  *          was collected on); the inference paths of valor_amd ask for 384 per call through a valor_gemm_policy (env VALOR_GEMM_SKINNY; env
  *          VALOR_GEMM_SKINNY_ALL sets the process default). nn.Linear on the 2 rows per sequence of a
  *          K|V-cached decoding step (model/bert.py:233-235,351,403-420): 20-29 us -> 8.8-17.6 us per launch
- *          (profiles/r06_generation_kernel_stats_{kvcache,skinny}.md) */
+ *          (profiles/r06_generation_kernel_stats_{kvcache,skinny}.md)
+ *   key 12: family 3 on four waves of 128x128 outputs (csrc/gemm8q.hip; env VALOR_GEMM_WAVE128): the 256x256 tile with one wave per SIMD and
+ *          256 accumulator registers per lane -- 128 KiB instead of 192 KiB of LDS fragment reads per K-tile, same accumulation order, results
+ *          bit-identical to the eight-wave kernel. 0 = never, 1 = wherever family 3 runs and the kernel has the layout (k-slow A and B: the
+ *          weight gradients), 1000 (default) = measured per-class choice: the weight gradients with more than 48 K-tiles per workgroup
+ *          (ViT and cross-K|V wgrads: 1.13-1.27 x alone, -1.9 ms per step, profiles/wave128_gemm_ab.json, profiles/wave128_gemm_by_grid_after.txt).
+ *          A process default only: valor_gemm_policy has no field for it. */
 int valor_gemm_set_policy(int key, int value);
+/* 1 if valor_gemm would run this family-3 problem on csrc/gemm8q.hip under the policy in force (valor_gemm_kernel_for keeps answering 3) */
+int valor_gemm_wave128_for(int dtype, int transA, int transB, int M, int N, int K, int heavy_epilogue);
 /* K-loop schedule of the family-3 (256x256) kernel: 0 = eight barriers per K-tile, wave rows staggered by one barrier; 1 = software-pipelined:
  * two barriers per K-tile, fragment reads and LDS-DMA pieces between the MFMAs of the half-phase before their consumer. Same results (same
  * accumulation order). 1000 (default) = per problem: pipelined for forward / dgrad problems with K >= 2048 and for wgrads with at most 48 K-tiles

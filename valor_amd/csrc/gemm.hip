@@ -538,8 +538,10 @@ extern "C" int valor_gemm_set_variant(int v) { const int o = g_gemm_variant; if 
 //      ask for 384 per call (valor_gemm_tuned): caption generation with a K|V cache runs 2 rows per sequence and step (128 rows at 64
 //      clips, 384 with three beams) -- 20 .. 29 us per decoder GEMM on the 128 x 128 kernels (6 .. 24 workgroups),
 //      profiles/r06_generation_kernel_stats_{kvcache,skinny}.md
+// [12] family 3 on four waves of 128x128 outputs (gemm8q.hip): 0 = never, 1 = wherever family 3 runs and gemm8q.hip has the layout, 1000 = measured
+//      per-class choice (use_wave128). A process default only: the per-call valor_gemm_policy keeps its layout.
 thread_local const GemmTuning* t_gemm_tuning = nullptr;
-int g_gemm_policy_default[12] = {[] { const char* e = getenv("VALOR_GEMM_NT_MINK"); return e ? atoi(e) : 768; }(),
+int g_gemm_policy_default[13] = {[] { const char* e = getenv("VALOR_GEMM_NT_MINK"); return e ? atoi(e) : 768; }(),
                         [] { const char* e = getenv("VALOR_GEMM_SPLITK_BF16"); return e ? atoi(e) : 1; }(),
                         [] { const char* e = getenv("VALOR_GEMM_MIN_TILES"); return e ? atoi(e) : 256; }(),
                         [] { const char* e = getenv("VALOR_GEMM_NT_MIN_TILES"); return e ? atoi(e) : 1024; }(),
@@ -550,9 +552,10 @@ int g_gemm_policy_default[12] = {[] { const char* e = getenv("VALOR_GEMM_NT_MINK
                         [] { const char* e = getenv("VALOR_GEMM_NARROW"); return e ? atoi(e) : 1000; }(),
                         [] { const char* e = getenv("VALOR_GEMM_MFMA32"); return e ? atoi(e) : 0; }(),
                         [] { const char* e = getenv("VALOR_GEMM_WIDE"); return e ? atoi(e) : 0; }(),
-                        [] { const char* e = getenv("VALOR_GEMM_SKINNY_ALL"); return e ? atoi(e) : 0; }()};
+                        [] { const char* e = getenv("VALOR_GEMM_SKINNY_ALL"); return e ? atoi(e) : 0; }(),
+                        [] { const char* e = getenv("VALOR_GEMM_WAVE128"); return e ? atoi(e) : 1000; }()};
 extern "C" int valor_gemm_set_policy(int key, int value) {
-    if (key < 0 || key > 11) return VALOR_ERR_ARG;
+    if (key < 0 || key > 12) return VALOR_ERR_ARG;
     const int old = g_gemm_policy_default[key];
     if (value >= 0) g_gemm_policy_default[key] = value;
     return old;
@@ -609,6 +612,35 @@ static int gemm_family(int dtype, int transA, int transB, int M, int N, int K, b
     if (use_8ph2(dtype, transA, transB, M, N, K, heavy_epi, big)) return 4;
     if (big) return 3;
     return gemm_variant() == 2 ? 2 : 1;
+}
+
+// K-tiles per workgroup of a family-3 problem when gemm_impl is offered its usual workspace (the slicing rule of gemm_impl below)
+static int family3_ktiles_per_workgroup(int M, int N, int K) {
+    const int nk = K / 64, tiles = ((M + 255) / 256) * ((N + 255) / 256);
+    int sl = 1;
+    if (2 * tiles <= 256 && nk >= 24) {
+        sl = 256 / tiles;
+        if (sl > nk / 6) sl = nk / 6;
+        if (sl > 64) sl = 64;
+        if (sl < 2) sl = 1;
+    }
+    return (nk + sl - 1) / sl;
+}
+// family 3 on the four-wave kernel of gemm8q.hip (policy key 12). It has the k-slow x k-slow layout (the wgrads) with the general epilogue.
+static bool use_wave128(int dtype, int transA, int transB, int M, int N, int K, bool heavy_epi) {
+    const int mode = gemm_policy(12);
+    if (mode == 0 || gemm_family(dtype, transA, transB, M, N, K, heavy_epi) != 3) return false;
+    if (!(transA && transB)) return false;
+    if (mode == 1) return true;
+    // mode 1000, measured per class (tools/gemm_wave128_ab.py, profiles/wave128_gemm_ab.json; in the step profiles/wave128_gemm_by_grid_{before,
+    // before2,after}.txt): the wgrads whose K-slices are long (more than 48 K-tiles per workgroup: the ViT and cross-K|V weight gradients, the
+    // class gemm_8ph_kernel runs on its eight-barrier schedule): 1.13 .. 1.27 x alone, -1.3 and -0.65 ms per step. The AST / decoder wgrads
+    // (37 / 20 K-tiles per workgroup) measured 1.02 x, inside the old kernel's spread: they stay on the pipelined eight-wave schedule.
+    return family3_ktiles_per_workgroup(M, N, K) > 48;
+}
+// 1 if a family-3 problem would run on gemm8q.hip under the policy in force (valor_gemm_kernel_for* keeps answering 3 for it)
+extern "C" int valor_gemm_wave128_for(int dtype, int transA, int transB, int M, int N, int K, int heavy_epilogue) {
+    return use_wave128(dtype, transA, transB, M, N, K, heavy_epilogue != 0) ? 1 : 0;
 }
 
 // which kernel family valor_gemm uses for a problem (bench.py groups its roofline numbers by this)
@@ -668,8 +700,10 @@ static int launch_gemm(hipStream_t st, int transA, int transB, GemmArgs p) {
         if (p.kslices > 1) grid = dim3(tiles * p.kslices, 1);     // split-K: 1-D grid over (slice, tile) work items
         const int fam = gemm_family(VALOR_DT_BF16, transA, transB, p.M, p.N, p.K, p.dact_aux != nullptr && !(p.act & VALOR_ACT_DERIV));
         if (fam == 4) launch_gemm_8ph2(st, transA, transB, p);
-        else if (fam == 3) launch_gemm_8ph(st, transA, transB, p);
-        else {
+        else if (fam == 3) {
+            if (use_wave128(VALOR_DT_BF16, transA, transB, p.M, p.N, p.K, p.dact_aux != nullptr && !(p.act & VALOR_ACT_DERIV))) launch_gemm_8q(st, transA, transB, p);
+            else launch_gemm_8ph(st, transA, transB, p);
+        } else {
             // policy key 6: the 128x128 kernels store big bf16 outputs of short-K problems non-temporally too (A/B hook, default off)
             p.st_mode = (gemm_policy(6) && !p.out_f32 && p.kslices <= 1 && p.K <= 1024 && (int64_t)p.M * p.N >= (4 << 20)) ? 1 : 0;
             if (gemm_variant() == 2) launch_gemm_glds<2>(st, transA, transB, p, grid);

@@ -224,6 +224,8 @@ DEVINL void epilogue_store8(const GemmArgs& p, int m, int n0, f32x4_t a0, f32x4_
 
 // 256x256 8-phase bf16 kernel (gemm8.hip). grid.x = tiles(256) * max(kslices, 1).
 void launch_gemm_8ph(hipStream_t st, int transA, int transB, const GemmArgs& p);
+// the same tile on four waves of 128x128 outputs (gemm8q.hip, policy key 12): general fp32 epilogue, results bit-identical to launch_gemm_8ph
+void launch_gemm_8q(hipStream_t st, int transA, int transB, const GemmArgs& p);
 // 256x128 8-phase bf16 kernel, two workgroups per CU (gemm8n.hip). grid.x = tiles(256 x 128) * max(kslices, 1).
 void launch_gemm_8ph2(hipStream_t st, int transA, int transB, const GemmArgs& p);
 // the same tile on 512-thread workgroups (gemm8w.hip: 64x64 outputs per wave, four waves per SIMD), NN layout without split-K; p carries
@@ -237,10 +239,10 @@ int launch_gemm_skinny(hipStream_t st, const GemmArgs& p);
 // park a pointer to it in a thread-local for the duration of the call, every read below looks there first. -1 = the process default.
 struct GemmTuning { int key[12]; int variant, tr_asm, fast_epilogue, sched_256, sched_narrow; };
 extern thread_local const GemmTuning* t_gemm_tuning;
-extern int g_gemm_policy_default[12];     // valor_gemm_set_policy (gemm.hip)
+extern int g_gemm_policy_default[13];     // valor_gemm_set_policy (gemm.hip); key 12 is a process default only (the per-call struct keeps its 17 ints)
 static inline int gemm_policy(int k) {
     const GemmTuning* o = t_gemm_tuning;
-    return (o && o->key[k] >= 0) ? o->key[k] : g_gemm_policy_default[k];
+    return (o && k < 12 && o->key[k] >= 0) ? o->key[k] : g_gemm_policy_default[k];
 }
 #define GEMM_KNOB(FIELD_, GLOBAL_) ((t_gemm_tuning && t_gemm_tuning->FIELD_ >= 0) ? t_gemm_tuning->FIELD_ : (GLOBAL_))
 int gemm_tr_asm_now();            // gemm8.hip: the transposing-read flavour / tile-epilogue mode in force for this call

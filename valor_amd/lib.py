@@ -77,6 +77,7 @@ SIGNATURES = {
     "valor_gemm_reduce_group": [_vp, _i, _vp, _i],
     "valor_gemm_set_variant": [_i],
     "valor_gemm_kernel_for": [_i, _i, _i, _i, _i, _i, _i],
+    "valor_gemm_wave128_for": [_i, _i, _i, _i, _i, _i, _i],
     "valor_gemm_set_tr_asm": [_i],
     "valor_gemm_set_fast_epilogue": [_i],
     "valor_gemm_set_policy": [_i, _i],
