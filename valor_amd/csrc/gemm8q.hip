@@ -8,7 +8,35 @@
 // The WAVE (wm, wn) owns rows {128 mh + 64 wm + [0,64)} x columns {128 nh + 64 wn + [0,64)}, mh, nh in {0,1}: a 64x64 piece of every
 // quadrant (A'mh, B'nh), so a half-tile is consumed by all four waves in one phase and its slot is dead right after.
 //
-// K loop: four phases per K-tile, one quadrant of 32 MFMAs each, in the order (0,0) (0,1) (1,1) (1,0), MFMA i = 16 kk + 4 mt + nt. With
+// K loop of the k-slow x k-slow layout (the weight gradients, the only layout the launcher is given): EIGHT SLOTS of 16 MFMAs per K-tile,
+// slot s = 2 q + kk of quadrant q in the order (0,0) (0,1) (1,0) (1,1), MFMA i = 4 mt + nt. Where the time of the four-phase loop below
+// went was measured with cycle stamps and ablation builds (Q8_STAMP / Q8_ABLATE): not in its waits but in ISSUE. An MFMA
+// 16x16x32 leaves 8 of its 16 cycles to other instructions, and two transposing reads plus the address add in front of them do not fit.
+// So here ONE ds_read_b64_tr_b16 goes behind an MFMA, its half-tile and k-half in the offset field, from eight per-lane address registers
+// per buffer that change buffers by 16 adds in the one slot without reads. Register sets as below (FAX = A'0, FAY = A'1, FB0, FB1), by k-halves:
+//   slot  MFMAs            reads behind MFMAs 0-7 (s0, s6: 0-15)       DMA behind MFMAs 9, 13   end of slot
+//   s0    A'0 k0 x B'0 k0  FB1 k0, k1 <- B'1(c)                        A'0(c+2) 0, 1            -
+//   s1    A'0 k1 x B'0 k1  FAY k0 <- A'1(c)                            A'0(c+2) 2, 3            lgkmcnt(8): FB1
+//   s2    A'0 k0 x B'1 k0  FAY k1 <- A'1(c)                            B'0(c+2) 0, 1            lgkmcnt(8): FAY k0
+//   s3    A'0 k1 x B'1 k1  -                                           B'0(c+2) 2, 3            lgkmcnt(0): FAY k1; vmcnt(16); barrier
+//   s4    A'1 k0 x B'0 k0  FAX k0 <- A'0(c+1)                          B'1(c+2) 0, 1            -
+//   s5    A'1 k1 x B'0 k1  FAX k1 <- A'0(c+1)                          B'1(c+2) 2, 3            lgkmcnt(8): FAX k0
+//   s6    A'1 k0 x B'1 k0  FB0 k0, k1 <- B'0(c+1)                      A'1(c+2) 0, 1            lgkmcnt(15): FAX k1
+//   s7    A'1 k1 x B'1 k1  - (the 16 address adds)                     A'1(c+2) 2, 3            lgkmcnt(0): FB0; vmcnt(16); barrier
+// Registers: a k-half is read at the earliest in the slot after its last MFMA (FB1 k0 / k1 after s6 / s7, FAY after s6 / s7, FAX k0 / k1
+// after s2 / s3, FB0 k0 / k1 after s4 / s5) and first multiplied two slots or more after the slot that read it; the wait that ties it sits one
+// slot after its reads and leaves that slot's own reads in flight (LDS reads return in order), so no wait is closer than 9 MFMAs to what it
+// waits for, and nothing is in flight where two K-tiles meet. WAR on a half-tile slot: B'1(c) and A'1(c) are read in s0 - s2 and complete
+// in every wave at the end of s3, the barrier there opens their refill in s4 - s7; A'0(c+1) and B'0(c+1) are read in s4 - s6 and complete
+// at the end of s7, its barrier opens their refill in s0 - s3 of the next K-tile. RAW: pieces go out in the order A'0 B'0 B'1 A'1 of a
+// K-tile, two per slot. At the barrier of s3 the 16 youngest pieces of a wave are B'1(c+1), A'1(c+1), A'0(c+2) and B'0(c+2): what is older
+// -- A'0(c+1), read from s4, and B'0(c+1), read in s6 -- has landed in every wave behind vmcnt(16) and the barrier; at the barrier of s7 the 16
+// youngest are A'0(c+2), B'0(c+2), B'1(c+2) and A'1(c+2), so B'1(c+1) and A'1(c+1), read in s0 - s2 of the next K-tile, have landed.
+// The look-ahead is eight slots behind a half-tile's last piece (the four-phase loop: nine). Past the last K-tile a zero-length descriptor keeps
+// the counts; the prologue issues K-tiles 0 and 1 in that order and waits for all of K-tile 0.
+//
+// The other layouts keep the first order of this kernel (nobody launches them): four phases per K-tile, one quadrant of 32 MFMAs each, in
+// the order (0,0) (0,1) (1,1) (1,0), MFMA i = 16 kk + 4 mt + nt. With
 // one wave per SIMD nobody else fills the issue slots, so every phase carries, BETWEEN its MFMAs, the fragment reads a later phase needs
 // and the four 1 KiB LDS-DMA pieces of one half-tile; it ends in lgkmcnt(0), a counted vmcnt and ONE barrier. Four register sets of
 // 32 (FAX = A'0, FAY = A'1, FB0, FB1) next to the 256 accumulators; B'0 is multiplied in the first and the last phase, so its set is
@@ -29,6 +57,7 @@
 // Requirements as for gemm_8ph_kernel: K % 64 == 0; M / N tails by the buffer range check (zero fill) and masked stores.
 #include "gemm_common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 #define HT_BYTES 16384
 #define BUF_BYTES (4 * HT_BYTES)
@@ -64,9 +93,59 @@ DEVINL void wait8(FragSet<true>& s) { tr_wait8(s.f); }
 DEVINL void wait4(FragSet<false>&, int) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 DEVINL void wait4(FragSet<true>& s, int kk) { tr_wait_4(s.f[0][kk], s.f[1][kk], s.f[2][kk], s.f[3][kk]); }
 
+// the reads into k-half kk of a set, issued a slot (16 MFMAs) before the NEWER youngest LDS reads of the wave, are complete: LDS reads return
+// in order, so all but those have returned
+template <int NEWER> DEVINL void wait4_older(FragSet<true>& s, int kk) {
+    asm volatile("s_waitcnt lgkmcnt(%8)" : TR_TIE(s.f[0][kk]), TR_TIE(s.f[1][kk]), TR_TIE(s.f[2][kk]), TR_TIE(s.f[3][kk]) : "n"(NEWER));
+}
+
+// f(integral_constant<int, I>) for I = FIRST .. LAST - 1: the index is a constant expression in the body (asm immediates)
+template <int FIRST, int LAST, class F> DEVINL void static_for(F&& f) {
+    if constexpr (FIRST < LAST) {
+        f(std::integral_constant<int, FIRST>{});
+        static_for<FIRST + 1, LAST>(f);
+    }
+}
+// ONE transposing read of k-half KK of a set: J = 2 * block + half (0 = lo, 1 = hi) from the per-lane address of that block in its K-tile
+// buffer; where the half-tile and the k-half start goes into the instruction's offset field (no address arithmetic in the loop)
+template <int HT_OFF, int KK, int J> DEVINL void tr_read1(FragSet<true>& s, const uint32_t (&ad)[4]) {
+    if constexpr (J & 1) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(s.f[J >> 1][KK].hi) : "v"(ad[J >> 1]), "n"(HT_OFF + KK * (32 * 256) + 1024));
+    else asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(s.f[J >> 1][KK].lo) : "v"(ad[J >> 1]), "n"(HT_OFF + KK * (32 * 256)));
+}
+
+#ifdef Q8_STAMP
+// diagnostic build only (tools/build_stamp_lib.sh, tools/gemm8q_stamp.py): cycle stamps of every wave, [block][wave][64] uint64 in a buffer of
+// their own: [0..5] kernel entry / prologue done / K loop done / drained / epilogue pass 0 / pass 1, [6..7] s_memrealtime around the loop,
+// [8] HW_ID, [9] XCC_ID, [10] K-tiles, [11] 1 = slot order, [16..] the boundaries inside K-tile Q8_STAMP_TILE in program order
+#define Q8_STAMP_TILE 5
+#define Q8_STAMP_BLOCKS 1024
+__device__ uint64_t q8_stamp_buf[Q8_STAMP_BLOCKS * 4 * 64];
+extern "C" int valor_gemm8q_read_stamps(void* host, int64_t bytes) {
+    if (bytes > (int64_t)sizeof(uint64_t) * Q8_STAMP_BLOCKS * 4 * 64) return VALOR_ERR_ARG;
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(q8_stamp_buf), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : VALOR_ERR_ARG;
+}
+#define Q8_AT(i) st_[i] = __builtin_amdgcn_s_memtime()
+#define Q8_HS(i) do { if (rel == Q8_STAMP_TILE) hs_[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define Q8_AT(i)
+#define Q8_HS(i)
+#endif
+// ablation builds of the diagnostic library: bit 0 = no DMA in the K loop, bit 1 = no fragment reads in the K loop (results are garbage)
+#ifndef Q8_ABLATE
+#define Q8_ABLATE 0
+#endif
+
+// The k-slow x k-slow layout (the only one the launcher is given today) runs the slot order, the other layouts keep the four phases
 template <bool TA, bool TB>
 __global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
     typedef bf16_t T;
+    constexpr bool SLOTS = TA && TB;
+#ifdef Q8_STAMP
+    uint64_t st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hs_[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) hs_[i] = 0;
+    Q8_AT(0);
+#endif
     constexpr int BK = 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -220,8 +299,12 @@ __global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
         PIN();                                                                                                    \
     } while (0)
 
+#define LOOP_DMA(...) do { if constexpr (!(Q8_ABLATE & 1)) { __VA_ARGS__; } } while (0)
+#define LOOP_RD(...) do { if constexpr (!(Q8_ABLATE & 2)) { __VA_ARGS__; } } while (0)
+
     FragSet<TA> fax, fay;      // A'0, A'1
     FragSet<TB> fb0, fb1;      // B'0, B'1
+    if constexpr (!SLOTS) {
     if (ntile > 0) {
         // prologue = what the phases before tile 0 would have issued, in their order: A'0(0) B'0(0) B'1(0) A'1(0) A'0(1) B'0(1) B'1(1)
         // A'1(1) = 32 pieces; with 20 in flight A'0(0), B'0(0) and B'1(0) have landed
@@ -290,11 +373,130 @@ __global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
             PHASE_END();
         }
     }
+    } else {
+    if (ntile > 0) {
+        // end of slot s: `tie` waits for the k-half(s) read in slot s - 1, which is at least 9 MFMAs behind by then; nfly > 0: a barrier
+        // slot, what was issued more than nfly pieces ago has landed
+#define SLOT_END(s, tie, nfly)                                                                                    \
+    do {                                                                                                          \
+        Q8_HS(1 + 2 * (s));                                                                                       \
+        tie;                                                                                                      \
+        PIN();                                                                                                    \
+        if constexpr ((nfly) > 0) {                                                                               \
+            Q8_HS(17 + 2 * ((s) >> 1));                                                                           \
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(nfly) : "memory");                                           \
+            Q8_HS(18 + 2 * ((s) >> 1));                                                                           \
+            __builtin_amdgcn_s_barrier();                                                                         \
+            PIN();                                                                                                \
+        }                                                                                                         \
+        Q8_HS(2 + 2 * (s));                                                                                       \
+    } while (0)
+        // prologue = what the slots before K-tile 0 would have issued, in their order: A'0 B'0 B'1 A'1 of K-tiles 0 and 1; K-tile 0 has
+        // landed, K-tile 1 stays in flight
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            char* const b = smem + t * BUF_BYTES;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dmaA(0, b, t, i);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dmaB(0, b, t, i);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dmaB(1, b, t, i);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dmaA(1, b, t, i);
+        }
+        PIN();
+        asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        PIN();
+        // what the second half of a K-tile before the first would have read: A'0(0) and B'0(0); behind the barrier that follows, their
+        // slots may be refilled
+#pragma unroll
+        for (int i = 0; i < 8; ++i) rdA(smem + OFF_A0, fax, i & 3, i >> 2);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) rdB(smem + OFF_B0, fb0, i & 3, i >> 2);
+        PIN();
+        wait8(fax); wait8(fb0);
+        __builtin_amdgcn_s_barrier();
+        PIN();
+        Q8_AT(1);
+#ifdef Q8_STAMP
+        st_[6] = __builtin_amdgcn_s_memrealtime();
+#endif
+        // the per-lane read addresses of the four A and B blocks in the K-tile's buffer (ad*) and in the other one (an*)
+        uint32_t adA[4], adB[4], anA[4], anB[4];
+        int adelta = BUF_BYTES;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            adA[i] = (uint32_t)(uintptr_t)LDS_PTR(smem) + trA[i];
+            adB[i] = (uint32_t)(uintptr_t)LDS_PTR(smem) + trB[i];
+            anA[i] = adA[i] + BUF_BYTES;
+            anB[i] = adB[i] + BUF_BYTES;
+        }
+        // 16 MFMAs of a slot with `gap(integral_constant i)` behind MFMA i
+        auto slot = [&](int mh, int nh, int kk, FragSet<true>& sa, FragSet<true>& sb, auto&& gap) __attribute__((always_inline)) {
+            static_for<0, 16>([&](auto ic) __attribute__((always_inline)) {
+                constexpr int i = decltype(ic)::value;
+                mfma_acc(acc[mh * 4 + (i >> 2)][nh * 4 + (i & 3)], frag_of(sb.f[i & 3][kk]), frag_of(sa.f[i >> 2][kk]));
+                gap(ic);
+                PIN();
+            });
+        };
+        for (int rel = 0; rel < ntile; ++rel) {
+            char* const cur = smem + (rel & 1) * BUF_BYTES;
+            char* const nxt = smem + ((rel & 1) ^ 1) * BUF_BYTES;
+            Q8_HS(0);
+            {
+                // behind MFMA i of a slot: the read(s) the variadic part names for gap i, DMA pieces d0 / d1 behind MFMAs 9 / 13
+#define GAP(d0, d1, ...)                                                                                          \
+    [&](auto ic) __attribute__((always_inline)) {                                                                 \
+        constexpr int i = decltype(ic)::value;                                                                    \
+        LOOP_RD(__VA_ARGS__);                                                                                     \
+        if constexpr (i == 9) LOOP_DMA(d0);                                                                       \
+        if constexpr (i == 13) LOOP_DMA(d1);                                                                      \
+    }
+                slot(0, 0, 0, fax, fb0, GAP(dmaA(0, cur, rel + 2, 0), dmaA(0, cur, rel + 2, 1), if constexpr (i < 8) tr_read1<OFF_B1, 0, (i & 7)>(fb1, adB); else tr_read1<OFF_B1, 1, (i & 7)>(fb1, adB)));
+                SLOT_END(0, (void)0, 0);
+                slot(0, 0, 1, fax, fb0, GAP(dmaA(0, cur, rel + 2, 2), dmaA(0, cur, rel + 2, 3), if constexpr (i < 8) tr_read1<OFF_A1, 0, (i & 7)>(fay, adA)));
+                rowsum(0, fax);
+                SLOT_END(1, (wait4_older<8>(fb1, 0), wait4_older<8>(fb1, 1)), 0);
+                slot(0, 1, 0, fax, fb1, GAP(dmaB(0, cur, rel + 2, 0), dmaB(0, cur, rel + 2, 1), if constexpr (i < 8) tr_read1<OFF_A1, 1, (i & 7)>(fay, adA)));
+                SLOT_END(2, wait4_older<8>(fay, 0), 0);
+                slot(0, 1, 1, fax, fb1, GAP(dmaB(0, cur, rel + 2, 2), dmaB(0, cur, rel + 2, 3), (void)0));
+                SLOT_END(3, wait4(fay, 1), 16);
+                slot(1, 0, 0, fay, fb0, GAP(dmaB(1, cur, rel + 2, 0), dmaB(1, cur, rel + 2, 1), if constexpr (i < 8) tr_read1<OFF_A0, 0, (i & 7)>(fax, anA)));
+                SLOT_END(4, (void)0, 0);
+                slot(1, 0, 1, fay, fb0, GAP(dmaB(1, cur, rel + 2, 2), dmaB(1, cur, rel + 2, 3), if constexpr (i < 8) tr_read1<OFF_A0, 1, (i & 7)>(fax, anA)));
+                rowsum(1, fay);
+                SLOT_END(5, wait4_older<8>(fax, 0), 0);
+                slot(1, 1, 0, fay, fb1, GAP(dmaA(1, cur, rel + 2, 0), dmaA(1, cur, rel + 2, 1), if constexpr (i < 8) tr_read1<OFF_B0, 0, (i & 7)>(fb0, anB); else tr_read1<OFF_B0, 1, (i & 7)>(fb0, anB)));
+                SLOT_END(6, wait4_older<15>(fax, 1), 0);
+                // no reads in the last slot: the addresses change buffers here, two per gap
+                slot(1, 1, 1, fay, fb1, [&](auto ic) __attribute__((always_inline)) {
+                    constexpr int i = decltype(ic)::value;
+                    if constexpr (i < 2) { adA[2 * i] += adelta; adA[2 * i + 1] += adelta; }
+                    else if constexpr (i < 4) { adB[2 * i - 4] += adelta; adB[2 * i - 3] += adelta; }
+                    else if constexpr (i < 6) { anA[2 * i - 8] -= adelta; anA[2 * i - 7] -= adelta; }
+                    else if constexpr (i < 8) { anB[2 * i - 12] -= adelta; anB[2 * i - 11] -= adelta; }
+                    if constexpr (i == 8) { adelta = -adelta; asm volatile("" : "+s"(adelta)); }
+                    if constexpr (i == 9) LOOP_DMA(dmaA(1, cur, rel + 2, 2));
+                    if constexpr (i == 13) LOOP_DMA(dmaA(1, cur, rel + 2, 3));
+                });
+                SLOT_END(7, wait8(fb0), 16);
+#undef GAP
+            }
+        }
+#undef SLOT_END
+    }
+    }
+#ifdef Q8_STAMP
+    st_[7] = __builtin_amdgcn_s_memrealtime();
+#endif
+    Q8_AT(2);
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_waitcnt vmcnt(0)" ::: "memory");     // the last MFMAs have written back; drain the look-ahead loads before LDS is reused
     PIN();
     __syncthreads();
-#undef PHASE_END
-#undef PIN
+    Q8_AT(3);
     if (do_rs && fg == 0) {     // racc[h][i][*] = sum_k A(m, k) for m = m0 + 128h + 64wm + 16(2wn + i) + fr
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh)
@@ -339,7 +541,26 @@ __global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
                 epilogue_store8<true, 0>(p, m, n, v0, v1, bias0, bias1);
             }
         }
+#ifdef Q8_STAMP
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        st_[4 + pass] = __builtin_amdgcn_s_memtime();
+#endif
     }
+#ifdef Q8_STAMP
+    if (lane == 0 && blockIdx.x < Q8_STAMP_BLOCKS) {
+        uint64_t* o = q8_stamp_buf + ((int64_t)blockIdx.x * 4 + wave) * 64;
+        for (int i = 0; i < 8; ++i) o[i] = st_[i];
+        o[8] = __builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_ID
+        o[9] = __builtin_amdgcn_s_getreg((31 << 11) | 20);      // XCC_ID
+        o[10] = ntile;
+        o[11] = SLOTS;
+        for (int i = 0; i < 32; ++i) o[16 + i] = hs_[i];
+    }
+#endif
+#undef PHASE_END
+#undef LOOP_DMA
+#undef LOOP_RD
+#undef PIN
 }
 
 void launch_gemm_8q(hipStream_t st, int transA, int transB, const GemmArgs& p_in) {
@@ -350,7 +571,7 @@ void launch_gemm_8q(hipStream_t st, int transA, int transB, const GemmArgs& p_in
     const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
     dim3 grid(tiles * (p.kslices > 1 ? p.kslices : 1));
     const size_t lds = 2 * BUF_BYTES;
-#define VALOR_8Q_LAUNCH(TA_, TB_)                                                                               \
+#define VALOR_8Q_LAUNCH(TA_, TB_)                                                                             \
     do {                                                                                                        \
         static bool attr_set = false;                                                                           \
         if (!attr_set) {                                                                                        \
