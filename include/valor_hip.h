@@ -560,6 +560,45 @@ int valor_decode_prologue(void* stream, int dtype, const int64_t* tok, const int
 int valor_beam_select(void* stream, const float* logits, int64_t ld, int64_t row_stride_s, int64_t row_stride_k, const float* lse,
                       const float* seq_logprob, const float* seq_mask, int b, int cur, int V, int beam, float* sel_val,
                       int64_t* sel_idx, float* lse_out);
+/* one step of the beam search with a pool of finished hypotheses (csrc/beam_pool.hip; valor_amd.decode.beam_pool_step_host restates
+ * this law on the host, bit for bit): selection, pool update, history reorder and the next step's inputs in one launch. K = beam <= 8,
+ * L = max_len <= 512, step t in [0, L). Per sample s (rows of the decoder are beam-major, r = k * b + s; the state is (sample, slot)):
+ *   scores_in [b, K] fp32: the summed log-probability c_k of slot k; -inf marks a DEAD slot (a live slot is always above -inf). Only the
+ *   slots k < cur are read (cur = 1 at step 0). hist_in / hist_out int64 [b, K, L]: the words so far, a ping-pong pair (never the same
+ *   buffer). inv_len fp32 [L + 1]: inv_len[l] = 1 / l^alpha rounded to fp32 by the caller (inv_len[0] = 1); the RANK score of a
+ *   hypothesis of summed log-probability c and length l is the fp32 product c * inv_len[l]. The pool, at most K entries per sample:
+ *   pool_seq int64 [b, K, L] (padded with eos), pool_logprob / pool_rank fp32 [b, K], pool_len / pool_ins int32 [b, K] (length; insertion
+ *   number), pool_cnt int32 [b, 2] = (entries held, insertions so far); the entries held are the slots 0 .. pool_cnt[s, 0] - 1.
+ *   done uint8 [b].
+ * A sample with done[s] != 0 is frozen: tok = eos, parent = the row itself, scores_out = scores_in, hist_out = hist_in, active = 0, the
+ * pool untouched. Otherwise:
+ *   1. candidates c(k, w) = scores_in[s, k] + (logits[row, w] - lse[row]) in fp32, in that order, for every live slot k < cur and every
+ *      w < V with logits[row, w] > floor; row = s * row_stride_s + k * row_stride_k, row pitch ld, lse[row] the caller's log-sum-exp of
+ *      the row (valor_xent_fwd's). floor: -inf, or VALOR_TRIE_FLOOR when valor_trie_constrain masked the rows (a floored column is no
+ *      continuation: inside an answer set a sample may run out of open hypotheses, and its pool may hold fewer than K).
+ *   2. the 2K best, value descending, equal values in order of the index k * V + w; a candidate equal to -inf (or NaN) is never taken.
+ *   3. they are walked in rank order rho = 0, 1, .. until K new slots are filled or the list ends: w == eos offers (words of k + eos, c,
+ *      length t + 1) to the pool when rho < K and is skipped otherwise; w != eos fills the next new slot (parent k, token w, score c), and
+ *      at t == L - 1 is offered to the pool besides (words of k + w, c, length L).
+ *   4. an offer is appended while the pool holds fewer than K entries; a full pool replaces its worst entry -- the lowest rank score,
+ *      among equal ones the newest -- only when the offer's rank score is strictly greater.
+ *   5. the slots left unfilled are dead: score -inf, token eos, parent = the slot itself.
+ *   6. t < L - 1: done[s] = 1 when no new slot was filled, or when the pool holds K entries and (early_stopping != 0 or
+ *      worst rank >= c_0 * inv_len[alpha_pos ? L : t + 2], c_0 = the score of new slot 0: the bound of what an open hypothesis can
+ *      still reach, exact for log-probabilities <= 0). t == L - 1: done[s] = 1 (the search is over).
+ *   7. out: scores_out [b, K]; hist_out[s, j, :] = hist_in[s, parent slot of j, :] with position t = the slot's token; tok / parent
+ *      int64 [K * b] beam-major (parent = parent slot * b + s) for the next decoding step; active uint8 [K, b] = the slot is live and
+ *      the sample is not done (the rows the next step's valor_logits_constrain / valor_trie_constrain act on).
+ * b == 0: no-op. VALOR_ERR_ARG, before any launch: a null pointer, hist_in == hist_out, b < 0, beam outside 1..8, cur outside 1..beam,
+ * V < 1, ld < V, a negative row stride, cur * V < 2 * beam or >= 2^31 - 1, max_len outside 1..512, t outside [0, max_len), eos outside
+ * [0, V), a NaN floor. One 1024-thread workgroup per sample reads its cur rows once (every thread keeps the best 2K of its stride in registers, then
+ * 2K rounds of a workgroup-wide arg max); the walk and the pool update run on one thread, the history and pool rows are copied by all.
+ * No atomics, no workspace, vector stores only: the result is a pure function of the inputs, graph replay equals eager issue. */
+int valor_beam_pool_step(void* stream, const float* logits, int64_t ld, int64_t row_stride_s, int64_t row_stride_k, const float* lse,
+                         const float* scores_in, const int64_t* hist_in, const float* inv_len, int b, int cur, int V, int beam, int max_len,
+                         int t, int64_t eos, float floor, int alpha_pos, int early_stopping, float* scores_out, int64_t* hist_out,
+                         int64_t* tok, int64_t* parent, uint8_t* active, int64_t* pool_seq, float* pool_logprob, float* pool_rank, int32_t* pool_len,
+                         int32_t* pool_ins, int32_t* pool_cnt, uint8_t* done);
 /* one step of the sampled caption decode, VALOR.decode_greedy mode 'sample' (pretrain.py:1007-1020): per row r < R of fp32 logits
  * [R, V] (row pitch ld >= V) with unfinished[r] != 0, the draw w = argmax_w (z_w - log(-log u_w)) (Gumbel-max: w ~ softmax(z);
  * u_w = (x >> 9) 2^-23 + 2^-24 (exact, in (0, 1)), x = Philox4x32-10(seed, offset + r * ceil(V / 4) + w / 4) word w % 4; ties to the

@@ -38,6 +38,11 @@ returns the exact sequence log-probability of every candidate by forced decoding
 a whole shared set exactly, level by level over the trie: one decoder row per trie node, a node's logits row scoring all its children
 (valor_trie_score_level; `trie_level_host` is its law on the host).
 
+`decode_beam` restates the reference's beam rule (an ended beam stays in the beam). `decode_beam_pool` (beam_search='pool') is the search
+with a pool of finished hypotheses: the beam stays `beam` OPEN hypotheses wide, length_penalty ranks while the search runs, the n best
+are returned and the loop leaves early; one valor_beam_pool_step launch per step does the selection, the pool update, the history
+reorder and the next step's inputs (`beam_pool_step_host` / `decode_beam_pool_host` are its law on the host, bit for bit).
+
 Everything here is inference: torch.no_grad, dropout off regardless of model.training (the reference calls it under model.eval())."""
 import contextlib
 import gc
@@ -910,6 +915,290 @@ def decode_beam(source, b, beam, max_len, constraints=None, candidates=None):
     return outputs.contiguous()[:, 0]
 
 
+# ------------------------------------------------------------------------------------------------ beam search with a finished-hypothesis pool
+POOL_MAX_BEAM = 8                        # valor_beam_pool_step keeps 2 * beam candidates per thread in registers
+_NO_INS = 2 ** 31 - 1                    # the insertion number of an empty pool entry
+
+
+def inv_length_table(max_len, alpha):
+    """inv[l] = 1 / l^alpha for l = 0 .. max_len (inv[0] = 1), computed in fp64 and rounded to fp32 once: the rank score of a hypothesis
+    is the fp32 PRODUCT logP * inv[length], the same bits on the host and in the kernel (no powf, no division on the device)."""
+    def one(l):
+        try:
+            return 1.0 / float(l) ** alpha
+        except OverflowError:
+            return 0.0
+        except ZeroDivisionError:
+            return float("inf")
+    return torch.tensor([1.0] + [one(l) for l in range(1, max_len + 1)], dtype=torch.float64).to(torch.float32)
+
+
+def _check_pool(who, b, beam, max_len, n_best=1, V=None, cur=None, t=None, eos=None):
+    if int(beam) != beam or not 1 <= beam <= POOL_MAX_BEAM:
+        raise ValueError(f"{who}: beam {beam!r} outside 1 .. {POOL_MAX_BEAM} (valor_beam_pool_step)")
+    if int(n_best) != n_best or not 1 <= n_best <= beam:
+        raise ValueError(f"{who}: n_best {n_best!r} outside 1 .. beam = {beam} (the pool holds `beam` finished hypotheses)")
+    if int(max_len) != max_len or not 1 <= max_len <= 512:
+        raise ValueError(f"{who}: max_len {max_len!r} outside 1 .. 512")
+    if b < 0:
+        raise ValueError(f"{who}: b = {b!r}")
+    if V is not None:
+        if not 1 <= cur <= beam:
+            raise ValueError(f"{who}: cur {cur!r} outside 1 .. beam = {beam}")
+        if cur * V < 2 * beam:
+            raise ValueError(f"{who}: {cur} rows of {V} words hold fewer than 2 * beam = {2 * beam} candidates")
+        if cur * V >= 2 ** 31 - 1:
+            raise ValueError(f"{who}: {cur} x {V} candidates do not fit a 32-bit index")
+        if not 0 <= t < max_len:
+            raise ValueError(f"{who}: step {t!r} outside [0, max_len = {max_len})")
+        if not 0 <= eos < V:
+            raise ValueError(f"{who}: [SEP] = {eos!r} is no column of {V}")
+
+
+class PoolState:
+    """The arrays of one pool search (valor_beam_pool_step, include/valor_hip.h), on one device. Per sample: `beam` slots -- scores [b, beam]
+    (-inf: a dead slot) and hist int64 [b, beam, max_len], each a ping-pong pair: step t reads [t % 2] and writes [(t + 1) % 2] -- the
+    pool of at most `beam` finished hypotheses (pool_seq, pool_logprob, pool_rank, pool_len, pool_ins, pool_cnt = (entries, insertions)),
+    `done` [b], `floor` (a logit at or below it is no continuation: -inf, or TRIE_FLOOR inside an answer set), and what a step leaves for the next one: tok / parent int64 [beam * b] beam-major, active uint8 [beam, b]."""
+    FIELDS = ("scores", "hist", "inv", "pool_seq", "pool_logprob", "pool_rank", "pool_len", "pool_ins", "pool_cnt", "done", "tok", "parent",
+              "active")
+
+    def __init__(self, b, beam, max_len, alpha=0.0, device="cpu", eos=None, floor=-float("inf")):
+        _check_pool("PoolState", b, beam, max_len)
+        self.floor = float(floor)                      # TRIE_FLOOR inside an answer set: a floored column is no continuation
+        self.b, self.beam, self.max_len, self.alpha = int(b), int(beam), int(max_len), float(alpha)
+        self.eos = EOS if eos is None else int(eos)
+        ninf = -float("inf")
+        mk = lambda shape, fill, dt: torch.full(shape, fill, dtype=dt, device=device)
+        self.scores = [mk((b, beam), ninf, torch.float32) for _ in range(2)]
+        self.scores[0][:, 0] = 0.0
+        self.hist = [mk((b, beam, max_len), 0, torch.int64) for _ in range(2)]
+        self.inv = inv_length_table(max_len, self.alpha).to(device)
+        self.pool_seq = mk((b, beam, max_len), self.eos, torch.int64)
+        self.pool_logprob, self.pool_rank = mk((b, beam), ninf, torch.float32), mk((b, beam), ninf, torch.float32)
+        self.pool_len, self.pool_ins = mk((b, beam), 0, torch.int32), mk((b, beam), _NO_INS, torch.int32)
+        self.pool_cnt = mk((b, 2), 0, torch.int32)
+        self.done = mk((b,), 0, torch.uint8)
+        self.tok, self.parent = mk((beam * b,), self.eos, torch.int64), torch.arange(beam * b, dtype=torch.int64, device=device)
+        self.active = mk((beam, b), 0, torch.uint8)
+
+    def to(self, device):
+        """a copy on `device`"""
+        import copy
+        out = copy.copy(self)
+        for k in self.FIELDS:
+            v = getattr(self, k)
+            setattr(out, k, [x.to(device, copy=True) for x in v] if isinstance(v, list) else v.to(device, copy=True))
+        return out
+
+    def arrays(self):
+        """{name: host tensor} of every array (the pairs as name0 / name1): what a comparison walks"""
+        out = {}
+        for k in self.FIELDS:
+            v = getattr(self, k)
+            for i, x in enumerate(v if isinstance(v, list) else [v]):
+                out[k + (str(i) if isinstance(v, list) else "")] = x.detach().cpu()
+        return out
+
+    def result(self, n_best):
+        """the pool sorted by rank score descending, equal scores by earlier insertion -> (seqs int64 [b, n, L], rank fp32 [b, n],
+        logprob fp32 [b, n], length int64 [b, n]); a missing entry is an all-[SEP] row with rank and logprob -inf and length 0"""
+        n, L = int(n_best), self.max_len
+        by_age = torch.sort(self.pool_ins, dim=1, stable=True)[1]
+        order = torch.gather(by_age, 1, torch.sort(torch.gather(self.pool_rank, 1, by_age), dim=1, descending=True, stable=True)[1])[:, :n]
+        seqs = torch.gather(self.pool_seq, 1, order[:, :, None].expand(self.b, n, L))
+        return (seqs.contiguous(), torch.gather(self.pool_rank, 1, order), torch.gather(self.pool_logprob, 1, order),
+                torch.gather(self.pool_len, 1, order).to(torch.int64))
+
+
+def beam_pool_step(logits, lse, state, t, cur, early_stopping=False, beam_major=True):
+    """one step of the pool search in ONE launch (valor_beam_pool_step; the law: include/valor_hip.h, restated by beam_pool_step_host):
+    logits fp32 [b * cur, V] (unit column stride; rows beam-major r = k * b + s, or sample-major r = s * cur + k), lse fp32 [b * cur]
+    (the rows' log-sum-exp as the caller has it: row_lse), state: a PoolState on the logits' device, updated in place (scores / hist
+    [(t + 1) % 2], tok, parent, active, the pool, done). Anything the kernel cannot do raises ValueError: there is no torch path."""
+    st = state
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError("beam_pool_step: logits fp32 [rows, V] with unit column stride and lse fp32 [rows]")
+    V = logits.shape[1]
+    _check_pool("beam_pool_step", st.b, st.beam, st.max_len, 1, V, cur, t, st.eos)
+    if logits.shape[0] != st.b * cur or lse.numel() != st.b * cur:
+        raise ValueError(f"beam_pool_step: {logits.shape[0]} rows / {lse.numel()} lse values for b * cur = {st.b * cur}")
+    K._check_gpu(logits, lse, st.done)
+    i, o = t % 2, (t + 1) % 2
+    rs_s, rs_k = (1, st.b) if beam_major else (cur, 1)
+    lib.call("valor_beam_pool_step", _st(), logits.data_ptr(), logits.stride(0), rs_s, rs_k, lse.data_ptr(), st.scores[i].data_ptr(),
+             st.hist[i].data_ptr(), st.inv.data_ptr(), st.b, cur, V, st.beam, st.max_len, t, st.eos, st.floor, int(st.alpha > 0.0), int(bool(early_stopping)),
+             st.scores[o].data_ptr(), st.hist[o].data_ptr(), st.tok.data_ptr(), st.parent.data_ptr(), st.active.data_ptr(),
+             st.pool_seq.data_ptr(), st.pool_logprob.data_ptr(), st.pool_rank.data_ptr(), st.pool_len.data_ptr(), st.pool_ins.data_ptr(),
+             st.pool_cnt.data_ptr(), st.done.data_ptr())
+    return st
+
+
+def beam_pool_step_host(logits, lse, state, t, cur, early_stopping=False, beam_major=True):
+    """THE LAW of one step of the pool search (include/valor_hip.h, valor_beam_pool_step), on the host in fp32: beam_pool_step's
+    arguments with a PoolState of host tensors, updated in place; logits / lse may live anywhere and are not modified. Every value
+    is one rounded fp32 operation in the kernel's order -- c = c_k + (z - lse), rank = c * inv[length], the bound c_0 * inv[..] --
+    so the kernel agrees with it bit for bit. The early-exit bound (rule 6) is the usual one taken literally: the best an open
+    hypothesis can still reach is its own score at the most favourable length, which is exact only while every further
+    log-probability is <= 0 (true of log-softmax rows; inside an answer set the scores are those of the unmasked rows, also <= 0)."""
+    st = state
+    z = logits.detach().to(device="cpu", dtype=torch.float32)
+    l = lse.detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    b, K_, L, eos = st.b, st.beam, st.max_len, st.eos
+    V = z.shape[1]
+    _check_pool("beam_pool_step_host", b, K_, L, 1, V, cur, t, eos)
+    if z.shape[0] != b * cur or l.numel() != b * cur:
+        raise ValueError(f"beam_pool_step_host: {z.shape[0]} rows / {l.numel()} lse values for b * cur = {b * cur}")
+    i, o = t % 2, (t + 1) % 2
+    sc_in, sc_out, h_in, h_out = st.scores[i], st.scores[o], st.hist[i], st.hist[o]
+    ninf = -float("inf")
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32)
+    for s in range(b):
+        if bool(st.done[s]):                                         # rule 7: frozen
+            sc_out[s], h_out[s] = sc_in[s], h_in[s]
+            for k in range(K_):
+                st.tok[k * b + s], st.parent[k * b + s], st.active[k, s] = eos, k * b + s, 0
+            continue
+        cand = torch.full((cur, V), ninf, dtype=torch.float32)
+        for k in range(cur):
+            if float(sc_in[s, k]) > ninf:                            # rule 1 (a dead slot supplies nothing)
+                r = k * b + s if beam_major else s * cur + k
+                cand[k] = torch.where(z[r] > st.floor, sc_in[s, k] + (z[r] - l[r]), f32(ninf))
+        flat = cand.reshape(-1)
+        flat = torch.where(flat.isnan(), f32(ninf), flat)
+        val, idx = torch.sort(flat, descending=True, stable=True)    # rule 2: value descending, equal values in index order
+        taken = [(val[j].clone(), int(idx[j])) for j in range(min(2 * K_, flat.numel())) if float(val[j]) > ninf]
+        pn, pnext = int(st.pool_cnt[s, 0]), int(st.pool_cnt[s, 1])
+        slots = []                                                   # (score, parent slot, token)
+        for rho, (c, ix) in enumerate(taken):                        # rule 3
+            if len(slots) == K_:
+                break
+            k, w = divmod(ix, V)
+            ends = w == eos
+            if ends and rho >= K_:
+                continue
+            if not ends:
+                slots.append((c, k, w))
+                if t < L - 1:
+                    continue
+            length = t + 1 if ends else L
+            rank = c * st.inv[length]
+            dst = -1
+            if pn < K_:                                              # rule 4
+                dst, pn = pn, pn + 1
+            else:
+                worst = 0
+                for j in range(1, K_):
+                    rj, rw = float(st.pool_rank[s, j]), float(st.pool_rank[s, worst])
+                    if rj < rw or (rj == rw and int(st.pool_ins[s, j]) > int(st.pool_ins[s, worst])):
+                        worst = j
+                if float(rank) > float(st.pool_rank[s, worst]):
+                    dst = worst
+            if dst >= 0:
+                st.pool_logprob[s, dst], st.pool_rank[s, dst], st.pool_len[s, dst], st.pool_ins[s, dst] = c, rank, length, pnext
+                pnext += 1
+                st.pool_seq[s, dst, :t] = h_in[s, k, :t]
+                st.pool_seq[s, dst, t] = w
+                st.pool_seq[s, dst, t + 1:] = eos
+        filled = len(slots)
+        slots += [(f32(ninf), j, eos) for j in range(filled, K_)]    # rule 5
+        d = True
+        if t < L - 1:                                                # rule 6
+            d = filled == 0
+            if not d and pn == K_:
+                d = bool(early_stopping) or float(st.pool_rank[s].min()) >= float(slots[0][0] * st.inv[L if st.alpha > 0.0 else t + 2])
+        st.pool_cnt[s, 0], st.pool_cnt[s, 1], st.done[s] = pn, pnext, int(d)
+        for j, (c, k, w) in enumerate(slots):
+            sc_out[s, j] = c
+            row = h_in[s, k].clone()
+            row[t] = w
+            h_out[s, j] = row
+            st.tok[j * b + s], st.parent[j * b + s] = w, k * b + s
+            st.active[j, s] = int(not d and float(c) > ninf)
+    return st
+
+
+def _pool_lse(z):
+    return torch.logsumexp(z.to(torch.float32), 1)
+
+
+def decode_beam_pool_host(script_or_source, b, beam, max_len, constraints=None, candidates=None, n_best=1, early_stopping=False, lse=None,
+                          eos=None):
+    """THE LAW of the pool search as a whole: decode_beam_pool's loop on the host, built on beam_pool_step_host, with constrain_rows_host /
+    trie_rows_host in the place of the launches. script_or_source: a list of max_len logits tensors [>= b * beam, V] (step t reads the
+    first b * cur rows, beam-major: a scripted decoder) or a step source (source.step(tok, parent)). lse: rows -> their log-sum-exp
+    (None: torch.logsumexp in fp32; pass the cross-entropy kernel's, row_lse, to reproduce a device run bit for bit). It asks after every
+    step whether all samples are done; a done sample is frozen, so the result does not depend on when a loop leaves.
+    -> PoolState.result(n_best): (seqs, rank, logprob, length)."""
+    eos = EOS if eos is None else eos
+    _check_pool("decode_beam_pool_host", b, beam, max_len, n_best)
+    alpha = 0.0 if constraints is None else constraints.length_penalty
+    st = PoolState(b, beam, max_len, alpha, "cpu", eos, -float("inf") if candidates is None else TRIE_FLOOR)
+    if candidates is not None:
+        _no_logits_rules(constraints)
+    rules = constraints is not None and not constraints.logits_off
+    lse = _pool_lse if lse is None else lse
+    scripted = isinstance(script_or_source, (list, tuple))
+    tok = parent = None
+    for t in range(max_len):
+        cur = 1 if t == 0 else beam
+        if scripted:
+            z = script_or_source[t][:b * cur]
+        else:
+            dev = script_or_source.m.device
+            z = script_or_source.step(None if tok is None else tok.to(dev), None if parent is None else parent.to(dev))[:b * cur]
+        hist = st.hist[t % 2].transpose(0, 1).reshape(beam * b, max_len)              # row k * b + s: the words of slot k of sample s
+        active = None if t == 0 else st.active.reshape(-1)
+        l = None
+        if candidates is not None:                                                    # the log-sum-exp of the row BEFORE its mask
+            l = lse(z).detach().cpu()
+            z = trie_rows_host(z, hist, t, candidates, eos, b, active)
+        elif rules:
+            z = constrain_rows_host(z, hist, t, constraints, eos, active)
+        if l is None:
+            l = lse(z).detach().cpu()
+        beam_pool_step_host(z, l, st, t, cur, early_stopping)
+        tok, parent = st.tok.clone(), st.parent.clone()
+        if t + 1 < max_len and bool(st.done.all()):
+            break
+    return st.result(n_best)
+
+
+def decode_beam_pool(source, b, beam, max_len, constraints=None, candidates=None, n_best=1, early_stopping=False):
+    """Beam search with a pool of finished hypotheses over a step source (rows beam-major), the search captioning users expect: a
+    hypothesis that produced [SEP] leaves the beam for a pool of at most `beam` finished ones, the beam stays `beam` OPEN hypotheses
+    wide, the pool is ranked by logP * inv[length] (inv[l] = 1 / l^length_penalty: the ranking acts while the search runs), and a
+    sample is done as soon as no open hypothesis can still enter its pool (early_stopping: as soon as the pool is full). The law:
+    beam_pool_step_host / decode_beam_pool_host, bit for bit.
+    Per step: the source's step, the constrainer's launch when a rule is on (valor_logits_constrain / valor_trie_constrain, as in
+    decode_beam; with an AnswerSet the log-sum-exp is that of the row BEFORE its mask), the cross-entropy kernel's row log-sum-exp, and
+    ONE valor_beam_pool_step launch that does the selection, the pool update, the history reorder and the next step's tok / parent /
+    active rows. Nothing is read back except `done`, every source.poll steps and never after the last one (_all_ended's pattern); the
+    loop leaves when every sample is done.
+    -> (seqs int64 [b, n_best, max_len] padded with [SEP], rank fp32 [b, n_best], logprob fp32 [b, n_best], length int64 [b, n_best]),
+    best first; fewer than n_best hypotheses (possible only inside an answer set) leave all-[SEP] rows with scores -inf and length 0.
+    beam outside 1 .. 8, n_best outside 1 .. beam, a vocabulary below 2 * beam raise ValueError: there is no torch path."""
+    dev = source.m.device
+    _check_pool("decode_beam_pool", b, beam, max_len, n_best)
+    st = PoolState(b, beam, max_len, 0.0 if constraints is None else constraints.length_penalty, dev,
+                   floor=-float("inf") if candidates is None else TRIE_FLOOR)
+    con = _constrainer(constraints, dev, candidates)
+    tok = parent = None
+    for t in range(max_len):
+        cur = 1 if t == 0 else beam
+        logits = source.step(tok, parent)[:b * cur]
+        lse = row_lse(logits)[0] if candidates is not None else None
+        if con is not None:                                          # the words so far sit in `hist` as (sample, slot); the rows are beam-major
+            con(logits, st.hist[t % 2], t, st.active.view(-1) if t > 0 else None, b, beam * max_len, max_len)
+        if lse is None:
+            lse = row_lse(logits)[0]
+        beam_pool_step(logits, lse, st, t, cur, early_stopping)
+        tok, parent = st.tok, st.parent
+        if (t + 1) % source.poll == 0 and t + 1 < max_len and bool(st.done.all()):
+            break
+    return st.result(n_best)
+
+
 @contextlib.contextmanager
 def no_gc():
     """Keep Python's cyclic collector out of a decoding step's capture. A dead cycle that still holds device resources -- an earlier model
@@ -1075,10 +1364,12 @@ def decode_sample(source, b, max_len, stream, sampling=None, constraints=None, c
     return sents, logprobs
 
 
-def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None, sampling=None, constraints=None, candidates=None):
+def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, stream=None, sampling=None, constraints=None, candidates=None,
+                   pool=None):
     """{group: (sequences, logprobs | None)} for the query groups present, through the K|V-cached session or the re-run path.
     stream: a SampleStream (after begin_call) -> sampled decoding (beam 1) under `sampling` (a Sampling or None). constraints: a
-    Constraints or None, for every mode; candidates: an AnswerSet fitted to the b rows (for_rows) or None"""
+    Constraints or None, for every mode; candidates: an AnswerSet fitted to the b rows (for_rows) or None. pool: (n_best,
+    early_stopping) -> the beam search is decode_beam_pool and a group's entry its (seqs, rank, logprob, length)"""
     c, a = constraints, candidates
     prompt = _prompt_rows(model, prompt, b)
     if stream is not None:
@@ -1091,6 +1382,8 @@ def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, s
         source = _group_source(sess, model, g, b, kv_layers, ranges, prompt)
         if stream is not None:
             out[g] = decode_sample(source, b, max_len, stream, sampling, c, a)
+        elif pool is not None and beam > 1:
+            out[g] = decode_beam_pool(source, b, beam, max_len, c, a, pool[0], pool[1])
         else:
             out[g] = (decode_beam(source, b, beam, max_len, c, a), None) if beam > 1 else decode_greedy(source, b, max_len, c, a)
     return out
@@ -1196,10 +1489,44 @@ def _named(name, res, logprobs):
     return out
 
 
+def _named_pool(name, res):
+    """the result of a generate_* call under the pool search: name + key [b * n, L] clip-major (rows i * n .. i * n + n - 1 are the n
+    best of clip i, best first), 'sequence_scores_' + key (the rank scores) and 'sequence_logprobs_' + key (the summed logP) [b * n]"""
+    out = {}
+    for g, (seqs, rank, logprob, _) in res.items():
+        key = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]
+        out[name + key] = seqs.reshape(-1, seqs.shape[-1])
+        out["sequence_scores_" + key] = rank.reshape(-1)
+        out["sequence_logprobs_" + key] = logprob.reshape(-1)
+    return out
+
+
+BEAM_RULES = ("reference", "pool")
+
+
+def _beam_rule(who, model, mode, beam, beam_search, early_stopping):
+    """the beam-search rule of a generate_* call -> (rule, early_stopping). beam_search / early_stopping None: the model's options
+    generation_beam_search (absent: 'reference') / generation_early_stopping (absent: False). beam_search='pool' GIVEN with a call that
+    runs no beam search (mode 'greedy' / 'sample', beam 1) raises; the model's option simply does not apply to such a call."""
+    from .model.valor import _opt
+    rule = _opt(model.opts, "generation_beam_search", "reference") if beam_search is None else beam_search
+    if rule not in BEAM_RULES:
+        raise ValueError(f"{who}: beam_search {rule!r} ('reference' or 'pool')")
+    searching = mode is None and beam > 1
+    if beam_search == "pool" and not searching:
+        raise ValueError(f"{who}: beam_search='pool' needs a beam search (mode None and a beam above 1; got mode {mode!r}, beam {beam})")
+    if not searching:
+        rule = "reference"
+    if early_stopping is not None and rule != "pool":
+        raise ValueError(f"{who}: early_stopping needs beam_search='pool'")
+    early = _opt(model.opts, "generation_early_stopping", False) if early_stopping is None else early_stopping
+    return rule, bool(early)
+
+
 @torch.no_grad()
 def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None, top_k=None,
                  top_p=None, num_return_sequences=1, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None,
-                 suppress_tokens=None, length_penalty=None, candidates=None):
+                 suppress_tokens=None, length_penalty=None, candidates=None, beam_search=None, early_stopping=None):
     """VALOR.generate_cap, model/pretrain.py:914-985 -> {'generated_sequences_t_v' | '_t_va' | '_t_a' (+ 'logprobs_*' when greedy or
     sampled)}. mode: None (beam search when beam_size > 1, else greedy), 'greedy' (whatever beam_size says) or 'sample' (decode_greedy's
     sample mode, :1007-1011: a draw from softmax(logits) per step, logprobs_* = the logP of the draws). seed: the sampled draws' seed
@@ -1214,18 +1541,33 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
     candidates: an AnswerSet (or a plain list of token lists: one shared set) -> every mode decodes INSIDE the set (one valor_trie_constrain
     launch per step): each output row is one of the candidates, AnswerSet.index_of names it; a per-sample set has one entry per clip
     (num_return_sequences rows read their clip's entry) or one per output row. It excludes the logits rules above (ValueError);
-    length_penalty stays. In sample mode the logprobs are those of the masked row: a column outside the set has mass exactly 0."""
+    length_penalty stays. In sample mode the logprobs are those of the masked row: a column outside the set has mass exactly 0.
+    beam_search: None (the model's option generation_beam_search, absent = 'reference'), 'reference' (decode_beam: the reference's rule,
+    unchanged) or 'pool' (decode_beam_pool: finished hypotheses leave the beam for a pool, length_penalty ranks while the search runs,
+    the loop leaves early; early_stopping, None = the option generation_early_stopping: a sample stops once its pool is full). Under
+    'pool', num_return_sequences = n <= beam_size returns the n best hypotheses of every clip: the outputs are [b * n, L] clip-major,
+    best first, and 'sequence_scores_*' (logP * length^-length_penalty) / 'sequence_logprobs_*' (logP) [b * n] come beside them.
+    beam_search='pool' with mode 'greedy' / 'sample' or beam 1 raises ValueError."""
     n = int(num_return_sequences)
     if n != num_return_sequences or n < 1:
         raise ValueError(f"generate_cap: num_return_sequences {num_return_sequences!r} must be an integer >= 1")
+    width = model.beam_size if beam_size is None else beam_size
+    rule, early = _beam_rule("generate_cap", model, mode, width, beam_search, early_stopping)
     sampling, constraints, beam, max_len, aset = _resolve(
-        "generate_cap", model, mode, model.beam_size if beam_size is None else beam_size, max_generation_len,
-        dict(temperature=temperature, top_k=top_k, top_p=top_p, num_return_sequences=None if n == 1 else n),
+        "generate_cap", model, mode, width, max_generation_len,
+        dict(temperature=temperature, top_k=top_k, top_p=top_p, num_return_sequences=None if n == 1 or rule == "pool" else n),
         (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty), candidates)
+    if rule == "pool":
+        _check_pool("generate_cap", 0, beam, max_len, n)
     was_training = model.training
     model.eval()
     try:
         b, kv_layers, ranges = encode_for_generation(model, batch, groups)
+        if rule == "pool":
+            if aset is not None:
+                aset = aset.for_rows(b)
+            res = _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, None, None, constraints, aset, (n, early))
+            return _named_pool("generated_sequences_", res)
         if n > 1:
             kv_layers = _repeat_clips(model, kv_layers, b, n)
             b *= n
@@ -1241,7 +1583,7 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
 @torch.no_grad()
 def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None,
                 top_k=None, top_p=None, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None, suppress_tokens=None,
-                length_penalty=None, candidates=None):
+                length_penalty=None, candidates=None, beam_search=None, early_stopping=None):
     """VALOR.generate_qa, model/pretrain.py:1366-1459: the caption decoders with the question rows as the prompt ->
     {'generated_answers_t_v' | '_t_va' | '_t_a'}. mode, seed, temperature / top_k / top_p and the Constraints arguments are
     generate_cap's: None (beam search when beam_size_qa > 1, else greedy), 'greedy', or 'sample' -- one sampled answer per question, with
@@ -1250,13 +1592,18 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
     expands the [video | audio] token rows per question; here the per-layer K|V projections are computed once per CLIP and their rows
     gathered per question (valor_gather_rows), so the projection GEMMs do not grow with the question count.
     candidates: generate_cap's -- closed-vocabulary QA: the answer is always one of the candidates (AnswerSet.index_of). A per-sample set
-    has one entry per question row, or one per clip (its sample_num question rows read it)."""
+    has one entry per question row, or one per clip (its sample_num question rows read it).
+    beam_search / early_stopping: generate_cap's; under 'pool' the best hypothesis is the answer and 'sequence_scores_*' /
+    'sequence_logprobs_*' come beside it."""
     # the reference switches to beam search when beam_size_qa > 1 but decode_beam always searches with self.beam_size, task 'qa'
     # included (pretrain.py:1061): beam_size_qa is the switch, beam_size the width
+    width = (model.beam_size if model.beam_size_qa > 1 else 1) if beam_size is None else beam_size
+    rule, early = _beam_rule("generate_qa", model, mode, width, beam_search, early_stopping)
     sampling, constraints, beam, max_len, aset = _resolve(
-        "generate_qa", model, mode, (model.beam_size if model.beam_size_qa > 1 else 1) if beam_size is None else beam_size,
-        max_generation_len, dict(temperature=temperature, top_k=top_k, top_p=top_p),
+        "generate_qa", model, mode, width, max_generation_len, dict(temperature=temperature, top_k=top_k, top_p=top_p),
         (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty), candidates)
+    if rule == "pool":
+        _check_pool("generate_qa", 0, beam, max_len)
     sample_num = [int(n) for n in batch.get("sample_num", [])]
     was_training = model.training
     model.eval()
@@ -1271,7 +1618,10 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
         if aset is not None:
             aset = aset.for_rows(b, sample_num if b != clips and aset.n_roots == clips else None)
         stream = _sample_stream(model, seed) if mode == "sample" else None
-        res = _decode_groups(model, groups, b, kv_layers, ranges, prompt_cpu, beam, max_len, stream, sampling, constraints, aset)
+        res = _decode_groups(model, groups, b, kv_layers, ranges, prompt_cpu, beam, max_len, stream, sampling, constraints, aset,
+                             (1, early) if rule == "pool" else None)
+        if rule == "pool":
+            return _named_pool("generated_answers_", res)
         return _named("generated_answers_", res, mode == "sample")
     finally:
         model.train(was_training)
