@@ -878,7 +878,11 @@ static int gemm_impl(void* stream, int dtype, int transA, int transB, int M, int
         const int64_t extA = transA ? (int64_t)K * lda : ((int64_t)(M - 1) * lda + K);
         const int64_t extB = transB ? (int64_t)K * ldb : ((int64_t)(N - 1) * ldb + K);
         if (extA * esz >= (1ll << 31) || extB * esz >= (1ll << 31)) return VALOR_ERR_ARG;   // buffer offsets are 32-bit
-        p.bytesA = (uint32_t)(extA * esz); p.bytesB = (uint32_t)(extB * esz);
+        // The range check drops a whole DWORD that reaches past the extent: with an odd K of bf16 a direct operand ends in the middle of
+        // one, and element K - 1 of its LAST row was read as zero (tests/test_gemm_exact_gpu.py, K = 1001: the last output column off by
+        // a[m][K-1] * b[N-1][K-1]). The extent is rounded up to whole dwords: the other half of that dword is element K of the same row,
+        // inside the row's padding (ld % 8 == 0 > K), and the k-tail patch / k >= K masks of the kernels zero it like every other row's.
+        p.bytesA = (uint32_t)((extA * esz + 3) & ~(int64_t)3); p.bytesB = (uint32_t)((extB * esz + 3) & ~(int64_t)3);
     }
     if (gemm_family(dtype, transA, transB, M, N, K, false) == 5 && !accumulate && !preact && !dact_aux && !rowsum_out && !(act & VALOR_ACT_DERIV)) {
         p.kslices = 1; p.ksteps_per_slice = 0;
