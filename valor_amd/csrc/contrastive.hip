@@ -68,7 +68,11 @@ __global__ __launch_bounds__(64) void fine_reduce_fwd_kernel(const float* S, int
 }
 
 // ---- InfoNCE statistics: waves 0..B-1 -> row logsumexp, waves B..2B-1 -> column logsumexp of k*score
+// (k * score is ROUNDED before anything is subtracted from it, here and in the backward: contracted into an fma the difference
+// k * score - mx would keep the product's rounding residual, the backward's k * score - lse likewise, and the probabilities of a row
+// would no longer be the exponentials of the numbers whose logsumexp was taken -- at B = 1 dscore was 3e-6 g k / 2 instead of 0)
 __global__ void infonce_lse_kernel(const float* score, const float* kdev, float* lse_r, float* lse_c, int B) {
+#pragma clang fp contract(off)
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (w >= 2 * B) return;
     const float k = *kdev;
@@ -98,6 +102,7 @@ __global__ __launch_bounds__(256) void infonce_loss_kernel(const float* score, c
 __global__ __launch_bounds__(256) void infonce_bwd_kernel(const float* score, const float* kdev, const float* lse_r,
                                                         const float* lse_c, const float* gdev, float* dscore,
                                                         float* dk_part, int B) {
+#pragma clang fp contract(off)
     __shared__ float red[4];
     const float k = *kdev, g = *gdev / (2.f * B);
     float dk = 0.f;
