@@ -599,6 +599,43 @@ int valor_beam_pool_step(void* stream, const float* logits, int64_t ld, int64_t 
                          int t, int64_t eos, float floor, int alpha_pos, int early_stopping, float* scores_out, int64_t* hist_out,
                          int64_t* tok, int64_t* parent, uint8_t* active, int64_t* pool_seq, float* pool_logprob, float* pool_rank, int32_t* pool_len,
                          int32_t* pool_ins, int32_t* pool_cnt, uint8_t* done);
+/* one step of the DIVERSE (group) beam search with finished-hypothesis pools (csrc/beam_group.hip; valor_amd.decode.beam_group_step_host
+ * restates this law on the host, bit for bit): diverse beam search (Vijayakumar et al.) with the Hamming penalty on the current step's
+ * words, on top of the pool law above (its rules 1-7 are cited by number). K = beam in 1..8, G = groups divides K, Kg = K / G.
+ * pen fp32 [K + 1]: pen[n] = diversity_penalty * n >= 0, the product in fp64 rounded to fp32 once by the caller, pen[0] = 0 (the device
+ * does one subtraction and no multiply, so no contraction can differ from the host).
+ * State: valor_beam_pool_step's arrays, where group g owns the slots g * Kg .. (g + 1) * Kg - 1 of scores / hist AND the same range of
+ * the pool's entries; pool_cnt int32 [b, G, 2] = (entries held, insertions so far) per group; gdone uint8 [b, G]; done uint8 [b].
+ * A sample with done[s] != 0 is frozen as rule 7 freezes it. Otherwise its groups are searched in order g = 0 .. G - 1:
+ *   1. a group with gdone[s, g] != 0 is frozen exactly as rule 7 freezes a sample (its slots: tok = eos, parent = the row itself,
+ *      scores_out = scores_in, hist_out = hist_in, active = 0; its pool range untouched), and it contributes no words to the counts below.
+ *   2. otherwise its candidates come from its own live slots k (cur == K), or, at the first step (cur == 1), from the one row of slot 0,
+ *      for every group: c(k, w) = scores_in[s, k] + (logits[row, w] - lse[row]) as rule 1, floor included. The SELECTION KEY is
+ *      a(k, w) = c(k, w) - pen[n_w], one fp32 subtraction, n_w = the number of NEW OPEN slots that the groups before g filled with word w
+ *      at this step (two earlier slots with the same word: pen[2]). eos never fills a slot, so it is never penalised.
+ *   3. the 2 Kg best by a, equal keys in order of the index k * V + w (k the slot's index within the sample); a key equal to -inf (or
+ *      NaN) is never taken.
+ *   4. the walk, the offers and the pool update are rules 3-5 with K -> Kg, on the group's slots and pool range. A new slot carries the
+ *      UNPENALISED c and an offer's rank score is c * inv_len[length]: the penalty steers the selection only, scores_out, pool_logprob
+ *      and pool_rank stay true (length-ranked) log-probabilities. (HF-style implementations fold the penalty into the running score of
+ *      a beam; here a returned score is always the model's own.)
+ *   5. rule 6 per group, gdone[s, g] in the place of done[s], the bound taken from the LARGEST c among the group's new slots (under a
+ *      penalised order that need not be its first slot). done[s] = 1 when every gdone[s, g] is.
+ *   6. out as rule 7; active[k, s] = the slot is live, its group not done (and hence the sample not done).
+ * Two identities: G == 1 is valor_beam_pool_step in every array; diversity_penalty == 0 makes every group an independent pool search of
+ * beam Kg (all groups then hold the same hypotheses).
+ * b == 0: no-op. VALOR_ERR_ARG, before any launch: valor_beam_pool_step's refusals -- cur * V < 2 * beam among them, which at the first
+ * step (cur == 1) asks for V >= 2 * beam although a group needs only 2 * Kg candidates -- and groups outside 1..beam or not dividing
+ * beam, cur neither 1 nor beam, V < 2 * Kg, a null pen / gdone. One 1024-thread workgroup per sample; the
+ * groups run one after another inside the launch (scan of the group's rows with per-thread lists of depth 2 Kg, arg-max rounds, a
+ * one-thread walk; the words the earlier groups took are a list of <= 8 in LDS). No atomics, no workspace, vector stores only: the
+ * result is a pure function of the inputs. */
+int valor_beam_group_step(void* stream, const float* logits, int64_t ld, int64_t row_stride_s, int64_t row_stride_k, const float* lse,
+                          const float* scores_in, const int64_t* hist_in, const float* inv_len, const float* pen, int b, int cur, int V,
+                          int beam, int groups, int max_len, int t, int64_t eos, float floor, int alpha_pos, int early_stopping,
+                          float* scores_out, int64_t* hist_out, int64_t* tok, int64_t* parent, uint8_t* active, int64_t* pool_seq,
+                          float* pool_logprob, float* pool_rank, int32_t* pool_len, int32_t* pool_ins, int32_t* pool_cnt, uint8_t* gdone,
+                          uint8_t* done);
 /* one step of the sampled caption decode, VALOR.decode_greedy mode 'sample' (pretrain.py:1007-1020): per row r < R of fp32 logits
  * [R, V] (row pitch ld >= V) with unfinished[r] != 0, the draw w = argmax_w (z_w - log(-log u_w)) (Gumbel-max: w ~ softmax(z);
  * u_w = (x >> 9) 2^-23 + 2^-24 (exact, in (0, 1)), x = Philox4x32-10(seed, offset + r * ceil(V / 4) + w / 4) word w % 4; ties to the

@@ -20,7 +20,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-val
 
 # substrings of (mangled) kernel names that must not touch scratch: the GEMM families, the LDS-resident attention, LayerNorm, AdamW,
 # cross-entropy, the fused contrastive forward, the VideoSwin window forward / dK-dV kernels and the retrieval search's top-k and pair scores ...
-HOT_KERNELS = ("beam_pool_step_kernel", "gemm_8ph_kernel", "gemm_8q_kernel", "gemm_8ph2_kernel", "gemm_glds_kernel", "gemm_splitk_reduce", "attn_res_", "attn_x_", "attn_xu_", "ln_fwd", "ln_bwd", "adamw_kernel", "xent_",
+HOT_KERNELS = ("beam_pool_step_kernel", "beam_group_step_kernel", "gemm_8ph_kernel", "gemm_8q_kernel", "gemm_8ph2_kernel", "gemm_glds_kernel", "gemm_splitk_reduce", "attn_res_", "attn_x_", "attn_xu_", "ln_fwd", "ln_bwd", "adamw_kernel", "xent_",
                "fine_fused_fwd", "fine_fused_fwd_fp8_kernel", "fine_ds_chunk_kernelIDF16bLi16", "win_fwd", "win_bwd_dkv", "topk_segment_kernel",
                "topk_merge_kernel", "fine_score_pairs_kernel", "grad_partial_kernel", "update_partial_kernel", "ema_kernel", "trie_constrain_kernel",
                "trie_score_level_kernel")

@@ -42,6 +42,8 @@ a whole shared set exactly, level by level over the trie: one decoder row per tr
 with a pool of finished hypotheses: the beam stays `beam` OPEN hypotheses wide, length_penalty ranks while the search runs, the n best
 are returned and the loop leaves early; one valor_beam_pool_step launch per step does the selection, the pool update, the history
 reorder and the next step's inputs (`beam_pool_step_host` / `decode_beam_pool_host` are its law on the host, bit for bit).
+`num_beam_groups` / `diversity_penalty` make it diverse beam search: the beam's groups are searched one after another inside ONE
+valor_beam_group_step launch per step, a later group paying for every word an earlier group has just taken (`beam_group_step_host`).
 
 Everything here is inference: torch.no_grad, dropout off regardless of model.training (the reference calls it under model.eval())."""
 import contextlib
@@ -1118,22 +1120,208 @@ def beam_pool_step_host(logits, lse, state, t, cur, early_stopping=False, beam_m
     return st
 
 
+# ------------------------------------------------------------------------------------------------ diverse beam search: beam groups
+def diversity_table(beam, diversity_penalty):
+    """pen[n] = diversity_penalty * n for n = 0 .. beam, the product in fp64 rounded to fp32 once (pen[0] = 0): the selection key of a
+    word that n earlier slots of the step took is the fp32 DIFFERENCE c - pen[n], the same bits on the host and in the kernel (no
+    multiply on the device, as inv_length_table)."""
+    lam = float(diversity_penalty)
+    return torch.tensor([0.0] + [lam * n for n in range(1, int(beam) + 1)], dtype=torch.float64).to(torch.float32)
+
+
+def _check_groups(who, beam, groups, diversity_penalty=0.0, V=None, cur=None):
+    if int(groups) != groups or not 1 <= groups <= beam or beam % groups:
+        raise ValueError(f"{who}: num_beam_groups {groups!r} must divide the beam {beam}")
+    lam = float(diversity_penalty)
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError(f"{who}: diversity_penalty {diversity_penalty!r} must be finite and >= 0")
+    if V is not None:
+        if cur not in (1, beam):
+            raise ValueError(f"{who}: cur {cur!r} is neither 1 (the first step) nor the beam {beam}")
+        if V < 2 * (beam // groups):
+            raise ValueError(f"{who}: {V} words hold fewer than 2 * beam / groups = {2 * (beam // groups)} candidates")
+
+
+class GroupPoolState(PoolState):
+    """The arrays of one diverse (group) pool search (valor_beam_group_step, include/valor_hip.h): PoolState's, with the `beam` slots and
+    the `beam` pool entries split into `groups` ranges of beam / groups (group g owns g * Kg .. (g + 1) * Kg - 1 of both), pool_cnt int32
+    [b, groups, 2] = (entries held, insertions) per group, gdone uint8 [b, groups] (done[s] = all of gdone[s]) and pen fp32 [beam + 1],
+    the diversity_table of the penalty."""
+    FIELDS = PoolState.FIELDS + ("gdone", "pen")
+
+    def __init__(self, b, beam, groups, max_len, alpha=0.0, device="cpu", eos=None, floor=-float("inf"), diversity_penalty=0.0):
+        super().__init__(b, beam, max_len, alpha, device, eos, floor)
+        _check_groups("GroupPoolState", beam, groups, diversity_penalty)
+        self.groups, self.diversity_penalty = int(groups), float(diversity_penalty)
+        self.pool_cnt = torch.zeros((b, self.groups, 2), dtype=torch.int32, device=device)
+        self.gdone = torch.zeros((b, self.groups), dtype=torch.uint8, device=device)
+        self.pen = diversity_table(beam, diversity_penalty).to(device)
+
+    def result(self, n_best):
+        """every group's pool sorted as PoolState.result sorts one (rank score descending, equal scores by earlier insertion), then the
+        entries by their PLACE within their group (0 = the group's best), within one place by rank score descending, equal scores by
+        group index: entry 0 is the overall best and the first `groups` entries are one hypothesis per group
+        -> (seqs int64 [b, n, L], rank fp32 [b, n], logprob fp32 [b, n], length int64 [b, n], group int64 [b, n])"""
+        n, L, G = int(n_best), self.max_len, self.groups
+        Kg = self.beam // G
+        ins, rank = self.pool_ins.view(self.b, G, Kg), self.pool_rank.view(self.b, G, Kg)
+        by_age = torch.sort(ins, dim=2, stable=True)[1]
+        place = torch.gather(by_age, 2, torch.sort(torch.gather(rank, 2, by_age), dim=2, descending=True, stable=True)[1])   # [b, G, place]
+        place = place + torch.arange(G, device=place.device).view(1, G, 1) * Kg                                               # pool entries
+        rank_at = torch.gather(self.pool_rank, 1, place.reshape(self.b, -1)).view(self.b, G, Kg)
+        by_group = torch.sort(rank_at, dim=1, descending=True, stable=True)[1]                                                # [b, ., place]
+        order = torch.gather(place, 1, by_group).transpose(1, 2).reshape(self.b, -1)[:, :n]
+        seqs = torch.gather(self.pool_seq, 1, order[:, :, None].expand(self.b, n, L))
+        return (seqs.contiguous(), torch.gather(self.pool_rank, 1, order), torch.gather(self.pool_logprob, 1, order),
+                torch.gather(self.pool_len, 1, order).to(torch.int64), order // Kg)
+
+
+def beam_group_step(logits, lse, state, t, cur, early_stopping=False, beam_major=True):
+    """one step of the group pool search in ONE launch (valor_beam_group_step; the law: include/valor_hip.h, restated by
+    beam_group_step_host): beam_pool_step's arguments with a GroupPoolState on the logits' device, updated in place (gdone besides).
+    cur is 1 (the first step: every group reads the one row of slot 0) or the beam. Anything the kernel cannot do raises ValueError:
+    there is no torch path."""
+    st = state
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError("beam_group_step: logits fp32 [rows, V] with unit column stride and lse fp32 [rows]")
+    V = logits.shape[1]
+    _check_pool("beam_group_step", st.b, st.beam, st.max_len, 1, V, cur, t, st.eos)
+    _check_groups("beam_group_step", st.beam, st.groups, st.diversity_penalty, V, cur)
+    if logits.shape[0] != st.b * cur or lse.numel() != st.b * cur:
+        raise ValueError(f"beam_group_step: {logits.shape[0]} rows / {lse.numel()} lse values for b * cur = {st.b * cur}")
+    K._check_gpu(logits, lse, st.done)
+    i, o = t % 2, (t + 1) % 2
+    rs_s, rs_k = (1, st.b) if beam_major else (cur, 1)
+    lib.call("valor_beam_group_step", _st(), logits.data_ptr(), logits.stride(0), rs_s, rs_k, lse.data_ptr(), st.scores[i].data_ptr(),
+             st.hist[i].data_ptr(), st.inv.data_ptr(), st.pen.data_ptr(), st.b, cur, V, st.beam, st.groups, st.max_len, t, st.eos, st.floor,
+             int(st.alpha > 0.0), int(bool(early_stopping)), st.scores[o].data_ptr(), st.hist[o].data_ptr(), st.tok.data_ptr(),
+             st.parent.data_ptr(), st.active.data_ptr(), st.pool_seq.data_ptr(), st.pool_logprob.data_ptr(), st.pool_rank.data_ptr(),
+             st.pool_len.data_ptr(), st.pool_ins.data_ptr(), st.pool_cnt.data_ptr(), st.gdone.data_ptr(), st.done.data_ptr())
+    return st
+
+
+def beam_group_step_host(logits, lse, state, t, cur, early_stopping=False, beam_major=True):
+    """THE LAW of one step of the group pool search (include/valor_hip.h, valor_beam_group_step), on the host in fp32: beam_group_step's
+    arguments with a GroupPoolState of host tensors, updated in place. The groups of a sample are searched one after another; a group
+    is beam_pool_step_host's law on its own slots and pool range, except that the candidates are ORDERED by the key
+    a = c - pen[n_w] (n_w: the new open slots that earlier groups filled with word w at this step) while a slot, an offer and the
+    bound carry the unpenalised c. Every value is one rounded fp32 operation in the kernel's order, so the kernel agrees bit for bit."""
+    st = state
+    z = logits.detach().to(device="cpu", dtype=torch.float32)
+    l = lse.detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    b, K_, G, L, eos = st.b, st.beam, st.groups, st.max_len, st.eos
+    Kg = K_ // G
+    V = z.shape[1]
+    _check_pool("beam_group_step_host", b, K_, L, 1, V, cur, t, eos)
+    _check_groups("beam_group_step_host", K_, G, st.diversity_penalty, V, cur)
+    if z.shape[0] != b * cur or l.numel() != b * cur:
+        raise ValueError(f"beam_group_step_host: {z.shape[0]} rows / {l.numel()} lse values for b * cur = {b * cur}")
+    i, o = t % 2, (t + 1) % 2
+    sc_in, sc_out, h_in, h_out = st.scores[i], st.scores[o], st.hist[i], st.hist[o]
+    ninf = -float("inf")
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32)
+
+    def freeze(s, k):
+        sc_out[s, k], h_out[s, k] = sc_in[s, k], h_in[s, k]
+        st.tok[k * b + s], st.parent[k * b + s], st.active[k, s] = eos, k * b + s, 0
+
+    for s in range(b):
+        if bool(st.done[s]):                                         # a done sample is frozen
+            for k in range(K_):
+                freeze(s, k)
+            continue
+        count = torch.zeros(V, dtype=torch.int64)                    # n_w: the words the earlier groups' new open slots took
+        for g in range(G):
+            lo = g * Kg
+            if bool(st.gdone[s, g]):                                 # a done group is frozen and lends no words
+                for k in range(lo, lo + Kg):
+                    freeze(s, k)
+                continue
+            ks = [0] if cur == 1 else list(range(lo, lo + Kg))       # the first step: every group reads the one row of slot 0
+            cand = torch.full((len(ks), V), ninf, dtype=torch.float32)
+            for j, k in enumerate(ks):
+                if float(sc_in[s, k]) > ninf:
+                    r = k * b + s if beam_major else s * cur + k
+                    cand[j] = torch.where(z[r] > st.floor, sc_in[s, k] + (z[r] - l[r]), f32(ninf))
+            key = (cand - st.pen[count][None, :]).reshape(-1)        # one fp32 subtraction; pen[0] = 0 leaves c as it is
+            key = torch.where(key.isnan(), f32(ninf), key)
+            val, idx = torch.sort(key, descending=True, stable=True)
+            taken = [(cand.reshape(-1)[int(idx[j])].clone(), ks[int(idx[j]) // V], int(idx[j]) % V)
+                     for j in range(min(2 * Kg, key.numel())) if float(val[j]) > ninf]
+            pn, pnext = int(st.pool_cnt[s, g, 0]), int(st.pool_cnt[s, g, 1])
+            slots = []                                               # (score, parent slot, token)
+            for rho, (c, k, w) in enumerate(taken):
+                if len(slots) == Kg:
+                    break
+                ends = w == eos
+                if ends and rho >= Kg:
+                    continue
+                if not ends:
+                    slots.append((c, k, w))
+                    if t < L - 1:
+                        continue
+                length = t + 1 if ends else L
+                rank = c * st.inv[length]
+                dst = -1
+                if pn < Kg:
+                    dst, pn = pn, pn + 1
+                else:
+                    worst = 0
+                    for j in range(1, Kg):
+                        rj, rw = float(st.pool_rank[s, lo + j]), float(st.pool_rank[s, lo + worst])
+                        if rj < rw or (rj == rw and int(st.pool_ins[s, lo + j]) > int(st.pool_ins[s, lo + worst])):
+                            worst = j
+                    if float(rank) > float(st.pool_rank[s, lo + worst]):
+                        dst = worst
+                if dst >= 0:
+                    e = lo + dst
+                    st.pool_logprob[s, e], st.pool_rank[s, e], st.pool_len[s, e], st.pool_ins[s, e] = c, rank, length, pnext
+                    pnext += 1
+                    st.pool_seq[s, e, :t] = h_in[s, k, :t]
+                    st.pool_seq[s, e, t] = w
+                    st.pool_seq[s, e, t + 1:] = eos
+            filled = len(slots)
+            for c, _, w in slots:
+                count[w] += 1
+            d = True
+            if t < L - 1:
+                d = filled == 0
+                if not d and pn == Kg:                               # the bound: the group's largest new score (need not be its slot 0)
+                    top = max(float(c) for c, _, _ in slots)
+                    d = bool(early_stopping) or float(st.pool_rank[s, lo:lo + Kg].min()) >= float(f32(top) * st.inv[L if st.alpha > 0.0 else t + 2])
+            slots += [(f32(ninf), lo + j, eos) for j in range(filled, Kg)]
+            st.pool_cnt[s, g, 0], st.pool_cnt[s, g, 1], st.gdone[s, g] = pn, pnext, int(d)
+            for j, (c, k, w) in enumerate(slots):
+                sc_out[s, lo + j] = c
+                row = h_in[s, k].clone()
+                row[t] = w
+                h_out[s, lo + j] = row
+                st.tok[(lo + j) * b + s], st.parent[(lo + j) * b + s] = w, k * b + s
+                st.active[lo + j, s] = int(not d and float(c) > ninf)
+        st.done[s] = int(bool(st.gdone[s].all()))
+    return st
+
+
 def _pool_lse(z):
     return torch.logsumexp(z.to(torch.float32), 1)
 
 
 def decode_beam_pool_host(script_or_source, b, beam, max_len, constraints=None, candidates=None, n_best=1, early_stopping=False, lse=None,
-                          eos=None):
+                          eos=None, num_beam_groups=1, diversity_penalty=0.0):
     """THE LAW of the pool search as a whole: decode_beam_pool's loop on the host, built on beam_pool_step_host, with constrain_rows_host /
     trie_rows_host in the place of the launches. script_or_source: a list of max_len logits tensors [>= b * beam, V] (step t reads the
     first b * cur rows, beam-major: a scripted decoder) or a step source (source.step(tok, parent)). lse: rows -> their log-sum-exp
     (None: torch.logsumexp in fp32; pass the cross-entropy kernel's, row_lse, to reproduce a device run bit for bit). It asks after every
     step whether all samples are done; a done sample is frozen, so the result does not depend on when a loop leaves.
-    -> PoolState.result(n_best): (seqs, rank, logprob, length)."""
+    num_beam_groups > 1: the same loop on a GroupPoolState with beam_group_step_host in the place of beam_pool_step_host.
+    -> PoolState.result(n_best): (seqs, rank, logprob, length); with groups GroupPoolState.result(n_best): the group index besides."""
     eos = EOS if eos is None else eos
     _check_pool("decode_beam_pool_host", b, beam, max_len, n_best)
+    grouped = _grouped("decode_beam_pool_host", beam, num_beam_groups, diversity_penalty)
     alpha = 0.0 if constraints is None else constraints.length_penalty
-    st = PoolState(b, beam, max_len, alpha, "cpu", eos, -float("inf") if candidates is None else TRIE_FLOOR)
+    floor = -float("inf") if candidates is None else TRIE_FLOOR
+    st = (GroupPoolState(b, beam, num_beam_groups, max_len, alpha, "cpu", eos, floor, diversity_penalty) if grouped else
+          PoolState(b, beam, max_len, alpha, "cpu", eos, floor))
     if candidates is not None:
         _no_logits_rules(constraints)
     rules = constraints is not None and not constraints.logits_off
@@ -1157,14 +1345,23 @@ def decode_beam_pool_host(script_or_source, b, beam, max_len, constraints=None, 
             z = constrain_rows_host(z, hist, t, constraints, eos, active)
         if l is None:
             l = lse(z).detach().cpu()
-        beam_pool_step_host(z, l, st, t, cur, early_stopping)
+        (beam_group_step_host if grouped else beam_pool_step_host)(z, l, st, t, cur, early_stopping)
         tok, parent = st.tok.clone(), st.parent.clone()
         if t + 1 < max_len and bool(st.done.all()):
             break
     return st.result(n_best)
 
 
-def decode_beam_pool(source, b, beam, max_len, constraints=None, candidates=None, n_best=1, early_stopping=False):
+def _grouped(who, beam, num_beam_groups, diversity_penalty):
+    """whether a pool search runs in beam groups (num_beam_groups > 1), after the checks of the two arguments"""
+    _check_groups(who, beam, num_beam_groups, diversity_penalty)
+    if num_beam_groups == 1 and float(diversity_penalty) > 0.0:
+        raise ValueError(f"{who}: diversity_penalty {diversity_penalty!r} needs num_beam_groups > 1 (one group has nobody to differ from)")
+    return num_beam_groups > 1
+
+
+def decode_beam_pool(source, b, beam, max_len, constraints=None, candidates=None, n_best=1, early_stopping=False, num_beam_groups=1,
+                     diversity_penalty=0.0):
     """Beam search with a pool of finished hypotheses over a step source (rows beam-major), the search captioning users expect: a
     hypothesis that produced [SEP] leaves the beam for a pool of at most `beam` finished ones, the beam stays `beam` OPEN hypotheses
     wide, the pool is ranked by logP * inv[length] (inv[l] = 1 / l^length_penalty: the ranking acts while the search runs), and a
@@ -1177,11 +1374,20 @@ def decode_beam_pool(source, b, beam, max_len, constraints=None, candidates=None
     loop leaves when every sample is done.
     -> (seqs int64 [b, n_best, max_len] padded with [SEP], rank fp32 [b, n_best], logprob fp32 [b, n_best], length int64 [b, n_best]),
     best first; fewer than n_best hypotheses (possible only inside an answer set) leave all-[SEP] rows with scores -inf and length 0.
-    beam outside 1 .. 8, n_best outside 1 .. beam, a vocabulary below 2 * beam raise ValueError: there is no torch path."""
+    beam outside 1 .. 8, n_best outside 1 .. beam, a vocabulary below 2 * beam raise ValueError: there is no torch path.
+    num_beam_groups = G > 1 (G divides beam), diversity_penalty >= 0: diverse beam search (Vijayakumar et al.). The beam is G groups of
+    beam / G slots, each with its own pool range, searched one after another inside the step's ONE valor_beam_group_step launch; a
+    later group orders its candidates by c - diversity_penalty * (the number of new open slots of earlier groups that took the word at
+    this step). The penalty steers the selection only: scores, ranks and the returned log-probabilities stay true log-probabilities
+    (HF-style implementations fold the penalty into the running score). The law: beam_group_step_host. The result gains a fifth
+    entry, the group of every hypothesis, and is ordered as GroupPoolState.result orders it (the first G: one per group)."""
     dev = source.m.device
     _check_pool("decode_beam_pool", b, beam, max_len, n_best)
-    st = PoolState(b, beam, max_len, 0.0 if constraints is None else constraints.length_penalty, dev,
-                   floor=-float("inf") if candidates is None else TRIE_FLOOR)
+    grouped = _grouped("decode_beam_pool", beam, num_beam_groups, diversity_penalty)
+    alpha, floor = 0.0 if constraints is None else constraints.length_penalty, -float("inf") if candidates is None else TRIE_FLOOR
+    st = (GroupPoolState(b, beam, num_beam_groups, max_len, alpha, dev, floor=floor, diversity_penalty=diversity_penalty) if grouped else
+          PoolState(b, beam, max_len, alpha, dev, floor=floor))
+    step = beam_group_step if grouped else beam_pool_step
     con = _constrainer(constraints, dev, candidates)
     tok = parent = None
     for t in range(max_len):
@@ -1192,7 +1398,7 @@ def decode_beam_pool(source, b, beam, max_len, constraints=None, candidates=None
             con(logits, st.hist[t % 2], t, st.active.view(-1) if t > 0 else None, b, beam * max_len, max_len)
         if lse is None:
             lse = row_lse(logits)[0]
-        beam_pool_step(logits, lse, st, t, cur, early_stopping)
+        step(logits, lse, st, t, cur, early_stopping)
         tok, parent = st.tok, st.parent
         if (t + 1) % source.poll == 0 and t + 1 < max_len and bool(st.done.all()):
             break
@@ -1369,7 +1575,8 @@ def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, s
     """{group: (sequences, logprobs | None)} for the query groups present, through the K|V-cached session or the re-run path.
     stream: a SampleStream (after begin_call) -> sampled decoding (beam 1) under `sampling` (a Sampling or None). constraints: a
     Constraints or None, for every mode; candidates: an AnswerSet fitted to the b rows (for_rows) or None. pool: (n_best,
-    early_stopping) -> the beam search is decode_beam_pool and a group's entry its (seqs, rank, logprob, length)"""
+    early_stopping[, num_beam_groups, diversity_penalty]) -> the beam search is decode_beam_pool and a group's entry its (seqs, rank,
+    logprob, length[, beam group])"""
     c, a = constraints, candidates
     prompt = _prompt_rows(model, prompt, b)
     if stream is not None:
@@ -1383,7 +1590,7 @@ def _decode_groups(model, groups, b, kv_layers, ranges, prompt, beam, max_len, s
         if stream is not None:
             out[g] = decode_sample(source, b, max_len, stream, sampling, c, a)
         elif pool is not None and beam > 1:
-            out[g] = decode_beam_pool(source, b, beam, max_len, c, a, pool[0], pool[1])
+            out[g] = decode_beam_pool(source, b, beam, max_len, c, a, *pool)
         else:
             out[g] = (decode_beam(source, b, beam, max_len, c, a), None) if beam > 1 else decode_greedy(source, b, max_len, c, a)
     return out
@@ -1491,14 +1698,36 @@ def _named(name, res, logprobs):
 
 def _named_pool(name, res):
     """the result of a generate_* call under the pool search: name + key [b * n, L] clip-major (rows i * n .. i * n + n - 1 are the n
-    best of clip i, best first), 'sequence_scores_' + key (the rank scores) and 'sequence_logprobs_' + key (the summed logP) [b * n]"""
+    best of clip i, best first), 'sequence_scores_' + key (the rank scores) and 'sequence_logprobs_' + key (the summed logP) [b * n];
+    under beam groups 'sequence_groups_' + key besides (int64 [b * n]: the beam group of each hypothesis, GroupPoolState.result's order)"""
     out = {}
-    for g, (seqs, rank, logprob, _) in res.items():
+    for g, (seqs, rank, logprob, _, *group) in res.items():
         key = {"tv": "t_v", "tva": "t_va", "ta": "t_a"}[g]
         out[name + key] = seqs.reshape(-1, seqs.shape[-1])
         out["sequence_scores_" + key] = rank.reshape(-1)
         out["sequence_logprobs_" + key] = logprob.reshape(-1)
+        if group:
+            out["sequence_groups_" + key] = group[0].reshape(-1)
     return out
+
+
+def _beam_groups(who, model, rule, beam, num_beam_groups, diversity_penalty, searching=True):
+    """the beam groups of a generate_* call -> (num_beam_groups, diversity_penalty). None: the model's options
+    generation_num_beam_groups (absent: 1) / generation_diversity_penalty (absent: 0.0). rule: _beam_rule's; searching: the call runs
+    a beam search (mode None and a beam above 1). Groups or a penalty without the pool rule raise ValueError: GIVEN, with any call; from
+    the model's options, with a call that searches under the reference rule (num_beam_groups=1, diversity_penalty=0.0 GIVEN switch
+    them off for that call). To a call that runs no beam search the options simply do not apply, as generation_beam_search."""
+    from .model.valor import _opt
+    G = _opt(model.opts, "generation_num_beam_groups", 1) if num_beam_groups is None else num_beam_groups
+    lam = _opt(model.opts, "generation_diversity_penalty", 0.0) if diversity_penalty is None else diversity_penalty
+    if rule != "pool":
+        given = (num_beam_groups is not None and num_beam_groups != 1) or (diversity_penalty is not None and diversity_penalty != 0.0)
+        if given or (searching and (G != 1 or lam != 0.0)):
+            raise ValueError(f"{who}: num_beam_groups {G!r} / diversity_penalty {lam!r} need beam_search='pool'"
+                             + ("" if given else " (the model's options ask for them; this call searches under the reference rule)"))
+        return 1, 0.0
+    _grouped(who, beam, G, lam)
+    return int(G), float(lam)
 
 
 BEAM_RULES = ("reference", "pool")
@@ -1526,7 +1755,8 @@ def _beam_rule(who, model, mode, beam, beam_search, early_stopping):
 @torch.no_grad()
 def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None, top_k=None,
                  top_p=None, num_return_sequences=1, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None,
-                 suppress_tokens=None, length_penalty=None, candidates=None, beam_search=None, early_stopping=None):
+                 suppress_tokens=None, length_penalty=None, candidates=None, beam_search=None, early_stopping=None, num_beam_groups=None,
+                 diversity_penalty=None):
     """VALOR.generate_cap, model/pretrain.py:914-985 -> {'generated_sequences_t_v' | '_t_va' | '_t_a' (+ 'logprobs_*' when greedy or
     sampled)}. mode: None (beam search when beam_size > 1, else greedy), 'greedy' (whatever beam_size says) or 'sample' (decode_greedy's
     sample mode, :1007-1011: a draw from softmax(logits) per step, logprobs_* = the logP of the draws). seed: the sampled draws' seed
@@ -1547,7 +1777,14 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
     the loop leaves early; early_stopping, None = the option generation_early_stopping: a sample stops once its pool is full). Under
     'pool', num_return_sequences = n <= beam_size returns the n best hypotheses of every clip: the outputs are [b * n, L] clip-major,
     best first, and 'sequence_scores_*' (logP * length^-length_penalty) / 'sequence_logprobs_*' (logP) [b * n] come beside them.
-    beam_search='pool' with mode 'greedy' / 'sample' or beam 1 raises ValueError."""
+    beam_search='pool' with mode 'greedy' / 'sample' or beam 1 raises ValueError.
+    num_beam_groups = G / diversity_penalty (None: the model's options generation_num_beam_groups, absent = 1, and
+    generation_diversity_penalty, absent = 0.0), under 'pool' only: diverse beam search. The beam is G groups of beam_size / G, searched
+    one after another inside every step; a later group pays diversity_penalty for every earlier group's slot that has just taken the
+    same word (decode_beam_pool). The n returned are ordered by place within their group, then by score: the first G are one hypothesis
+    per group, and 'sequence_groups_*' (int64 [b * n]) names the group of each. The penalty steers the selection only;
+    'sequence_scores_*' / 'sequence_logprobs_*' stay true (length-ranked) log-probabilities. G not dividing beam_size, a negative or
+    non-finite penalty, a penalty with one group, groups without beam_search='pool' raise ValueError."""
     n = int(num_return_sequences)
     if n != num_return_sequences or n < 1:
         raise ValueError(f"generate_cap: num_return_sequences {num_return_sequences!r} must be an integer >= 1")
@@ -1559,6 +1796,7 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
         (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty), candidates)
     if rule == "pool":
         _check_pool("generate_cap", 0, beam, max_len, n)
+    groups_of = _beam_groups("generate_cap", model, rule, beam, num_beam_groups, diversity_penalty, mode is None and beam > 1)
     was_training = model.training
     model.eval()
     try:
@@ -1566,7 +1804,8 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
         if rule == "pool":
             if aset is not None:
                 aset = aset.for_rows(b)
-            res = _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, None, None, constraints, aset, (n, early))
+            res = _decode_groups(model, groups, b, kv_layers, ranges, "caption", beam, max_len, None, None, constraints, aset,
+                                 (n, early) + groups_of)
             return _named_pool("generated_sequences_", res)
         if n > 1:
             kv_layers = _repeat_clips(model, kv_layers, b, n)
@@ -1583,7 +1822,7 @@ def generate_cap(model, batch, groups, beam_size=None, max_generation_len=None, 
 @torch.no_grad()
 def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation_len=None, mode=None, seed=None, temperature=None,
                 top_k=None, top_p=None, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None, suppress_tokens=None,
-                length_penalty=None, candidates=None, beam_search=None, early_stopping=None):
+                length_penalty=None, candidates=None, beam_search=None, early_stopping=None, num_beam_groups=None, diversity_penalty=None):
     """VALOR.generate_qa, model/pretrain.py:1366-1459: the caption decoders with the question rows as the prompt ->
     {'generated_answers_t_v' | '_t_va' | '_t_a'}. mode, seed, temperature / top_k / top_p and the Constraints arguments are
     generate_cap's: None (beam search when beam_size_qa > 1, else greedy), 'greedy', or 'sample' -- one sampled answer per question, with
@@ -1594,7 +1833,8 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
     candidates: generate_cap's -- closed-vocabulary QA: the answer is always one of the candidates (AnswerSet.index_of). A per-sample set
     has one entry per question row, or one per clip (its sample_num question rows read it).
     beam_search / early_stopping: generate_cap's; under 'pool' the best hypothesis is the answer and 'sequence_scores_*' /
-    'sequence_logprobs_*' come beside it."""
+    'sequence_logprobs_*' come beside it. num_beam_groups / diversity_penalty: generate_cap's (the answer is the overall best of the
+    groups, 'sequence_groups_*' names its group)."""
     # the reference switches to beam search when beam_size_qa > 1 but decode_beam always searches with self.beam_size, task 'qa'
     # included (pretrain.py:1061): beam_size_qa is the switch, beam_size the width
     width = (model.beam_size if model.beam_size_qa > 1 else 1) if beam_size is None else beam_size
@@ -1604,6 +1844,7 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
         (repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens, length_penalty), candidates)
     if rule == "pool":
         _check_pool("generate_qa", 0, beam, max_len)
+    groups_of = _beam_groups("generate_qa", model, rule, beam, num_beam_groups, diversity_penalty, mode is None and beam > 1)
     sample_num = [int(n) for n in batch.get("sample_num", [])]
     was_training = model.training
     model.eval()
@@ -1619,7 +1860,7 @@ def generate_qa(model, batch, groups, prompt_cpu, beam_size=None, max_generation
             aset = aset.for_rows(b, sample_num if b != clips and aset.n_roots == clips else None)
         stream = _sample_stream(model, seed) if mode == "sample" else None
         res = _decode_groups(model, groups, b, kv_layers, ranges, prompt_cpu, beam, max_len, stream, sampling, constraints, aset,
-                             (1, early) if rule == "pool" else None)
+                             (1, early) + groups_of if rule == "pool" else None)
         if rule == "pool":
             return _named_pool("generated_answers_", res)
         return _named("generated_answers_", res, mode == "sample")

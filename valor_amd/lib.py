@@ -158,6 +158,8 @@ SIGNATURES = {
     "valor_beam_select": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "valor_beam_pool_step": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _vp, _vp],
+    "valor_beam_group_step": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _f, _i, _i, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "valor_scatter_rows": [_vp, _i, _vp, _vp, _vp, _i64, _i, _i64],
     "valor_cast_from_f32": [_vp, _i, _vp, _vp, _i64],
     "valor_mask_tokens": [_vp, _vp, _vp, _i, _i, _u64, _u64, _i64, _i64, _i64, _vp, _vp],
