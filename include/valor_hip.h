@@ -473,6 +473,28 @@ int valor_fine_score_pairs(void* stream, const void* featA, const float* maskA, 
                            const float* wStoreB, int64_t NS, const int64_t* cand, int64_t ld_cand, float* score, int64_t ld_score,
                            int NA, int C, int T, int Nv, int D);
 
+/* ---- retrieval search, pair alignments: the token-level detail of the same pairs (csrc/search_align.hip; valor_amd/search.py align_pairs,
+ * RetrievalIndex.explain / search(explain=True)). gfx950. Inputs, coverage and alignment as valor_fine_score_pairs. For the pair
+ * (query a, clip b = cand[a, c]), with valor_fine_fused_fwd's padding law and tie rule:
+ *     x[t,v] = S[t,v] * maskA[a,t]                  (the clip mask is all ones and implicit)
+ *     a2b[t] = max_v x, idx_a[t] = the FIRST arg max;   b2a[v] = max_t x, idx_b[v] = the FIRST arg max
+ *     termA[t] = 0.5 * (wA[t] * a2b[t]);   termB[v] = wB[v] != 0 ? 0.5 * (wB[v] * b2a[v]) : 0
+ *     credit_b[v] = termB[v], then + termA[t] for every t in ascending order with idx_a[t] == v
+ *     credit_a[t] = termA[t], then + termB[v] for every v in ascending order with idx_b[v] == t
+ *   every step of the credits in fp32, rounded on its own (no fma), so a host loop in fp32 reproduces them bit for bit from the
+ *   kernel's maxima and indices; in exact arithmetic either credit array sums to the pair's score.
+ *   Outputs are dense, C columns per query, and each may be NULL on its own, except that an index array comes with its value array:
+ *   score fp32 [NA, C] (valor_fine_score_pairs' expression); a2b fp32 + idx_a uint8 [NA, C, T]; b2a fp32 + idx_b uint8 [NA, C, Nv];
+ *   credit_a fp32 [NA, C, T]; credit_b fp32 [NA, C, Nv]; sim fp32 [NA, C, T, Nv] = x itself (64-bit offsets).
+ *   A candidate outside [0, NS), -1 included, is never dereferenced: its score is -inf, its index bytes 255, its other floats 0.
+ *   One launch, no workspace, no float atomics: the same input gives the same bits. NA == 0 or C == 0: no-op. VALOR_ERR_ARG before any
+ *   launch on a null input pointer, a misaligned pointer, ld_cand < C, a negative count, a shape outside the coverage, or an index
+ *   array without its value array or the other way round. */
+int valor_fine_align_pairs(void* stream, const void* featA, const float* maskA, const float* wA, const void* storeB,
+                           const float* wStoreB, int64_t NS, const int64_t* cand, int64_t ld_cand, int NA, int C, int T, int Nv, int D,
+                           float* score, float* a2b, uint8_t* idx_a, float* b2a, uint8_t* idx_b, float* credit_a, float* credit_b,
+                           float* sim);
+
 /* ---- fused multi-tensor AdamW + global-norm clip over flat arenas.  Replaces optim/adamw.py:40-103, optim/misc.py:66-77
  * (10 param groups), torch clip_grad_norm_ (train_utils.py:358-360) and apex-amp's master<->model copies
  * (apex/apex/amp/_process_optimizer.py:14-22). n % valor_adamw_chunk() == 0; chunk_group: int8 [n/chunk], -1 = skip. */

@@ -137,6 +137,7 @@ SIGNATURES = {
     "valor_fp8_quantize_rows": [_vp, _i, _vp, _i64, _i64, _i, _vp, _vp],
     "valor_fine_fused_fwd_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
     "valor_fine_score_pairs": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i],
+    "valor_fine_align_pairs": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "valor_adamw_chunk": [],
     "valor_adamw_set_nt": [_i],
     "valor_adamw": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _c.POINTER(_f), _c.POINTER(_f), _i, _f, _f, _f, _i, _i, _vp, _i],

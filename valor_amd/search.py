@@ -29,10 +29,17 @@ feature store (score_pairs; the law restated in fp64 by pair_scores_host). Three
                                         candidates, they are re-scored on the exact features, the exact top k is returned with the
                                         exact scores. shortlist=0 (and every index without a store) is the fp8-only search.
 
+Pair alignments (csrc/search_align.hip): valor_fine_align_pairs keeps what the pair score reduces away -- per pair the maxima of either
+direction, their first arg maxima, the score split over the text tokens and over the clip tokens (the credits), and on request the
+masked token similarities (align_pairs; the law restated by align_pairs_host / credits_host). explain(model, queries, candidates)
+returns them as an Alignment for given bank indices, search(..., explain=True) attaches one for exactly the returned indices; the
+scores and indices of the search are untouched. `token_layout` names the modality of every clip token, so the clip credits can be
+summed per modality (Alignment.clip_credit_by_modality) and the best clip token named (Alignment.best_clip_token).
+
 Out of scope: dual_softmax (it needs the whole matrix), the va / vta / atv directions, a bank sharded over GPUs,
 deletion, approximate search, a coarse first stage, kernel reads of host memory (the host store is gathered and copied), fp32 or
 coarse pair scores; for fp8 banks also coarse banks (they need an fp8 GEMM), block-scaled (MX) codes, and fp8 anywhere in validate_ret
-or training."""
+or training; alignments on coarse banks or straight on fp8 codes, the clip -> text direction, word strings, span selection."""
 import ctypes
 
 import torch
@@ -226,6 +233,155 @@ def score_pairs(ft, mask, wq, store, wstore, cand):
     return out
 
 
+# ------------------------------------------------------------------ pair alignments: the law on the host (checks only) and the wrapper
+def credits_host(a2b, idx_a, b2a, idx_b, wA, wB):
+    """The credit sequence of valor_fine_align_pairs on given maxima and arg-max bytes, in fp32 on the CPU, every step rounded on its
+    own: termA = 0.5 * (wA * a2b); termB = wB != 0 ? 0.5 * (wB * b2a) : 0; credit_b[v] = termB[v], then + termA[t] for t ascending
+    with idx_a[t] == v; credit_a[t] = termA[t], then + termB[v] for v ascending with idx_b[v] == t. a2b / idx_a [..., T], b2a / idx_b
+    [..., Nv]; wA and wB broadcast against them. Returns (credit_a fp32 [..., T], credit_b fp32 [..., Nv])."""
+    f32 = lambda t: torch.as_tensor(t).detach().cpu().float()
+    a2b, b2a = f32(a2b), f32(b2a)
+    ia, ib = torch.as_tensor(idx_a).detach().cpu().long(), torch.as_tensor(idx_b).detach().cpu().long()
+    wA, wB = f32(wA).expand_as(a2b), f32(wB).expand_as(b2a)
+    T, Nv = a2b.shape[-1], b2a.shape[-1]
+    termA = 0.5 * (wA * a2b)
+    termB = torch.where(wB != 0, 0.5 * (wB * b2a), torch.zeros_like(b2a))
+    credit_a, credit_b = termA.clone(), termB.clone()
+    slots_v, slots_t = torch.arange(Nv), torch.arange(T)
+    for t in range(T):
+        credit_b = torch.where(ia[..., t, None] == slots_v, credit_b + termA[..., t, None], credit_b)
+    for v in range(Nv):
+        credit_a = torch.where(ib[..., v, None] == slots_t, credit_a + termB[..., v, None], credit_a)
+    return credit_a, credit_b
+
+
+def align_pairs_host(featA, maskA, wA, store, wstore, cand, sim=False):
+    """What valor_fine_align_pairs computes, on the CPU: for the pairs (query a, clip cand[a, c]) x = S * maskA in fp64 on the
+    bf16-rounded features (the clip mask all ones), the maxima and FIRST arg maxima of either direction from it, the score as
+    pair_scores_host, and the credits by credits_host on the fp32-rounded maxima. A candidate outside [0, NS): score -inf, index
+    bytes 255, every other number 0. A dict: score fp64 [NA, C]; a2b fp64, idx_a uint8 [NA, C, T]; b2a fp64, idx_b uint8 [NA, C, Nv];
+    credit_a fp32 [NA, C, T]; credit_b fp32 [NA, C, Nv]; sim fp64 [NA, C, T, Nv] or None."""
+    bf = lambda t: t.detach().cpu().to(torch.bfloat16).double()
+    f64 = lambda t: t.detach().cpu().double()
+    fa, fs, mA, wa, ws = bf(featA), bf(store), f64(maskA), f64(wA), f64(wstore)
+    cand = cand.detach().cpu().long()
+    NA, C = cand.shape
+    NS, Nv = fs.shape[:2]
+    T = fa.shape[1]
+    ok = (cand >= 0) & (cand < NS)
+    safe = torch.where(ok, cand, torch.zeros_like(cand))
+    x = torch.empty((NA, C, T, Nv), dtype=torch.float64)
+    for a in range(NA):
+        x[a] = torch.einsum("td,cvd->ctv", fa[a], fs[safe[a]]) * mA[a][None, :, None]
+    xn = x.numpy()                                                       # numpy's argmax is the FIRST maximal index
+    a2b, b2a = x.max(dim=3)[0], x.max(dim=2)[0]
+    idx_a, idx_b = torch.from_numpy(xn.argmax(axis=3)), torch.from_numpy(xn.argmax(axis=2))
+    wsel = ws[safe] if NS else torch.zeros((NA, C, Nv), dtype=torch.float64)
+    score = ((a2b * wa[:, None, :]).sum(-1) + (b2a * wsel).sum(-1)) / 2.0
+    live3, live4 = ok[:, :, None], ok[:, :, None, None]
+    a2b, b2a = torch.where(live3, a2b, torch.zeros_like(a2b)), torch.where(live3, b2a, torch.zeros_like(b2a))
+    idx_a = torch.where(live3, idx_a, torch.full_like(idx_a, 255)).to(torch.uint8)
+    idx_b = torch.where(live3, idx_b, torch.full_like(idx_b, 255)).to(torch.uint8)
+    credit_a, credit_b = credits_host(a2b, idx_a, b2a, idx_b, wa[:, None, :], torch.where(live3, wsel, torch.zeros_like(wsel)))
+    return dict(score=torch.where(ok, score, torch.full_like(score, float("-inf"))), a2b=a2b, idx_a=idx_a, b2a=b2a, idx_b=idx_b,
+                credit_a=credit_a, credit_b=credit_b, sim=torch.where(live4, x, torch.zeros_like(x)) if sim else None)
+
+
+def align_pairs(ft, mask, wq, store, wstore, cand, sim=False):
+    """valor_fine_align_pairs on the pairs (query a, clip cand[a, c]): a dict of device tensors score fp32 [NA, C]; a2b fp32, idx_a
+    uint8 [NA, C, T]; b2a fp32, idx_b uint8 [NA, C, Nv]; credit_a fp32 [NA, C, T]; credit_b fp32 [NA, C, Nv]; sim fp32 [NA, C, T, Nv]
+    (sim=True) or None. Arguments and coverage as score_pairs; a candidate outside [0, NS) gives -inf, 255 and zeros."""
+    K._check_gpu(ft, mask, wq, store, wstore, cand)
+    if ft.dtype != torch.bfloat16 or store.dtype != torch.bfloat16 or ft.dim() != 3 or store.dim() != 3 or ft.shape[2] != store.shape[2]:
+        raise ValueError(f"align_pairs: bf16 [NA, T, D] queries and a bf16 [NS, Nv, D] store, got {tuple(ft.shape)} {ft.dtype}, {tuple(store.shape)} {store.dtype}")
+    NA, T, D = ft.shape
+    NS, Nv = store.shape[:2]
+    if D % 64 or D == 0 or not 1 <= T <= 64 or not 1 <= Nv <= 64:
+        raise ValueError(f"align_pairs: D % 64 == 0 and 1 .. 64 tokens on either side (valor_fine_align_pairs has no fallback), got T={T}, Nv={Nv}, D={D}")
+    for name, t, shape in (("mask", mask, (NA, T)), ("wq", wq, (NA, T)), ("wstore", wstore, (NS, Nv))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"align_pairs: {name}: a contiguous fp32 {list(shape)} tensor")
+    if not ft.is_contiguous() or not store.is_contiguous():
+        raise ValueError("align_pairs: contiguous features")
+    if cand.dtype != torch.int64 or cand.dim() != 2 or cand.shape[0] != NA or (cand.shape[1] > 1 and cand.stride(1) != 1):
+        raise ValueError(f"align_pairs: cand: an int64 [{NA}, C] tensor with unit column stride")
+    C = cand.shape[1]
+    f32, u8 = dict(dtype=torch.float32, device=ft.device), dict(dtype=torch.uint8, device=ft.device)
+    out = dict(score=torch.empty((NA, C), **f32), a2b=torch.empty((NA, C, T), **f32), idx_a=torch.empty((NA, C, T), **u8),
+               b2a=torch.empty((NA, C, Nv), **f32), idx_b=torch.empty((NA, C, Nv), **u8), credit_a=torch.empty((NA, C, T), **f32),
+               credit_b=torch.empty((NA, C, Nv), **f32), sim=torch.empty((NA, C, T, Nv), **f32) if sim else None)
+    if NA and C:
+        lib.call("valor_fine_align_pairs", K._stream(), ft.data_ptr(), mask.data_ptr(), wq.data_ptr(), store.data_ptr(), wstore.data_ptr(), NS,
+                 cand.data_ptr(), cand.stride(0) if NA > 1 else max(cand.stride(0), C), NA, C, T, Nv, D,
+                 *[None if out[n] is None else out[n].data_ptr() for n in ("score", "a2b", "idx_a", "b2a", "idx_b", "credit_a", "credit_b", "sim")])
+    return out
+
+
+MODALITIES = ("video", "audio")
+
+
+def _check_layout(layout, tokens):
+    """one part's token layout as a list of (modality, count) whose counts cover the part's tokens, or ValueError"""
+    try:
+        layout = [(str(m), int(n)) for m, n in layout]
+    except (TypeError, ValueError):
+        raise ValueError(f"token_layout: per part a list of (modality, count), got {layout!r}")
+    if any(m not in MODALITIES or n < 1 for m, n in layout) or sum(n for _, n in layout) != tokens:
+        raise ValueError(f"token_layout {layout}: modalities from {MODALITIES}, counts >= 1 that add up to the part's {tokens} tokens")
+    return layout
+
+
+class AlignmentPart:
+    """the alignment of one bank part, device tensors: score fp32 [NQ, C]; text_max fp32 / text_best uint8 [NQ, C, T] (every query token's
+    best clip token: value, slot); clip_max / clip_best [NQ, C, Nv] (every clip token's best query token); text_credit [NQ, C, T] and
+    clip_credit [NQ, C, Nv] (the part's score split over the tokens of either side); sim fp32 [NQ, C, T, Nv] or None; layout: the part's
+    [(modality, count), ...] or None."""
+
+    def __init__(self, out, layout):
+        self.score, self.text_max, self.text_best, self.clip_max, self.clip_best = out["score"], out["a2b"], out["idx_a"], out["b2a"], out["idx_b"]
+        self.text_credit, self.clip_credit, self.sim, self.layout = out["credit_a"], out["credit_b"], out["sim"], layout
+
+
+class Alignment:
+    """indices int64 [NQ, C] (bank indices; -1 = an empty slot: 255 / 0 in every part) and parts: one AlignmentPart, or two (video,
+    audio) under late fusion, each with its part's stored weights."""
+
+    def __init__(self, indices, parts):
+        self.indices, self.parts = indices, list(parts)
+
+    def _layouts(self):
+        if any(p.layout is None for p in self.parts):
+            raise ValueError("the index has no token_layout (a fused 'tva' bank built from features: pass from_features(..., token_layout=))")
+        return [p.layout for p in self.parts]
+
+    def clip_credit_by_modality(self):
+        """{"video": [NQ, C], "audio": [NQ, C]} fp32 on the device: the clip credits of every layout entry summed, added over the parts
+        (a modality the bank does not hold: zeros). Nothing is read back."""
+        out = {m: torch.zeros(self.indices.shape, dtype=torch.float32, device=self.indices.device) for m in MODALITIES}
+        for part, layout in zip(self.parts, self._layouts()):
+            v0 = 0
+            for m, n in layout:
+                out[m] = out[m] + part.clip_credit[:, :, v0:v0 + n].sum(-1)
+                v0 += n
+        return out
+
+    def best_clip_token(self):
+        """(part, modality index, token index within the modality), int64 [NQ, C] each, on the device: the clip token of largest credit
+        over all parts, the lowest (part, token) among equals (an equality mask and a min over positions: no arg max whose tie rule is
+        unspecified); the modality index counts the entries of the part's layout. An empty slot holds -1."""
+        layouts = self._layouts()
+        dev = self.indices.device
+        credit = torch.cat([p.clip_credit for p in self.parts], dim=-1)
+        n = credit.shape[-1]
+        pos = torch.arange(n, dtype=torch.int64, device=dev)
+        first = torch.where(credit == credit.amax(-1, keepdim=True), pos, torch.full_like(pos, n)).amin(-1).clamp(max=n - 1)
+        table = [(pi, mi, j) for pi, layout in enumerate(layouts) for mi, (_, cnt) in enumerate(layout) for j in range(cnt)]
+        table = torch.tensor(table, dtype=torch.int64, device=dev)
+        got = table[first]
+        got = torch.where((self.indices >= 0)[..., None], got, torch.full_like(got, -1))
+        return got[..., 0], got[..., 1], got[..., 2]
+
+
 def within_prepare(cand, NB):
     """The candidate rows of a subset search, made ready for the selection (torch ops: the device path and the host plan share them):
     every row sorted ascending, repeated entries and entries outside [0, NB) turned into -1. A position then stands for one clip, and
@@ -253,10 +409,12 @@ def within_host(score, cand, k):
 
 class SearchResult:
     """scores fp32 [NQ, k] and indices int64 [NQ, k] on the device (-inf / -1 where the bank has fewer than k clips); `.ids` reads the
-    indices back and maps them to the bank's clip ids (None for -1)."""
+    indices back and maps them to the bank's clip ids (None for -1). `alignment`: the Alignment of exactly these indices after
+    search(..., explain=True), None otherwise. Iterating gives (ids, scores, indices)."""
 
-    def __init__(self, scores, indices, bank_ids):
+    def __init__(self, scores, indices, bank_ids, alignment=None):
         self.scores, self.indices, self._bank_ids, self._ids = scores, indices, bank_ids, None
+        self.alignment = alignment
 
     @property
     def ids(self):
@@ -322,7 +480,7 @@ class RetrievalIndex:
     `exact_feats` are those features, one bf16 [clips, tokens, D] tensor per part."""
 
     def __init__(self, group, contra_type, late_fusion, feats, weights, ids, bank_dtype=None, *, scales=None, dtype=None, exact=None,
-                 exact_feats=None):
+                 exact_feats=None, token_layout=None):
         if group not in GROUPS:
             raise ValueError(f"group {group!r}: one of {GROUPS} (the va / vta / atv directions are not searchable)")
         if contra_type not in ("fine", "coarse"):
@@ -373,6 +531,30 @@ class RetrievalIndex:
         self._feats = [_Bank(f) for f in feats]
         self._weights = [None if w is None else _Bank(w) for w in weights]
         self.ids = list(ids)
+        self.token_layout = self._token_layout(token_layout)
+        # only a fused 'tva' bank's layout cannot be inferred from the group and the token counts: it alone is saved and handed on
+        self._layout_saved = self.token_layout is not None and group == "tva" and nparts == 1
+
+    def _token_layout(self, given):
+        """per part a list of (modality, count) over the clip's token axis, or None (a coarse bank; a fused 'tva' bank nobody described).
+        'tv', 'ta' and the two parts of a late-fusion bank hold one modality each: inferred from the token count."""
+        if self.contra_type != "fine":
+            if given is not None:
+                raise ValueError("token_layout: a coarse bank has no tokens")
+            return None
+        tokens = [int(b.data.shape[1]) for b in self._feats]
+        inferred = {"tv": [[("video", tokens[0])]], "ta": [[("audio", tokens[0])]]}.get(self.group)
+        if self.group == "tva" and len(tokens) == 2:
+            inferred = [[("video", tokens[0])], [("audio", tokens[1])]]
+        if given is None:
+            return inferred
+        given = list(given)
+        if len(given) != len(tokens):
+            raise ValueError(f"token_layout: one list of (modality, count) per bank part ({len(tokens)}), got {given!r}")
+        given = [_check_layout(l, n) for l, n in zip(given, tokens)]
+        if inferred is not None and given != inferred:
+            raise ValueError(f"token_layout {given}: a {self.group!r} bank{' under late fusion' if len(tokens) == 2 else ''} holds {inferred}")
+        return given
 
     # ------------------------------------------------------------------ description
     def __len__(self):
@@ -435,12 +617,16 @@ class RetrievalIndex:
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_features(cls, feats, weights=None, ids=None, *, group="tv", contra_type="fine", late_fusion=False, weights_softmaxed=False,
-                      bank_dtype=None, exact=None):
+                      bank_dtype=None, exact=None, token_layout=None):
         """An index over given tensors (device tensors; a CPU index can be saved and loaded but not searched). feats: [NB, Nv, D] (fine)
         or [NB, D] (coarse), or a (video, audio) pair for late_fusion 'tva'. weights (fine, one parts): the RAW token weights [NB, Nv],
         softmaxed here as validate_ret does; None = unit weights, which is what late_fusion always uses. weights_softmaxed: `weights`
         (one tensor per part) already are the softmaxed values. bank_dtype "fp8": the features are quantised on the device and dropped,
-        unless exact "device" / "host" keeps them for the two-stage search."""
+        unless exact "device" / "host" keeps them for the two-stage search. token_layout: per part a list of (modality, count) along the
+        clip's token axis, e.g. [[("video", 8), ("audio", 2)]] for a fused 'tva' bank (one part: the list itself will do); 'tv', 'ta' and
+        late-fusion banks infer theirs, a fused 'tva' bank without one has None (Alignment's per-modality methods then refuse)."""
+        if token_layout and isinstance(token_layout[0], (list, tuple)) and token_layout[0] and isinstance(token_layout[0][0], str):
+            token_layout = [token_layout]                                # one part given as the list itself
         if bank_dtype == "fp8" and contra_type != "fine":
             raise ValueError("bank_dtype='fp8': only fine banks are covered (a coarse bank needs an fp8 GEMM)")
         if group not in GROUPS:
@@ -456,7 +642,7 @@ class RetrievalIndex:
                 raise ValueError("late_fusion scores use unit token weights: pass none")
             ws = [_softmax_ones_mask(torch.ones(f.shape[:2], dtype=torch.float32, device=f.device) if w is None else w) for f, w in zip(feats, raw)]
         ids = list(range(feats[0].shape[0])) if ids is None else list(ids)
-        return cls(group, contra_type, late_fusion, feats, ws, ids, bank_dtype, exact=exact)
+        return cls(group, contra_type, late_fusion, feats, ws, ids, bank_dtype, exact=exact, token_layout=token_layout)
 
     def quantize(self, exact=None):
         """A new fp8 index over this fine bf16 / fp32 bank, quantised on the device; this index is untouched. exact "device" / "host":
@@ -464,12 +650,17 @@ class RetrievalIndex:
         if self.bank_dtype is not None:
             raise ValueError("the bank is quantised already")
         return RetrievalIndex(self.group, self.contra_type, self.late_fusion, self.feats, [None if w is None else w.clone() for w in self.weights],
-                              self.ids, "fp8", exact=exact)
+                              self.ids, "fp8", exact=exact, token_layout=self.token_layout)
 
     @staticmethod
     def encode_gallery(model, batch, group):
         """The bank rows of one gallery batch: the encoders named by the group's letters run with the text side off (the letters of a
         'ret%..' group list choose the encoders; compute_loss=False returns feat_v / feat_a). Returns (feats, softmaxed weights)."""
+        return RetrievalIndex._encode_gallery(model, batch, group)[:2]
+
+    @staticmethod
+    def _encode_gallery(model, batch, group):
+        """encode_gallery and the rows' token layout (None for coarse rows): (feats, softmaxed weights, layout)"""
         if group not in GROUPS:
             raise ValueError(f"group {group!r}: one of {GROUPS}")
         P, sp = model.P, model.spec
@@ -481,14 +672,15 @@ class RetrievalIndex:
                 feats = [ops.l2_normalize(ops.linear(torch.cat((fv, fa), dim=-1), P["va_fusion.weight"], P["va_fusion.bias"]))]
             else:
                 feats = [f for f, c in ((fv, "v"), (fa, "a")) if c in group]
-            return [f.detach().contiguous() for f in feats], [None] * len(feats)
+            return [f.detach().contiguous() for f in feats], [None] * len(feats), None
         named = [(n, f) for n, f, c in (("video", fv, "v"), ("audio", fa, "a")) if c in group]
         if late:
             feats = [f for _, f in named]
-            return [f.detach().contiguous() for f in feats], [_softmax_ones_mask(torch.ones(f.shape[:2], dtype=torch.float32, device=f.device)) for f in feats]
+            return ([f.detach().contiguous() for f in feats], [_softmax_ones_mask(torch.ones(f.shape[:2], dtype=torch.float32, device=f.device)) for f in feats],
+                    [[(n, int(f.shape[1]))] for n, f in named])
         feat = torch.cat([f for _, f in named], dim=1).detach().contiguous()
         raw = torch.cat([E._fine_weights(model, n, f) for n, f in named], dim=1)
-        return [feat], [_softmax_ones_mask(raw)]
+        return [feat], [_softmax_ones_mask(raw)], [[(n, int(f.shape[1])) for n, f in named]]      # the concatenation order
 
     @classmethod
     @torch.no_grad()
@@ -499,8 +691,9 @@ class RetrievalIndex:
         model.eval()
         for batch in loader:
             if index is None:
-                feats, ws = cls.encode_gallery(model, batch, group)
-                index = cls(group, model.spec.contra_type, bool(model.spec.late_fusion), feats, ws, list(batch["ids"]), bank_dtype, exact=exact)
+                feats, ws, layout = cls._encode_gallery(model, batch, group)
+                index = cls(group, model.spec.contra_type, bool(model.spec.late_fusion), feats, ws, list(batch["ids"]), bank_dtype, exact=exact,
+                            token_layout=layout)
             else:
                 index.add(model, batch)
         if index is None:
@@ -512,15 +705,24 @@ class RetrievalIndex:
         """Extend the bank in place by one gallery batch; earlier indices keep their meaning."""
         self._check_model(model)
         model.eval()
-        feats, ws = self.encode_gallery(model, batch, self.group)
-        self.add_features(feats, ws, batch["ids"])
+        feats, ws, layout = self._encode_gallery(model, batch, self.group)
+        self.add_features(feats, ws, batch["ids"], token_layout=layout)
 
-    def add_features(self, feats, weights, ids):
+    def add_features(self, feats, weights, ids, token_layout=None):
         """add() on encoded rows: one tensor per part, weights already softmaxed (None for coarse). An fp8 bank takes bf16 / fp32
-        features and quantises them first; a non-finite row raises ValueError before anything is appended."""
+        features and quantises them first; a non-finite row raises ValueError before anything is appended. token_layout: the rows'
+        own layout, if the caller knows it; it must be the bank's (rows of another layout, or of another token count, are refused)."""
         ids = list(ids)
         if len(feats) != len(self._feats) or any(f.shape[0] != len(ids) for f in feats):
             raise ValueError("one feature tensor per bank part, one row per id")
+        if self.contra_type == "fine":
+            for bank, f in zip(self._feats, feats):
+                if f.dim() != 3 or f.shape[1] != bank.data.shape[1]:
+                    raise ValueError(f"rows of {tuple(f.shape[1:])} against a bank part of {int(bank.data.shape[1])} tokens per clip ({self.token_layout})")
+            if token_layout is not None:
+                rows = [_check_layout(l, int(f.shape[1])) for l, f in zip(token_layout, feats)]
+                if self.token_layout is not None and rows != self.token_layout:
+                    raise ValueError(f"rows of token_layout {rows} against the bank's {self.token_layout}")
         if self.bank_dtype == "fp8":
             for bank, f in zip(self._feats, feats):
                 if f.shape[1:] != bank.data.shape[1:]:
@@ -543,6 +745,8 @@ class RetrievalIndex:
 
     # ------------------------------------------------------------------ persistence
     def save(self, path):
+        """Formats 1 (features), 2 (fp8 codes) and 3 (codes and the exact store). The token layout of a fused 'tva' bank (the one that
+        cannot be inferred) travels as the extra key "token_layout", outside the fingerprint; files without the key are what they were."""
         if self.bank_dtype == "fp8":
             blob = {"format": "valor_amd.RetrievalIndex/2", "fingerprint": self.fingerprint(), "ids": self.ids,
                     "codes": [f.cpu().clone() for f in self.feats], "scales": [s.cpu().clone() for s in self.scales],
@@ -550,10 +754,12 @@ class RetrievalIndex:
             if self.exact is not None:                                   # format 3 = format 2 + the exact store
                 blob["format"] = "valor_amd.RetrievalIndex/3"
                 blob["exact_feats"] = [e.cpu().clone() for e in self.exact_feats]
-            torch.save(blob, path)
-            return
-        torch.save({"format": "valor_amd.RetrievalIndex/1", "fingerprint": self.fingerprint(), "ids": self.ids,
-                    "feats": [f.cpu().clone() for f in self.feats], "weights": [None if w is None else w.cpu().clone() for w in self.weights]}, path)
+        else:
+            blob = {"format": "valor_amd.RetrievalIndex/1", "fingerprint": self.fingerprint(), "ids": self.ids,
+                    "feats": [f.cpu().clone() for f in self.feats], "weights": [None if w is None else w.cpu().clone() for w in self.weights]}
+        if self._layout_saved:
+            blob["token_layout"] = [[[m, n] for m, n in part] for part in self.token_layout]
+        torch.save(blob, path)
 
     @classmethod
     def load(cls, path, device):
@@ -567,10 +773,11 @@ class RetrievalIndex:
             feature_dtype = {str(t): t for t in (torch.bfloat16, torch.float32)}.get(fp.get("dtype"))
             index = cls(fp["group"], fp["contra_type"], fp["late_fusion"], [c.to(device) for c in blob["codes"]],
                         [w.to(device) for w in blob["weights"]], blob["ids"], "fp8", scales=[s.to(device) for s in blob["scales"]], dtype=feature_dtype,
-                        exact=fp.get("exact") if third else None, exact_feats=blob["exact_feats"] if third else None)
+                        exact=fp.get("exact") if third else None, exact_feats=blob["exact_feats"] if third else None,
+                        token_layout=blob.get("token_layout"))
         else:
             index = cls(fp["group"], fp["contra_type"], fp["late_fusion"], [f.to(device) for f in blob["feats"]],
-                        [None if w is None else w.to(device) for w in blob["weights"]], blob["ids"])
+                        [None if w is None else w.to(device) for w in blob["weights"]], blob["ids"], token_layout=blob.get("token_layout"))
         if index.fingerprint() != fp:
             raise ValueError(f"{path}: the stored tensors do not match the stored fingerprint {fp}")
         return index
@@ -707,29 +914,56 @@ class RetrievalIndex:
         """fp32 [NQ, C]: the exact scores of the bank indices cand (int64 [NQ, C] on the device; outside [0, NB): -inf), the parts of a
         late-fusion bank added. A host store costs one synchronisation: the indices are read back, their rows gathered into a pinned
         staging buffer and copied once; the kernel then reads the staging buffer with cand = arange."""
+        out = None
+        for store, ws, pairs in self._pair_operands(ft, cand):
+            sc = score_pairs(ft, mask, wq, store, ws, pairs)
+            out = sc if out is None else out.add_(sc)                    # late fusion: the tv and ta scores added, as the chunk path does
+        return out
+
+    def _pair_operands(self, ft, cand):
+        """What a pair kernel reads, per bank part: (store bf16 [NS, Nv, D], its softmaxed weights [NS, Nv], candidates into that store).
+        A bank or a "device" store is read in place; the rows of a "host" store are gathered into a pinned staging buffer and copied
+        once (the one synchronisation: the indices are read back), and the candidates become positions in it. Pair scores and pair
+        alignments share this."""
         store = self._pair_queries(ft)
         NQ, C = cand.shape
         NB = len(self)
-        out = None
-        if self.exact == "host" and NQ * C:
+        staged = self.exact == "host" and NQ * C
+        if staged:
             ok = (cand >= 0) & (cand < NB)
             flat = torch.where(ok, cand, torch.zeros_like(cand)).view(-1)
             local = torch.where(ok, torch.arange(NQ * C, dtype=torch.int64, device=cand.device).view(NQ, C), torch.full_like(cand, -1))
             flat_host = flat.cpu()                                       # the one synchronisation of a host-store search
         for part, bank in enumerate(store):
             ws = self._weights[part].view()
-            if self.exact == "host" and NQ * C:
+            if staged:
                 rows = (NQ * C,) + tuple(bank.data.shape[1:])
                 if part not in self._stage or self._stage[part][0].shape[0] < NQ * C:          # one pair of buffers per part, reused
                     self._stage[part] = (_pinned_empty(rows, torch.bfloat16), torch.empty(rows, dtype=torch.bfloat16, device=cand.device))
                 host, devbuf = self._stage[part][0][:NQ * C], self._stage[part][1][:NQ * C]
                 torch.index_select(bank.view(), 0, flat_host, out=host)
                 devbuf.copy_(host, non_blocking=True)
-                sc = score_pairs(ft, mask, wq, devbuf, ws.index_select(0, flat), local)
+                yield devbuf, ws.index_select(0, flat), local
             else:
-                sc = score_pairs(ft, mask, wq, bank.view(), ws, cand)
-            out = sc if out is None else out.add_(sc)                    # late fusion: the tv and ta scores added, as the chunk path does
-        return out
+                yield bank.view(), ws, cand
+
+    def _explain(self, ft, mask, wq, cand, sim):
+        layouts = self.token_layout or [None] * len(self._feats)
+        parts = [AlignmentPart(align_pairs(ft, mask, wq, store, ws, pairs, sim=sim), layout)
+                 for (store, ws, pairs), layout in zip(self._pair_operands(ft, cand), layouts)]
+        return Alignment(cand, parts)
+
+    @torch.no_grad()
+    def explain(self, model, batch_or_tokens, candidates, sim=False):
+        """The token alignments of given bank indices: candidates int64 [NQ, C] on the device, -1 (or anything outside the bank) = an
+        empty slot (score -inf, index bytes 255, zeros). Returns an Alignment: per bank part (one; video and audio under late_fusion,
+        each with the part's stored weights) every query token's best clip token, every clip token's best query token, the part's
+        score split over the tokens of either side and, with sim=True, the masked token similarities [NQ, C, T, Nv]. Coverage and
+        refusals as rescore(): a bf16 fine bank is read directly, an fp8 bank through its exact store ("host": one synchronisation);
+        coarse banks, fp32 banks and fp8 banks without a store raise ValueError. Queries as in search()."""
+        self._pair_store()
+        ft, mask, wq = self._queries(model, batch_or_tokens)
+        return self._explain(ft, mask, wq, self._check_candidates(candidates, ft.shape[0]), bool(sim))
 
     @torch.no_grad()
     def rescore(self, model, batch_or_tokens, candidates):
@@ -755,7 +989,7 @@ class RetrievalIndex:
         return min(MAX_SHORTLIST, SHORTLIST_FACTOR * int(k))
 
     @torch.no_grad()
-    def search(self, model, batch_or_tokens, k, chunk=None, *, within=None, shortlist=None):
+    def search(self, model, batch_or_tokens, k, chunk=None, *, within=None, shortlist=None, explain=False, sim=False):
         """The k best clips of every query: SearchResult (ids: list of lists, on demand; scores, indices: device [NQ, k]), best first,
         equal scores in index order. model None: batch_or_tokens = {'feat_t', 'mask', 'weight'} holds encoded queries (feat_t [NQ, T, D]
         or [NQ, D]; the text mask and RAW token weights of a fine model, None = ones).
@@ -764,7 +998,10 @@ class RetrievalIndex:
         shortlist (an fp8 bank with an exact store): the fp8 walk returns `shortlist` candidates (k <= shortlist <= 256), they are
         re-scored on the exact features and the exact top k is returned with the exact scores. None = default_shortlist(k) = min(256,
         4 k); 0 = fp8 scores only, which is all an index without a store does. With a "host" store the shortlist indices are read back,
-        their rows gathered and copied: ONE host synchronisation per search; with a "device" store there is none."""
+        their rows gathered and copied: ONE host synchronisation per search; with a "device" store there is none.
+        explain=True (every path; explain()'s coverage, checked before anything runs): the result carries `.alignment`, the Alignment
+        of exactly the returned indices (empty slots: 255 / 0), with the token similarities when sim=True. Scores and indices are
+        those of the search without it, bit for bit: the alignment's own score is not substituted."""
         if not 1 <= int(k) <= 256:
             raise ValueError("1 <= k <= 256 (valor_topk_rows)")
         k = int(k)
@@ -778,12 +1015,15 @@ class RetrievalIndex:
                 raise ValueError("shortlist: a two-stage search needs an fp8 bank with an exact store (exact='device' or 'host')")
             if not k <= shortlist <= MAX_SHORTLIST:
                 raise ValueError(f"k <= shortlist <= {MAX_SHORTLIST} (valor_topk_rows), got k={k}, shortlist={shortlist}")
-        if within is not None:
+        if within is not None or explain:
             self._pair_store()
         ft, mask, wq = self._queries(model, batch_or_tokens)
         NQ = ft.shape[0]
+        if explain:
+            self._pair_queries(ft)
+        attach = lambda val, idx: SearchResult(val, idx, self.ids, self._explain(ft, mask, wq, idx, bool(sim)) if explain else None)
         if within is not None:
-            return SearchResult(*self._select_within(ft, mask, wq, self._check_candidates(within, NQ), k), self.ids)
+            return attach(*self._select_within(ft, mask, wq, self._check_candidates(within, NQ), k))
         if shortlist:
             self._pair_queries(ft)
             k_out, k = k, shortlist
@@ -797,7 +1037,7 @@ class RetrievalIndex:
             topk_rows(score, k, col_base=c0, state=(top_val, top_idx), workspace=ws)
         if shortlist:                                                    # the second stage: exact scores of the fp8 walk's candidates
             top_val, top_idx = self._select_within(ft, mask, wq, top_idx, k_out)
-        return SearchResult(top_val, top_idx, self.ids)
+        return attach(top_val, top_idx)
 
     @torch.no_grad()
     def scores(self, model, batch_or_tokens, chunk=None):
