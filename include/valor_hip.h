@@ -111,6 +111,30 @@ int valor_gemm_deferred(void* stream, int dtype, int transA, int transB, int M, 
 int valor_gemm_pending_bytes(const valor_gemm_pending* pending, int64_t* bytes);
 int valor_gemm_reduce_group(void* stream, int dtype, const valor_gemm_pending* pendings, int n);
 
+/* ---- the weight gradients of a layer as ONE grouped split-K launch. Launched alone, each short wgrad of an AST / decoder layer is split
+ * until it fills a round of the 256 workgroup slots of the 256x256 kernel by itself: 7 .. 28 slices of 6 .. 37 K-tiles behind a full
+ * prologue and a full partial-tile epilogue each. A layer's six products are independent: issued together they fill the round with two
+ * slices (69 / 129 K-tiles per workgroup), a quarter of the partial-tile traffic and one ramp / tail instead of six.
+ *   valor_gemm_group_problem describes one product in `blob` and launches nothing. It takes bf16  C += alpha A^T . B  (valor_gemm's
+ *     transA = transB = 1, accumulate = 1, no bias / activation; rowsum_out as in valor_gemm) where valor_gemm_kernel_for answers 3,
+ *     valor_gemm's own split would leave at most 48 K-tiles per workgroup (the ViT / cross-K|V wgrads run 225 and keep their launches)
+ *     and no per-call policy is in force; anything else is VALOR_ERR_ARG and goes through valor_gemm / valor_gemm_deferred as before.
+ *   valor_gemm_group(stream, dtype, blobs, n, workspace, workspace_bytes) issues the n <= 8 described products as one launch. Slice plan:
+ *     the smallest common K-tile count per workgroup (>= 6) whose slice counts S_i = ceil(K_i / 64 / kt) fit sum tiles_i S_i <= 256; a
+ *     group whose tiles exceed half a round runs unsplit and accumulates straight into C. Partial tiles (bf16 under policy key 1) and the
+ *     [S][M] row-sum partials go to `workspace` (256-byte aligned; at most 65 MiB, VALOR_ERR_ARG if it does not fit), which stays
+ *     untouched until valor_gemm_reduce_group(stream, dtype, blobs, n) -- the blobs leave here as its pending products -- is enqueued.
+ *     Kernel: the four-wave loop of csrc/gemm8q.hip when the group's shortest K loop exceeds 48 K-tiles (policy key 12 = 0 / 1: never /
+ *     always), else the eight-wave pipelined loop; inside a slice every accumulator receives its K-tiles in valor_gemm's order.
+ *   valor_gemm_group_plan answers the plan for n shapes (M, N, K, fused row sums 0 / 1: 4 ints each) on the host: slices[n], ksteps[n]
+ *     (either may be NULL), info[4] = work items, shortest K loop in K-tiles, 1 if csrc/gemm8q.hip would run it, workspace bytes / 256.
+ * valor_amd queues eligible wgrads per stream and issues them at the end of the layer / of the backward pass (kernels.ReduceQueue;
+ * env VALOR_GROUP_WGRAD). */
+int valor_gemm_group_problem(valor_gemm_pending* blob, int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B,
+                             int64_t ldb, void* C, int64_t ldc, float alpha, int accumulate, void* rowsum_out, int rowsum_accumulate);
+int valor_gemm_group(void* stream, int dtype, valor_gemm_pending* blobs, int n, void* workspace, int64_t workspace_bytes);
+int valor_gemm_group_plan(const int* shapes, int n, int* slices, int* ksteps, int* info);
+
 /* selects the bf16 kernel of valor_gemm: 0 = register-staged 128x128 tiles, 1 = LDS-DMA (buffer_load ... lds) 128x128
  * single stage, 2 = LDS-DMA 128x128 double stage, 3 = 256x256 8-phase pipeline wherever eligible, 4 = measured per-shape
  * policy between 1 and 3 (default). Returns the previous value; v < 0 only queries. Tuning / A-B measurement hook. */

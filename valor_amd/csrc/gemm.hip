@@ -21,6 +21,7 @@
 // Split-K (gridDim.y > 1) writes fp32 partial tiles to a workspace; valor_gemm launches a
 // second kernel that sums the slices and applies the epilogue.
 #include "gemm_common.h"
+#include "gemm_group_plan.h"
 #include <stdlib.h>
 
 template <typename T, bool TA, bool TB>
@@ -812,6 +813,101 @@ extern "C" int valor_gemm_reduce_group(void* stream, int dtype, const void* pend
     else if (dtype == VALOR_DT_F32) hipLaunchKernelGGL((gemm_splitk_reduce_group<float>), dim3(a.first[a.n]), dim3(256), 0, st, a);
     else return VALOR_ERR_ARG;
     return valor_launch_status();
+}
+
+// ---- the weight gradients of a layer as ONE launch. Launched alone, each of these products is split along K until it fills a round of the
+// 256 family-3 slots by itself (gemm_impl below): 7 .. 28 slices of 6 .. 37 K-tiles, every one behind a full prologue and a full
+// partial-tile epilogue, and a reduction that reads it all back. A layer's products are independent; issued together they fill the round
+// with two slices each (gemm_group_plan.h).
+// valor_gemm_group_problem describes one product in `blob` (nothing is launched); VALOR_ERR_ARG = not a product the group takes (the
+// caller issues it through valor_gemm / valor_gemm_deferred): anything but a bf16  C += alpha A^T . B  that gemm_family sends to family 3.
+#define VALOR_BLOB_QUEUED 2       // PendingBlob::valid of a described, not yet launched problem
+extern "C" int valor_gemm_group_problem(void* blob, int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                                        void* C, int64_t ldc, float alpha, int accumulate, void* rowsum_out, int rowsum_accumulate) {
+    if (!blob) return VALOR_ERR_ARG;
+    PendingBlob* pb = (PendingBlob*)blob;
+    pb->valid = 0; pb->dtype = dtype; pb->p.kslices = 0;
+    if (dtype != VALOR_DT_BF16 || M <= 0 || N <= 0 || K <= 0 || !A || !B || !C || !accumulate) return VALOR_ERR_ARG;
+    if (t_gemm_tuning || gemm_family(dtype, 1, 1, M, N, K, false) != 3) return VALOR_ERR_ARG;
+    // a product whose own split already leaves long K loops (the ViT and cross-K|V weight gradients: 225 K-tiles per workgroup) gains
+    // nothing from a group and keeps its launch: the class gemm8q.hip was measured on
+    if (family3_ktiles_per_workgroup(M, N, K) > 48) return VALOR_ERR_ARG;
+    if ((lda % 8) || (ldb % 8) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || lda < M || ldb < N || ldc < N) return VALOR_ERR_ARG;
+    const int64_t extA = (int64_t)K * lda, extB = (int64_t)K * ldb, lim = (1ll << 31) - 65536;
+    if (extA * 2 >= lim || extB * 2 >= lim) return VALOR_ERR_ARG;           // (valor_gemm cuts such a contraction into launches)
+    GemmArgs& p = pb->p;
+    p.A = A; p.B = B; p.C = C; p.bias = nullptr; p.preact = nullptr; p.dact_aux = nullptr; p.ws = nullptr;
+    p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldaux = 0;
+    p.M = M; p.N = N; p.K = K; p.act = VALOR_ACT_NONE; p.accumulate = 1; p.out_f32 = 0;
+    p.kslices = 0; p.ksteps_per_slice = 0; p.alpha = alpha;
+    p.bytesA = (uint32_t)(extA * 2); p.bytesB = (uint32_t)(extB * 2);
+    p.rowsum_out = rowsum_out; p.rowsum_ws = nullptr; p.rowsum_acc = rowsum_accumulate;
+    p.fast_epi = 0; p.raster_g = 0; p.st_mode = 0; p.ws_bf16 = 0; p.defer_reduce = 0;
+    pb->valid = VALOR_BLOB_QUEUED;
+    return VALOR_OK;
+}
+
+// ONE launch for the n <= 8 products described in `blobs` (n x 256 bytes, valor_gemm_group_problem). The slice plan is gemm_group_plan's;
+// partial tiles go to `workspace` (bf16 under policy key 1), which must stay untouched until valor_gemm_reduce_group(stream, dtype, blobs, n)
+// -- the caller's next call -- has been enqueued: the blobs leave here as that call's pending products. A product the plan leaves unsplit
+// has accumulated into C when the launch is through and is skipped by the reduction. Kernel: the four-wave slot loop of gemm8q.hip when the
+// group's shortest K loop exceeds the key-12 threshold (48 K-tiles; key 12 = 0 / 1: never / always), else the eight-wave pipelined loop.
+extern "C" int valor_gemm_group(void* stream, int dtype, void* blobs, int n, void* workspace, int64_t workspace_bytes) {
+    if (n == 0) return VALOR_OK;
+    if (!blobs || n < 0 || n > VALOR_GEMM_GROUP || dtype != VALOR_DT_BF16 || workspace_bytes < 0) return VALOR_ERR_ARG;
+    if ((uintptr_t)workspace & 255) return VALOR_ERR_ARG;
+    GemmGroupShape shape[VALOR_GEMM_GROUP];
+    GemmGroupSlice plan[VALOR_GEMM_GROUP];
+    for (int i = 0; i < n; ++i) {
+        const PendingBlob* pb = (const PendingBlob*)((const char*)blobs + (size_t)i * 256);
+        if (pb->valid != VALOR_BLOB_QUEUED || pb->dtype != dtype) return VALOR_ERR_ARG;
+        shape[i].M = pb->p.M; shape[i].N = pb->p.N; shape[i].K = pb->p.K; shape[i].rowsum = pb->p.rowsum_out != nullptr;
+    }
+    const int bf16_partials = gemm_policy(1) ? 1 : 0;
+    int items = 0, min_ktiles = 0;
+    int64_t bytes = 0;
+    if (gemm_group_plan(shape, n, bf16_partials ? 2 : 4, workspace ? workspace_bytes : 0, plan, &items, &min_ktiles, &bytes) != 0) return VALOR_ERR_ARG;
+    GemmGroupArgs a;
+    a.n = n; a.first[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        PendingBlob* pb = (PendingBlob*)((char*)blobs + (size_t)i * 256);
+        GemmArgs& p = pb->p;
+        p.kslices = plan[i].slices;
+        p.ksteps_per_slice = plan[i].ksteps;
+        if (plan[i].slices > 1) {
+            p.ws = (float*)((char*)workspace + plan[i].ws_off);
+            p.rowsum_ws = p.rowsum_out ? (float*)((char*)workspace + plan[i].rs_off) : nullptr;
+            p.ws_bf16 = bf16_partials;
+            p.defer_reduce = 1;
+            pb->valid = 1;
+        } else {
+            pb->valid = 0;               // complete with the launch: nothing pending
+        }
+        a.g[i] = p;
+        a.first[i + 1] = a.first[i] + plan[i].tiles * plan[i].slices;
+    }
+    for (int i = n; i < VALOR_GEMM_GROUP; ++i) a.first[i + 1] = a.first[n];
+    const int mode = gemm_policy(12);
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 1 || (mode != 0 && min_ktiles > 48)) launch_gemm_8q_group(st, a);
+    else launch_gemm_8ph_group(st, a);
+    return valor_launch_status();
+}
+
+// the slice plan valor_gemm_group would run for n shapes (M, N, K, 1 if fused row sums: 4 ints each): slices[n] / ksteps[n] (may be NULL),
+// info[0 .. 3] = work items (grid), shortest K loop in K-tiles, 1 if it would run on gemm8q.hip, workspace bytes / 256 (rounded up). Host only.
+extern "C" int valor_gemm_group_plan(const int* shapes, int n, int* slices, int* ksteps, int* info) {
+    if (!shapes || !info || n < 1 || n > VALOR_GEMM_GROUP) return VALOR_ERR_ARG;
+    GemmGroupShape shape[VALOR_GEMM_GROUP];
+    GemmGroupSlice plan[VALOR_GEMM_GROUP];
+    for (int i = 0; i < n; ++i) { shape[i].M = shapes[4 * i]; shape[i].N = shapes[4 * i + 1]; shape[i].K = shapes[4 * i + 2]; shape[i].rowsum = shapes[4 * i + 3]; }
+    int items = 0, min_ktiles = 0;
+    int64_t bytes = 0;
+    if (gemm_group_plan(shape, n, gemm_policy(1) ? 2 : 4, -1, plan, &items, &min_ktiles, &bytes) != 0) return VALOR_ERR_ARG;
+    for (int i = 0; i < n; ++i) { if (slices) slices[i] = plan[i].slices; if (ksteps) ksteps[i] = plan[i].ksteps; }
+    const int mode = gemm_policy(12);
+    info[0] = items; info[1] = min_ktiles; info[2] = (mode == 1 || (mode != 0 && min_ktiles > 48)) ? 1 : 0; info[3] = (int)((bytes + 255) / 256);
+    return VALOR_OK;
 }
 
 static int gemm_impl(void* stream, int dtype, int transA, int transB, int M, int N, int K,

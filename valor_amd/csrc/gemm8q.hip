@@ -136,8 +136,9 @@ extern "C" int valor_gemm8q_read_stamps(void* host, int64_t bytes) {
 #endif
 
 // The k-slow x k-slow layout (the only one the launcher is given today) runs the slot order, the other layouts keep the four phases
+// The body takes its problem and its workgroup index `bid` among that problem's work items (gemm8.hip: gemm_8ph_body)
 template <bool TA, bool TB>
-__global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
+DEVINL void gemm_8q_body(const GemmArgs& p, const int bid) {
     typedef bf16_t T;
     constexpr bool SLOTS = TA && TB;
 #ifdef Q8_STAMP
@@ -161,11 +162,11 @@ __global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
     if (p.kslices > 1) {
         // work items (K-slice, tile) in slice-major order, a contiguous range per XCD, as in gemm_8ph_kernel
         const int ntiles = tiles_m * tiles_n;
-        const int item = xcd_remap(blockIdx.x, ntiles * p.kslices);
+        const int item = xcd_remap(bid, ntiles * p.kslices);
         slice = item / ntiles;
         logical = item - slice * ntiles;
     } else {
-        logical = xcd_remap(blockIdx.x, tiles_m * tiles_n);
+        logical = xcd_remap(bid, tiles_m * tiles_n);
     }
     int tm = logical / tiles_n, tn = logical - tm * tiles_n;
     if (p.raster_g > 0 && p.kslices <= 1) {       // L2-aware raster in groups of G tile columns (gemm8.hip)
@@ -547,8 +548,8 @@ __global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
 #endif
     }
 #ifdef Q8_STAMP
-    if (lane == 0 && blockIdx.x < Q8_STAMP_BLOCKS) {
-        uint64_t* o = q8_stamp_buf + ((int64_t)blockIdx.x * 4 + wave) * 64;
+    if (lane == 0 && bid < Q8_STAMP_BLOCKS) {
+        uint64_t* o = q8_stamp_buf + ((int64_t)bid * 4 + wave) * 64;
         for (int i = 0; i < 8; ++i) o[i] = st_[i];
         o[8] = __builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_ID
         o[9] = __builtin_amdgcn_s_getreg((31 << 11) | 20);      // XCC_ID
@@ -561,6 +562,17 @@ __global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
 #undef LOOP_DMA
 #undef LOOP_RD
 #undef PIN
+}
+
+template <bool TA, bool TB>
+__global__ __launch_bounds__(256) void gemm_8q_kernel(GemmArgs p) {
+    gemm_8q_body<TA, TB>(p, blockIdx.x);
+}
+// valor_gemm_group: the weight gradients of a layer in one launch, each workgroup on the slot loop of its own problem
+__global__ __launch_bounds__(256) void gemm_8q_kernel_grp(GemmGroupArgs a) {
+    int i = 0;
+    while (i + 1 < a.n && (int)blockIdx.x >= a.first[i + 1]) ++i;
+    gemm_8q_body<true, true>(a.g[i], (int)blockIdx.x - a.first[i]);
 }
 
 void launch_gemm_8q(hipStream_t st, int transA, int transB, const GemmArgs& p_in) {
@@ -585,4 +597,14 @@ void launch_gemm_8q(hipStream_t st, int transA, int transB, const GemmArgs& p_in
     else if (!transA && transB) VALOR_8Q_LAUNCH(false, true);
     else VALOR_8Q_LAUNCH(true, false);
 #undef VALOR_8Q_LAUNCH
+}
+
+void launch_gemm_8q_group(hipStream_t st, const GemmGroupArgs& a) {
+    const size_t lds = 2 * BUF_BYTES;
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipFuncSetAttribute((const void*)gemm_8q_kernel_grp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(gemm_8q_kernel_grp, dim3(a.first[a.n]), dim3(256), lds, st, a);
 }

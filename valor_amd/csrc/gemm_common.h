@@ -226,6 +226,16 @@ DEVINL void epilogue_store8(const GemmArgs& p, int m, int n0, f32x4_t a0, f32x4_
 void launch_gemm_8ph(hipStream_t st, int transA, int transB, const GemmArgs& p);
 // the same tile on four waves of 128x128 outputs (gemm8q.hip, policy key 12): general fp32 epilogue, results bit-identical to launch_gemm_8ph
 void launch_gemm_8q(hipStream_t st, int transA, int transB, const GemmArgs& p);
+// A group of up to 8 k-slow x k-slow family-3 problems in ONE launch (valor_gemm_group): the 1-D grid is the concatenation of the problems'
+// (slice, tile) items, workgroups [first[i], first[i + 1]) run the unchanged kernel body on g[i] with their index inside that range.
+struct GemmGroupArgs {
+    GemmArgs g[8];
+    int first[9];
+    int n;
+};
+// the group on the eight-wave pipelined loop (gemm8.hip, SCHED 1) / on the four-wave slot loop (gemm8q.hip); grid.x = a.first[a.n]
+void launch_gemm_8ph_group(hipStream_t st, const GemmGroupArgs& a);
+void launch_gemm_8q_group(hipStream_t st, const GemmGroupArgs& a);
 // 256x128 8-phase bf16 kernel, two workgroups per CU (gemm8n.hip). grid.x = tiles(256 x 128) * max(kslices, 1).
 void launch_gemm_8ph2(hipStream_t st, int transA, int transB, const GemmArgs& p);
 // the same tile on 512-thread workgroups (gemm8w.hip: 64x64 outputs per wave, four waves per SIMD), NN layout without split-K; p carries

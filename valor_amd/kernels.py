@@ -70,16 +70,29 @@ class ReduceQueue:
     BYTES = 1 << 30
     PIECE = _WS_BYTES            # every product is offered what valor_gemm gets: the same slice counts, bit-identical sums
     enabled = os.environ.get("VALOR_GROUP_REDUCE", "8") != "0"
+    # VALOR_GROUP_WGRAD=1: an eligible weight gradient (bf16  C += A^T . B  on the 256x256 kernel whose own split would leave at most 48
+    # K-tiles per workgroup: the AST / decoder layers' wgrads) is not launched when gemm() is called. It waits here, with references to
+    # its operands, and the products of a layer run as ONE launch at flush (valor_gemm_group: a common slice plan, two slices instead of
+    # 7 .. 28), followed by the grouped reduction. Default on (profiles/wgrad_group_ab.json, wgrad_group_step_ab.txt); 0: every product
+    # is launched when it is issued, exactly as before.
+    group_wgrad = os.environ.get("VALOR_GROUP_WGRAD", "1") != "0"
+    GROUP_WS = 72 << 20          # partial tiles of one grouped launch: at most 256 work items x 256 KiB, plus the row-sum partials
     _queues = {}
     _armed = False               # an end-of-backward flush is scheduled
+    _nqueued = 0                 # queued (not yet launched) products over all streams: guard_write's fast path
 
     def __init__(self, device, stream):
         import ctypes
         self.stream = stream
         self.ws = torch.empty(self.BYTES, dtype=torch.uint8, device=device)
         self.blobs = (ctypes.c_char * (256 * self.GROUP))()
-        self.n, self.off, self.done, self.dtype = 0, 0, [], None
+        self.nd, self.off, self.done, self.dtype = 0, 0, [], None       # nd: products launched, their reduction deferred
         self.targets = set()       # output / row-sum buffers of the pending products (see gemm(): no two of them may be the same)
+        # products waiting for their grouped launch: their descriptions, the tensors they will read and write (kept alive until the
+        # launch is enqueued) and the storages of their operands (guard_write: nobody may overwrite those before the launch)
+        self.gblobs = (ctypes.c_char * (256 * self.GROUP))()
+        self.gws = torch.empty(self.GROUP_WS, dtype=torch.uint8, device=device) if self.group_wgrad else None
+        self.gn, self.gtiles, self.held, self.operands = 0, 0, [], set()
 
     @classmethod
     def current(cls, device):
@@ -90,12 +103,55 @@ class ReduceQueue:
             q = cls._queues[key] = ReduceQueue(device, st)
         return q
 
+    @property
+    def n(self):
+        """products that wait for the flush: launched with their reduction deferred, or queued for the grouped launch"""
+        return self.nd + self.gn
+
+    @staticmethod
+    def tiles(M, N):
+        return ((M + 255) // 256) * ((N + 255) // 256)
+
+    def queue(self, dt, M, N, K_, a, lda, b, ldb, out, ldc, alpha, rowsum_out, rowsum_accumulate, done):
+        """describe  out += alpha a^T . b  for the next grouped launch; False (nothing queued) if valor_gemm_group does not take it"""
+        import ctypes
+        if self.gws is None:
+            self.gws = torch.empty(self.GROUP_WS, dtype=torch.uint8, device=out.device)
+        rc = lib.load().valor_gemm_group_problem(ctypes.addressof(self.gblobs) + 256 * self.gn, dt, M, N, K_, _ptr(a), lda, _ptr(b), ldb,
+                                                 _ptr(out), ldc, float(alpha), 1, _ptr(rowsum_out), int(rowsum_accumulate))
+        if rc == -1:
+            return False
+        if rc != 0:
+            raise lib.ValorHipError(f"valor_gemm_group_problem failed with code {rc}")
+        self.dtype = dt
+        self.gn += 1
+        self.gtiles += self.tiles(M, N)
+        ReduceQueue._nqueued += 1
+        self.held.append((a, b, out, rowsum_out))
+        self.operands |= {a.untyped_storage().data_ptr(), b.untyped_storage().data_ptr()}
+        self.done.append(done)
+        return True
+
+    def _drop_queued(self):
+        ReduceQueue._nqueued -= self.gn
+        self.gn, self.gtiles, self.held = 0, 0, []
+        self.operands.clear()
+
     def flush(self):
-        if self.n:
-            import ctypes
-            lib.call("valor_gemm_reduce_group", self.stream.cuda_stream, self.dtype, ctypes.cast(self.blobs, ctypes.c_void_p), self.n)
+        import ctypes
+        n = self.nd
+        if self.gn:
+            # the queued products as one launch; their blobs leave it as pending products and join the table of the reduction
+            # (queue() and gemm() keep n + gn <= GROUP). The launch goes to the queue's stream, whichever stream is current.
+            lib.call("valor_gemm_group", self.stream.cuda_stream, self.dtype, ctypes.cast(self.gblobs, ctypes.c_void_p), self.gn,
+                     self.gws.data_ptr(), self.gws.numel())
+            ctypes.memmove(ctypes.addressof(self.blobs) + 256 * n, self.gblobs, 256 * self.gn)
+            n += self.gn
+        if n:
+            lib.call("valor_gemm_reduce_group", self.stream.cuda_stream, self.dtype, ctypes.cast(self.blobs, ctypes.c_void_p), n)
+        self._drop_queued()
         done, self.done = self.done, []
-        self.n, self.off = 0, 0
+        self.nd, self.off = 0, 0
         self.targets.clear()
         for fn in done:
             fn()
@@ -120,10 +176,28 @@ class ReduceQueue:
         stale = cls._armed or any(q.n or q.done for q in cls._queues.values())
         if stale:
             for q in cls._queues.values():
-                q.n, q.off, q.done = 0, 0, []
+                q.nd, q.off, q.done = 0, 0, []
                 q.targets.clear()
+                q._drop_queued()          # products that never ran: nothing of them reaches the next step's gradients
             cls._armed = False
         return stale
+
+    @classmethod
+    def batch(cls):
+        """`with ReduceQueue.batch():` outside a backward pass (tests, tools): deferred / queued products issued inside wait, as they
+        would for the end of a backward pass, and are flushed at exit"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def held():
+            prev, cls._armed = cls._armed, True
+            try:
+                yield
+            finally:
+                cls._armed = prev
+                if not prev:
+                    cls.flush_all()
+        return held()
 
     @classmethod
     def _arm(cls):
@@ -135,6 +209,26 @@ class ReduceQueue:
             cls._armed = True
         except RuntimeError:          # not inside a backward pass (a direct call from a test): nothing will flush later -- do it now
             cls.flush_all()
+
+
+def guard_write(*tensors):
+    """A kernel is about to WRITE into these caller-supplied buffers (an `out=` / `C +=` target, a static buffer, an in-place update).
+    A weight gradient queued for a grouped launch reads its operands later than it was issued: if one of them lives in a storage that
+    is written now, its queue is flushed first -- the queued product sees the operand's value at the time it was issued. Freshly
+    allocated outputs need no check (the queue holds references: the allocator cannot hand out an operand's memory)."""
+    if not ReduceQueue._nqueued:
+        return
+    st = None
+    for t in tensors:
+        if t is None:
+            continue
+        sp = t.untyped_storage().data_ptr()
+        for q in ReduceQueue._queues.values():
+            if q.gn and sp in q.operands:
+                q.flush()
+                st = st or torch.cuda.current_stream(t.device)
+                if q.stream != st:
+                    st.wait_stream(q.stream)
 
 
 def _rowmajor(t):
@@ -158,6 +252,8 @@ def gemm(a, b, *, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, want_pr
     odt = out_dtype or a.dtype
     if out is None:
         out = torch.empty((M, N), dtype=odt, device=a.device)
+    else:
+        guard_write(out)
     assert out.shape == (M, N) and out.dtype == odt
     ldc = _rowmajor(out)
     out_f32 = 1 if (odt == torch.float32 and a.dtype != torch.float32) else 0
@@ -174,9 +270,21 @@ def gemm(a, b, *, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, want_pr
         # with the same C (or the same row-sum buffer) would race on a non-atomic read-modify-write (a weight used by two Linears of a
         # shallow stack: the shared-BERT text encoder / decoder, the tied word embedding). Such a product closes the group first.
         tg = {t.data_ptr() for t in (out, rowsum_out) if t is not None}
-        if q.n == q.GROUP or q.off + q.PIECE > q.BYTES or (q.n and q.dtype != dt) or (q.targets & tg):
+        if q.n >= q.GROUP or q.off + q.PIECE > q.BYTES or (q.n and q.dtype != dt) or (q.targets & tg):
             q.flush()
-        blob = ctypes.addressof(q.blobs) + 256 * q.n
+        # a grouped launch can only be split while its tiles fill at most half a round of the 256 workgroup slots (valor_gemm_group): a
+        # product that would push the queued ones past that closes their group -- at the bench shapes exactly a layer (126 / 108 tiles)
+        if q.gn and q.gtiles + q.tiles(M, N) > 128:
+            q.flush()
+        # the product joins the layer's grouped launch instead of running now: the short-slice wgrads only (the ViT / cross-K|V ones run
+        # 225 K-tiles per workgroup alone and keep their launches), with nothing in the epilogue but alpha and C +=
+        if (ReduceQueue.group_wgrad and trans_a and trans_b and accumulate and dt == DT_BF16 and not out_f32 and bias is None
+                and act == ACT_NONE and dact_aux is None
+                and q.queue(dt, M, N, K, a, lda, b, ldb, out, ldc, alpha, rowsum_out, rowsum_accumulate, defer_done)):
+            q.targets |= tg
+            ReduceQueue._arm()
+            return out
+        blob = ctypes.addressof(q.blobs) + 256 * q.nd
         lib.call("valor_gemm_deferred", _stream(), dt, int(trans_a), int(trans_b), M, N, K,
                  _ptr(a), lda, _ptr(b), ldb, _ptr(out), ldc, _ptr(bias), act, 0, _ptr(dact_aux), ldaux,
                  float(alpha), int(accumulate), out_f32, q.ws.data_ptr() + q.off, q.PIECE, _ptr(rowsum_out), int(rowsum_accumulate), blob)
@@ -184,7 +292,7 @@ def gemm(a, b, *, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, want_pr
         lib.call("valor_gemm_pending_bytes", blob, ctypes.cast(ctypes.byref(used), ctypes.c_void_p))
         if used.value:
             q.dtype = dt
-            q.n += 1
+            q.nd += 1
             q.off += used.value
             q.done.append(defer_done)
             q.targets |= tg
@@ -247,6 +355,8 @@ def bdrln_fwd(x, bias, residual, gamma, beta, eps, *, p_drop=0.0, seed=0, offset
     assert x.is_contiguous() and (residual is None or residual.is_contiguous())
     z = None
     if write_z:
+        if inplace_z:
+            guard_write(x)
         z = x if inplace_z else torch.empty_like(x)
     y = torch.empty_like(x) if want_y else None
     mean = torch.empty(rows, dtype=torch.float32, device=x.device) if want_y else None
@@ -299,6 +409,8 @@ def colsum(x, out=None, accumulate=False):
     if out is None:
         out = torch.empty(cols, dtype=x.dtype, device=x.device)
         accumulate = False
+    else:
+        guard_write(out)
     ws = workspace(x.device)
     assert ws.numel() >= part_blocks() * cols
     lib.call("valor_colsum", _stream(), dt_of(x), _ptr(x), rows, cols, ld, _ptr(ws), _ptr(out), 0, int(accumulate))
@@ -319,6 +431,7 @@ def attn_fwd(q, k, v, n_heads, *, mask=None, kv_range=None, kv_bmod=0, scale=Non
     assert E == n_heads * 64, "head_dim is fixed at 64"
     if scale is None:
         scale = 0.125
+    guard_write(o, lse)
     if o is None:
         o = torch.empty((B, Sq, E), dtype=q.dtype, device=q.device)
     if lse is None:
@@ -368,6 +481,7 @@ def attn_bwd(q, k, v, o, lse, dout, n_heads, *, dq=None, dk=None, dv=None, mask=
     Skv = k.shape[1]
     if scale is None:
         scale = 0.125
+    guard_write(dq, dk, dv)
     if dq is None:
         dq = torch.empty((B, Sq, E), dtype=q.dtype, device=q.device)
     if dk is None:
@@ -431,6 +545,7 @@ def cross_attn_fwd_fused(segs, k, v, n_heads, kv_bmod, *, scale=0.125, p_drop=0.
     if not _xattn_domain(segs, k, kv_bmod):
         return False
     import ctypes
+    guard_write(*[sg["o"] for sg in segs], *[sg["lse"] for sg in segs])
     arr = _xattn_segs(segs, kv_bmod, False)
     kb, kr = _bsr(k); vb, vr = _bsr(v)
     return _xattn_call("valor_cross_attn_fwd_fused", _stream(), DT_BF16, ctypes.cast(arr, ctypes.c_void_p), len(segs), _ptr(k), _ptr(v),
@@ -443,6 +558,7 @@ def cross_attn_bwd_fused(segs, k, v, dk, dv, n_heads, kv_bmod, *, scale=0.125, p
     Returns False (nothing launched) when the shape is outside the fused kernel's domain -- the caller runs attn_bwd per pass."""
     if not _xattn_domain(segs, k, kv_bmod):
         return False
+    guard_write(dk, dv, *[sg["dq"] for sg in segs])
     arr = _xattn_segs(segs, kv_bmod, True)
     kb, kr = _bsr(k); vb, vr = _bsr(v); dkb, dkr = _bsr(dk); dvb, dvr = _bsr(dv)
     import ctypes

@@ -75,6 +75,9 @@ SIGNATURES = {
                             _f, _i, _i, _vp, _i64, _vp, _i, _vp],
     "valor_gemm_pending_bytes": [_vp, _vp],
     "valor_gemm_reduce_group": [_vp, _i, _vp, _i],
+    "valor_gemm_group_problem": [_vp, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _f, _i, _vp, _i],
+    "valor_gemm_group": [_vp, _i, _vp, _i, _vp, _i64],
+    "valor_gemm_group_plan": [_vp, _i, _vp, _vp, _vp],
     "valor_gemm_set_variant": [_i],
     "valor_gemm_kernel_for": [_i, _i, _i, _i, _i, _i, _i],
     "valor_gemm_wave128_for": [_i, _i, _i, _i, _i, _i, _i],

@@ -798,6 +798,7 @@ class DecoderXentFn(Function):
     def backward(ctx, *douts):
         h, w_emb, labels, lse, buf, w_rows = ctx.saved_tensors
         V, Vpad = ctx.V, buf.shape[1]
+        K.guard_write(buf)          # overwritten in place below: no queued weight gradient may still have to read it
         r0 = 0
         for nr, dl in zip(ctx.seg_rows, douts):        # (the outputs behind the segment losses have no gradient; an unused loss: zero)
             g = dl.to(torch.float32).contiguous() if dl is not None else torch.zeros((), dtype=torch.float32, device=h.device)
