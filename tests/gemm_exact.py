@@ -14,7 +14,7 @@ from functools import lru_cache
 import torch
 
 CANARY, UNWRITTEN = -320.0, -384.0       # both exact in bf16, both outside any result (|result| <= 256)
-ACT_NONE, ACT_RELU, ACT_DERIV = 0, 3, 16  # include/valor_hip.h
+from valor_amd.lib import ACT_DERIV, ACT_NONE, ACT_RELU  # noqa: E402  (plain constants: the library is not loaded)
 
 
 @dataclass(frozen=True)

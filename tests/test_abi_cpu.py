@@ -1,6 +1,6 @@
-"""CPU: the C-ABI library loads, exports every symbol include/valor_hip.h declares, the ctypes table matches the
-header, a C translation unit including the header compiles, and the product refuses to run without a GPU
-(no CPU fallback)."""
+"""CPU: the C-ABI library loads and exports exactly the symbols include/valor_hip.h declares, every kernel file is compiled against
+that header, the ctypes table of valor_amd/lib.py matches it by argument type, struct layout and constant value, a C translation unit
+including the header compiles, and the product refuses to run without a GPU (no CPU fallback)."""
 import ctypes
 import os
 import re
@@ -12,6 +12,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "valor_hip.h")
+CSRC = os.path.join(ROOT, "valor_amd", "csrc")
 
 
 def _decls():
@@ -33,9 +34,152 @@ def test_library_exports_every_header_symbol():
     for name in decls:
         assert hasattr(so, name), f"{name} declared in include/valor_hip.h but not exported"
     assert set(decls) == set(lib.SIGNATURES), set(decls) ^ set(lib.SIGNATURES)
-    for name, args in decls.items():
-        assert len(args) == len(lib.SIGNATURES[name]), (name, len(args), len(lib.SIGNATURES[name]))
     assert so.valor_adamw_chunk() == 1024 and so.valor_ln_part_blocks() > 0
+
+
+C_SCALARS = ("int", "int64_t", "uint64_t", "float", "double")
+
+
+def _c_class(param):
+    """class of one parameter of a prototype: "pointer" or one of C_SCALARS; anything else is an error, not a guess"""
+    if "*" in param:
+        return "pointer"
+    words = [w for w in param.split() if w != "const"]
+    assert len(words) == 2 and words[0] in C_SCALARS, f"unrecognised C parameter {param!r}"
+    return words[0]
+
+
+def _ctypes_class(t):
+    if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    # c_int32 / c_long alias c_int / c_int64 on this ABI: compare the classes, not the spellings
+    known = {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_uint64: "uint64_t", ctypes.c_float: "float", ctypes.c_double: "double"}
+    assert t in known, f"unrecognised ctypes argument {t!r}"
+    return known[t]
+
+
+def test_signatures_match_header_by_type():
+    """every argument of every entry of lib.SIGNATURES has the class of the header's parameter at that position: an int64_t stride bound
+    as c_int, or a float bound as c_int, has the right COUNT and the wrong calling convention"""
+    from valor_amd import lib
+    decls = _decls()
+    assert set(decls) == set(lib.SIGNATURES), set(decls) ^ set(lib.SIGNATURES)
+    for name, params in decls.items():
+        want = [_c_class(a) for a in params]
+        got = [_ctypes_class(t) for t in lib.SIGNATURES[name]]
+        assert got == want, (name, [(i, w, g) for i, (w, g) in enumerate(zip(want, got)) if w != g] or (len(want), len(got)))
+
+
+# public struct -> its ctypes mirror (valor_gemm_pending is opaque: its size is lib.GEMM_PENDING_BYTES)
+STRUCTS = dict(valor_gemm_policy="GemmPolicy", valor_xattn_seg="XattnSeg", valor_reward_tables="RewardTables",
+               valor_capeval_tables="CapevalTables", valor_capeval_summary="CapevalSummary")
+INT_MACROS = ("VALOR_DT_BF16", "VALOR_DT_F32", "VALOR_ACT_NONE", "VALOR_ACT_GELU_ERF", "VALOR_ACT_QUICK_GELU", "VALOR_ACT_RELU",
+              "VALOR_ACT_TANH", "VALOR_ACT_DERIV", "VALOR_STATS_FIELDS", "VALOR_METER_FIELDS", "VALOR_METER_MAX_SRC")
+
+
+def _struct_fields(name):
+    """member names of `typedef struct name { ... } name;` as the header spells them"""
+    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), src, flags=re.S).group(1)
+    out = []
+    for decl in body.split(";"):
+        for d in decl.split(","):
+            m = re.search(r"(\w+)\s*(?:\[\d+\])?\s*$", d)
+            if m:
+                out.append(m.group(1))
+    return out
+
+
+def test_struct_layouts_and_constants_match_header(tmp_path):
+    """gcc is the judge of the header: a C program prints sizeof, and offsetof / sizeof of every member, of every public struct and the
+    value of every public macro, and the ctypes classes and constants of valor_amd/lib.py must say the same"""
+    from valor_amd import lib
+    lines = []
+    for cname, pyname in STRUCTS.items():
+        fields = _struct_fields(cname)
+        assert fields == [f[0] for f in getattr(lib, pyname)._fields_], (cname, fields)
+        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'printf("{cname}.{f} %zu:%zu\\n", offsetof({cname}, {f}), sizeof((({cname}*)0)->{f}));' for f in fields]
+    assert _struct_fields("valor_gemm_pending") == ["opaque"]
+    lines.append('printf("valor_gemm_pending %zu\\n", sizeof(valor_gemm_pending));')
+    lines += [f'printf("{m} %d\\n", (int)({m}));' for m in INT_MACROS]
+    lines.append('printf("VALOR_TRIE_FLOOR %a\\n", (double)(VALOR_TRIE_FLOOR));')
+    c = tmp_path / "layout.c"
+    c.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "valor_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0;\n}\n")
+    exe = tmp_path / "layout"
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = dict(line.split() for line in r.stdout.splitlines())
+    assert len(got) == len(lines)
+
+    for cname, pyname in STRUCTS.items():
+        cls = getattr(lib, pyname)
+        assert int(got[cname]) == ctypes.sizeof(cls), (cname, got[cname], ctypes.sizeof(cls))
+        for f, _ in cls._fields_:
+            # offset AND size: a member that shrinks in front of alignment padding moves nothing else
+            assert got[f"{cname}.{f}"] == f"{getattr(cls, f).offset}:{getattr(cls, f).size}", (cname, f, got[f"{cname}.{f}"], getattr(cls, f))
+    assert int(got["valor_gemm_pending"]) == lib.GEMM_PENDING_BYTES
+    want = dict(VALOR_DT_BF16=lib.DT_BF16, VALOR_DT_F32=lib.DT_F32, VALOR_ACT_NONE=lib.ACT_NONE, VALOR_ACT_GELU_ERF=lib.ACT_GELU_ERF,
+                VALOR_ACT_QUICK_GELU=lib.ACT_QUICK_GELU, VALOR_ACT_RELU=lib.ACT_RELU, VALOR_ACT_TANH=lib.ACT_TANH, VALOR_ACT_DERIV=lib.ACT_DERIV,
+                VALOR_STATS_FIELDS=len(lib.STATS_FIELDS), VALOR_METER_FIELDS=len(lib.METER_FIELDS), VALOR_METER_MAX_SRC=lib.METER_MAX_SRC)
+    assert set(want) == set(INT_MACROS)
+    for m, v in want.items():
+        assert int(got[m]) == v, (m, got[m], v)
+    assert float.fromhex(got["VALOR_TRIE_FLOOR"]) == lib.TRIE_FLOOR
+
+
+def test_library_exports_exactly_the_header():
+    """the dynamic symbol table of the built library: every valor_* it defines is declared in the header, and the reverse"""
+    from valor_amd import lib
+    r = subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    exported = {ln.split()[-1] for ln in r.stdout.splitlines() if ln.split() and ln.split()[-1].startswith("valor_")}
+    assert exported == set(_decls()), exported ^ set(_decls())
+
+
+def _quoted_includes(path):
+    return [os.path.normpath(os.path.join(os.path.dirname(path), inc)) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), flags=re.M)]
+
+
+def _without_stamp_blocks(text):
+    """drop the `#if... *STAMP*` ... `#endif` blocks: the profiling builds' *_read_stamps entries are not part of the ABI"""
+    out, skip_depth, depth = [], None, 0
+    for line in text.splitlines():
+        d = line.strip()
+        if re.match(r"#\s*if", d):
+            depth += 1
+            if skip_depth is None and "STAMP" in d:
+                skip_depth = depth
+        if skip_depth is None:
+            out.append(line)
+        if re.match(r"#\s*endif", d):
+            if skip_depth == depth:
+                skip_depth = None
+            depth -= 1
+    assert depth == 0
+    return "\n".join(out)
+
+
+def test_every_kernel_file_is_compiled_against_the_header():
+    """the quoted #include graph of every csrc/*.hip reaches include/valor_hip.h, so the compiler compares each extern "C" definition
+    with its prototype; and no file declares a valor_* entry point itself: outside the stamp builds only definitions remain"""
+    hips = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    assert len(hips) >= 35
+    for f in hips:
+        seen, todo = set(), [os.path.join(CSRC, f)]
+        while todo:
+            p = todo.pop()
+            if p not in seen:
+                seen.add(p)
+                todo += _quoted_includes(p)
+        assert os.path.normpath(HDR) in seen, f"{f} never includes include/valor_hip.h"
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith((".hip", ".h")):
+            text = _without_stamp_blocks(re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(CSRC, f)).read(), flags=re.S))
+            redecl = re.findall(r'extern\s+"C"[^;{}()]*\b(valor_\w+)\s*\([^;{}]*\)\s*;', text)
+            assert not redecl, (f, redecl)
 
 
 def test_header_is_plain_c(tmp_path):

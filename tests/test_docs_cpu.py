@@ -49,7 +49,7 @@ def test_activation_ids_match_the_header():
     ids = {k: int(v) for k, v in re.findall(r"#define VALOR_ACT_(\w+)\s+(\d+)", hdr)}
     assert ids == {"NONE": lib.ACT_NONE, "GELU_ERF": lib.ACT_GELU_ERF, "QUICK_GELU": lib.ACT_QUICK_GELU, "RELU": lib.ACT_RELU,
                    "TANH": lib.ACT_TANH, "DERIV": lib.ACT_DERIV}
+    # the kernels take the ids from that header: csrc/common.h includes it and defines none of them again (only its internal mask)
     common = open(os.path.join(ROOT, "valor_amd", "csrc", "common.h")).read()
-    cids = {k: int(v) for k, v in re.findall(r"#define VALOR_ACT_(\w+)\s+(\d+)", common)}
-    for k, v in ids.items():
-        assert cids[k] == v, k
+    assert '#include "../../include/valor_hip.h"' in common
+    assert set(re.findall(r"#define VALOR_ACT_(\w+)", common)) == {"MASK"}

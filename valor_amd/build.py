@@ -41,7 +41,7 @@ def _headers_digest():
         if f.endswith(".h"):
             with open(os.path.join(CSRC, f), "rb") as fh:
                 h.update(fh.read())
-    with open(PUBLIC_HEADER, "rb") as fh:          # reward.hip takes valor_reward_tables from the public header
+    with open(PUBLIC_HEADER, "rb") as fh:          # csrc/common.h includes the public header: every file is compiled against it
         h.update(fh.read())
     return h.hexdigest()
 

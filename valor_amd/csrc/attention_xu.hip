@@ -21,14 +21,8 @@
 // A sub-tile only meets the tiles that intersect its group's kv_range (block-uniform skip); keys outside are masked.
 #include "attn_common.h"
 
-struct XuSeg {            // one decoder pass: q / o / dout / dq [B, Sq, E] views, lse [B, H, Sq], kv_range [B][2] or null
-    const void* q; const void* o; const void* dout; void* dq; const float* lse; const int* kv_range;
-    int64_t q_bs, q_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs;
-    int B, Sq;
-    uint64_t seed, offset;
-};
 struct XuArgs {
-    XuSeg s[2];
+    valor_xattn_seg s[2];       // one decoder pass each: q / o / dout / dq [B, Sq, E] views, lse [B, H, Sq], kv_range [B][2] or null
     const void* k; const void* v; void* dk; void* dv;
     int64_t k_bs, k_rs, v_bs, v_rs, dk_bs, dk_rs, dv_bs, dv_rs;
     int nseg, bmod, H, Skv;
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void attn_xu_bwd_kernel(XuArgs p) {
 #pragma unroll
         for (int u = 0; u < NQS; ++u) {
             if (sv_[u]) {
-                const XuSeg& sg = sg_[u] ? p.s[1] : p.s[0];
+                const valor_xattn_seg& sg = sg_[u] ? p.s[1] : p.s[0];
                 const int piece = wave & 1;
                 const int row = sq0_[u] + piece * 8 + prow;
                 if (wave < 2) {
@@ -133,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void attn_xu_bwd_kernel(XuArgs p) {
         for (int r0 = wave * 8; r0 < NQS * 16; r0 += 32) {
             const int u = r0 >> 4;                       // wave uniform (8 rows never straddle a sub-tile)
             const XuSub su = xu_sub(p, u, kvb);
-            const XuSeg& sg = su.seg ? p.s[1] : p.s[0];
+            const valor_xattn_seg& sg = su.seg ? p.s[1] : p.s[0];
             const int row = su.q0 + (r0 & 15) + (lane >> 3), c = lane & 7;
             float d = 0.f;
             const bool ok = su.valid && row < sg.Sq;
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void attn_xu_bwd_kernel(XuArgs p) {
                     const float kout = (key >= ss0_[u] && key < ss1_[u]) ? 0.f : INFINITY;     // key outside the group's range: P = 0
                     uint32_t hk = 0;
                     if (DROP) {
-                        const XuSeg& sg = sg_[u] ? p.s[1] : p.s[0];
+                        const valor_xattn_seg& sg = sg_[u] ? p.s[1] : p.s[0];
                         hk = attn_drop_headkey(sg.seed, (sg_[u] ? rng_off1 : rng_off0), sb_[u] * p.H + h);
                     }
                     const uint32_t row0 = (uint32_t)(sq0_[u] + 4 * g);
@@ -298,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void attn_xu_bwd_kernel(XuArgs p) {
 #pragma unroll
     for (int u = 0; u < NQS; ++u) {
         if (!sv_[u]) continue;
-        const XuSeg& sg = sg_[u] ? p.s[1] : p.s[0];
+        const valor_xattn_seg& sg = sg_[u] ? p.s[1] : p.s[0];
         const int qr = sq0_[u] + fr;
         if (qr < sg.Sq)
             store4<bf16_t>((bf16_t*)sg.dq + (int64_t)sb_[u] * sg.dq_bs + (int64_t)qr * sg.dq_rs + h * ATT_D + 16 * wave + 4 * g, dqacc[u] * p.scale);
@@ -362,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void attn_xu_fwd_kernel(XuArgs p) {
     for (int pc = wave; pc < 2 * NQS; pc += 4) {
         const int u = pc >> 1, piece = pc & 1;
         const XuSub su = xu_sub(p, u, kvb);
-        const XuSeg& sg = su.seg ? p.s[1] : p.s[0];
+        const valor_xattn_seg& sg = su.seg ? p.s[1] : p.s[0];
         if (su.valid) {
             const rsrc_t rq = xu_head_rsrc(sg.q, (int64_t)su.b * sg.q_bs + h * ATT_D, sg.Sq, sg.q_rs);
             glds16(rq, sQ + pc * 1024, (su.q0 + piece * 8 + prow) * (int)(sg.q_rs * 2) + pch * 16);
@@ -444,7 +438,7 @@ __global__ __launch_bounds__(256, 2) void attn_xu_fwd_kernel(XuArgs p) {
             f32x4_t pv;
             uint32_t hk = 0;
             if (DROP) {
-                const XuSeg& sg = sg_[u] ? p.s[1] : p.s[0];
+                const valor_xattn_seg& sg = sg_[u] ? p.s[1] : p.s[0];
                 hk = attn_drop_headkey(sg.seed, (sg_[u] ? rng_off1 : rng_off0), sb_[u] * p.H + h);
             }
             const uint32_t rowbase = (uint32_t)(sq0_[u] + fr) * (uint32_t)p.Skv;
@@ -487,7 +481,7 @@ __global__ __launch_bounds__(256, 2) void attn_xu_fwd_kernel(XuArgs p) {
 #pragma unroll
     for (int u = 0; u < NQS; ++u) {
         if (!sv_[u]) continue;
-        const XuSeg& sg = sg_[u] ? p.s[1] : p.s[0];
+        const valor_xattn_seg& sg = sg_[u] ? p.s[1] : p.s[0];
         const float* lp = sSum + u * 64 + fr;
         const float L = (lp[0] + lp[16]) + (lp[32] + lp[48]);
         const float inv = L > 0.f ? 1.0f / L : 0.f;
@@ -502,18 +496,9 @@ __global__ __launch_bounds__(256, 2) void attn_xu_fwd_kernel(XuArgs p) {
 // VALOR_ATTN_XFUSED=0 (or valor_attn_set_variant bit 3 cleared) keeps the per-pass kernels of attention_x.hip
 static int g_xu_on = [] { const char* e = getenv("VALOR_ATTN_XFUSED"); return e ? atoi(e) : 1; }();
 
-// plain C view of a segment (include/valor_hip.h: valor_xattn_seg)
-struct valor_xattn_seg_c {
-    const void* q; const void* o; const void* dout; void* dq; const float* lse; const int* kv_range;
-    int64_t q_bs, q_rs, o_bs, o_rs, do_bs, do_rs, dq_bs, dq_rs;
-    int B, Sq;
-    uint64_t seed, offset;
-};
-
 // shared argument handling of the two entries; bwd: the segments carry dout / dq too
-static int xu_fill(XuArgs& p, int dtype, const void* segs_, int nseg, const void* k, const void* v, int H, int Skv, int kv_bmod, int64_t k_bs,
+static int xu_fill(XuArgs& p, int dtype, const valor_xattn_seg* segs, int nseg, const void* k, const void* v, int H, int Skv, int kv_bmod, int64_t k_bs,
                    int64_t k_rs, int64_t v_bs, int64_t v_rs, float scale, float p_drop, bool bwd) {
-    const valor_xattn_seg_c* segs = (const valor_xattn_seg_c*)segs_;
     if (dtype != VALOR_DT_BF16 || !g_xu_on) return VALOR_ERR_ARG;          // the caller falls back to valor_attn_fwd / _bwd per pass
     if (!segs || nseg < 1 || nseg > 2 || !k || !v || H <= 0 || Skv < 64 || kv_bmod <= 0) return VALOR_ERR_ARG;
     if ((k_rs & 7) || (v_rs & 7) || (k_bs & 7) || (v_bs & 7) || ((uintptr_t)k & 15) || ((uintptr_t)v & 15)) return VALOR_ERR_ARG;
@@ -524,7 +509,7 @@ static int xu_fill(XuArgs& p, int dtype, const void* segs_, int nseg, const void
     p.k_bs = k_bs; p.k_rs = k_rs; p.v_bs = v_bs; p.v_rs = v_rs;
     int nsub = 0;
     for (int i = 0; i < nseg; ++i) {
-        const valor_xattn_seg_c& s = segs[i];
+        const valor_xattn_seg& s = segs[i];
         if (!s.q || !s.o || !s.lse || s.B <= 0 || s.Sq <= 0 || s.B % kv_bmod) return VALOR_ERR_ARG;
         if ((s.q_rs & 7) || (s.q_bs & 7) || ((uintptr_t)s.q & 15) || (int64_t)s.Sq * s.q_rs * 2 >= lim) return VALOR_ERR_ARG;
         if (bwd) {
@@ -532,10 +517,7 @@ static int xu_fill(XuArgs& p, int dtype, const void* segs_, int nseg, const void
             if ((s.o_rs & 7) || (s.o_bs & 7) || (s.do_rs & 7) || (s.do_bs & 7) || (s.dq_rs & 3) || (s.dq_bs & 3)) return VALOR_ERR_ARG;
             if (((uintptr_t)s.o & 15) || ((uintptr_t)s.dout & 15) || (int64_t)s.Sq * s.do_rs * 2 >= lim) return VALOR_ERR_ARG;
         } else if ((s.o_rs & 3) || (s.o_bs & 3)) return VALOR_ERR_ARG;
-        XuSeg& d = p.s[i];
-        d.q = s.q; d.o = s.o; d.dout = s.dout; d.dq = s.dq; d.lse = s.lse; d.kv_range = s.kv_range;
-        d.q_bs = s.q_bs; d.q_rs = s.q_rs; d.o_bs = s.o_bs; d.o_rs = s.o_rs; d.do_bs = s.do_bs; d.do_rs = s.do_rs; d.dq_bs = s.dq_bs; d.dq_rs = s.dq_rs;
-        d.B = s.B; d.Sq = s.Sq; d.seed = s.seed; d.offset = s.offset;
+        p.s[i] = s;
         const int qs = (s.Sq + 15) >> 4, n = (s.B / kv_bmod) * qs;
         if (i == 0) { p.qs0 = qs; p.n0 = n; } else p.qs1 = qs;
         nsub += n;
@@ -546,7 +528,7 @@ static int xu_fill(XuArgs& p, int dtype, const void* segs_, int nseg, const void
     return VALOR_OK;
 }
 
-extern "C" int valor_cross_attn_fwd_fused(void* stream, int dtype, const void* segs, int nseg, const void* k, const void* v, int H, int Skv,
+extern "C" int valor_cross_attn_fwd_fused(void* stream, int dtype, const valor_xattn_seg* segs, int nseg, const void* k, const void* v, int H, int Skv,
                                           int kv_bmod, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs, float scale, float p_drop,
                                           const uint64_t* rng_base) {
     XuArgs p = {};
@@ -573,7 +555,7 @@ extern "C" int valor_cross_attn_fwd_fused(void* stream, int dtype, const void* s
     return valor_launch_status();
 }
 
-extern "C" int valor_cross_attn_bwd_fused(void* stream, int dtype, const void* segs, int nseg, const void* k, const void* v, void* dk, void* dv,
+extern "C" int valor_cross_attn_bwd_fused(void* stream, int dtype, const valor_xattn_seg* segs, int nseg, const void* k, const void* v, void* dk, void* dv,
                                           int H, int Skv, int kv_bmod, int64_t k_bs, int64_t k_rs, int64_t v_bs, int64_t v_rs, int64_t dk_bs,
                                           int64_t dk_rs, int64_t dv_bs, int64_t dv_rs, float scale, float p_drop, const uint64_t* rng_base) {
     if (!dk || !dv || (dk_rs & 3) || (dv_rs & 3) || (dk_bs & 3) || (dv_bs & 3)) return VALOR_ERR_ARG;

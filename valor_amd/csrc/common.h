@@ -7,13 +7,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#define VALOR_DT_BF16 0
-#define VALOR_DT_F32 1
-
-#define VALOR_OK 0
-#define VALOR_ERR_ARG (-1)
-#define VALOR_ERR_LAUNCH (-2)
+// the C ABI: VALOR_DT_*, VALOR_OK / VALOR_ERR_*, VALOR_ACT_*, the public structs and the prototype of every entry point. Every .hip file
+// reaches this line, so a definition that drifts from its declaration does not compile.
+#include "../../include/valor_hip.h"
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -131,16 +127,12 @@ DEVINL uint32_t drop_threshold(float p) {
 }
 
 // ---------------------------------------------------------------- activations
-#define VALOR_ACT_NONE 0
-#define VALOR_ACT_GELU_ERF 1    // x*0.5*(1+erf(x/sqrt2))      bert.py:52-57, transformer.py:32-38
-#define VALOR_ACT_QUICK_GELU 2  // x*sigmoid(1.702x)           clip.py:167-169
-#define VALOR_ACT_RELU 3        // fine-weight MLP             pretrain.py:104-112
-#define VALOR_ACT_TANH 4
+// VALOR_ACT_* ids (include/valor_hip.h): GELU_ERF x*0.5*(1+erf(x/sqrt2)), QUICK_GELU x*sigmoid(1.702x), RELU (fine-weight MLP), TANH
 #define VALOR_ACT_MASK 15
-// flag on the activation id: the `preact` output of a forward GEMM holds act'(x) instead of x, and `dact_aux` of the matching dgrad holds
-// that derivative (the epilogue multiplies by it directly). sigmoid / erf / exp are evaluated ONCE, in the forward, where y = act(x) needs
-// them anyway: the dgrad epilogue drops from ~8-17 VALU instructions and two quarter-rate transcendentals per value to one multiply.
-#define VALOR_ACT_DERIV 16
+// VALOR_ACT_DERIV, the flag on the activation id: the `preact` output of a forward GEMM holds act'(x) instead of x, and `dact_aux` of the
+// matching dgrad holds that derivative (the epilogue multiplies by it directly). sigmoid / erf / exp are evaluated ONCE, in the forward,
+// where y = act(x) needs them anyway: the dgrad epilogue drops from ~8-17 VALU instructions and two quarter-rate transcendentals per
+// value to one multiply.
 
 // The activations run in GEMM epilogues at one value per MFMA output, i.e. on the VALU beside the matrix pipe: ViT fc1 alone is
 // 3.7e9 values per step. They are written for instruction count: v_rcp_f32 / v_exp_f32 (1 ulp) instead of IEEE division, and erf

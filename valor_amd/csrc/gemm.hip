@@ -541,7 +541,7 @@ extern "C" int valor_gemm_set_variant(int v) { const int o = g_gemm_variant; if 
 //      profiles/r06_generation_kernel_stats_{kvcache,skinny}.md
 // [12] family 3 on four waves of 128x128 outputs (gemm8q.hip): 0 = never, 1 = wherever family 3 runs and gemm8q.hip has the layout, 1000 = measured
 //      per-class choice (use_wave128). A process default only: the per-call valor_gemm_policy keeps its layout.
-thread_local const GemmTuning* t_gemm_tuning = nullptr;
+thread_local const valor_gemm_policy* t_gemm_tuning = nullptr;
 int g_gemm_policy_default[13] = {[] { const char* e = getenv("VALOR_GEMM_NT_MINK"); return e ? atoi(e) : 768; }(),
                         [] { const char* e = getenv("VALOR_GEMM_SPLITK_BF16"); return e ? atoi(e) : 1; }(),
                         [] { const char* e = getenv("VALOR_GEMM_MIN_TILES"); return e ? atoi(e) : 256; }(),
@@ -650,12 +650,11 @@ extern "C" int valor_gemm_kernel_for(int dtype, int transA, int transB, int M, i
 }
 // a valor_gemm_policy in force for the current call (and thread) only
 struct TuningScope {
-    const GemmTuning* prev;
-    explicit TuningScope(const void* t) : prev(t_gemm_tuning) { if (t) t_gemm_tuning = (const GemmTuning*)t; }
+    const valor_gemm_policy* prev;
+    explicit TuningScope(const valor_gemm_policy* t) : prev(t_gemm_tuning) { if (t) t_gemm_tuning = t; }
     ~TuningScope() { t_gemm_tuning = prev; }
 };
-static_assert(sizeof(GemmTuning) == 17 * sizeof(int), "valor_gemm_policy layout (include/valor_hip.h)");
-extern "C" int valor_gemm_kernel_for_tuned(const void* policy, int dtype, int transA, int transB, int M, int N, int K, int heavy_epilogue) {
+extern "C" int valor_gemm_kernel_for_tuned(const valor_gemm_policy* policy, int dtype, int transA, int transB, int M, int N, int K, int heavy_epilogue) {
     TuningScope scope(policy);
     return gemm_family(dtype, transA, transB, M, N, K, heavy_epilogue != 0);
 }
@@ -735,9 +734,9 @@ static int launch_gemm(hipStream_t st, int transA, int transB, GemmArgs p) {
     return valor_launch_status();
 }
 
-// what a deferred split-K product left to do (include/valor_hip.h: valor_gemm_pending, 256 opaque bytes)
+// what a deferred split-K product left to do: the contents of the caller's opaque valor_gemm_pending (include/valor_hip.h)
 struct PendingBlob { GemmArgs p; int dtype; int valid; };
-static_assert(sizeof(PendingBlob) <= 256, "valor_gemm_pending is 256 bytes");
+static_assert(sizeof(PendingBlob) <= sizeof(valor_gemm_pending), "PendingBlob lives in a valor_gemm_pending");
 
 static int gemm_impl(void* stream, int dtype, int transA, int transB, int M, int N, int K,
                      const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
@@ -756,7 +755,7 @@ extern "C" int valor_gemm(void* stream, int dtype, int transA, int transB, int M
 
 // valor_gemm under a per-call valor_gemm_policy (NULL = the process defaults): nothing global is read or written on behalf of the
 // fields that are set, so two threads (or two libraries in one process) can run different kernel choices side by side
-extern "C" int valor_gemm_tuned(const void* policy, void* stream, int dtype, int transA, int transB, int M, int N, int K,
+extern "C" int valor_gemm_tuned(const valor_gemm_policy* policy, void* stream, int dtype, int transA, int transB, int M, int N, int K,
                                 const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                                 const void* bias, int act, void* preact, const void* dact_aux, int64_t ldaux,
                                 float alpha, int accumulate, int out_f32, void* workspace, int64_t workspace_bytes,
@@ -773,7 +772,7 @@ extern "C" int valor_gemm_deferred(void* stream, int dtype, int transA, int tran
                                    const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                                    const void* bias, int act, void* preact, const void* dact_aux, int64_t ldaux,
                                    float alpha, int accumulate, int out_f32, void* workspace, int64_t workspace_bytes,
-                                   void* rowsum_out, int rowsum_accumulate, void* pending) {
+                                   void* rowsum_out, int rowsum_accumulate, valor_gemm_pending* pending) {
     if (!pending) return VALOR_ERR_ARG;
     PendingBlob* pb = (PendingBlob*)pending;
     pb->valid = 0; pb->dtype = dtype; pb->p.kslices = 0;
@@ -782,7 +781,7 @@ extern "C" int valor_gemm_deferred(void* stream, int dtype, int transA, int tran
 }
 
 // bytes of the workspace piece a pending product occupies (0: nothing pending), rounded up to 256
-extern "C" int valor_gemm_pending_bytes(const void* pending, int64_t* bytes) {
+extern "C" int valor_gemm_pending_bytes(const valor_gemm_pending* pending, int64_t* bytes) {
     if (!pending || !bytes) return VALOR_ERR_ARG;
     const PendingBlob* pb = (const PendingBlob*)pending;
     *bytes = 0;
@@ -793,13 +792,13 @@ extern "C" int valor_gemm_pending_bytes(const void* pending, int64_t* bytes) {
 }
 
 // ONE launch for the reductions (and epilogues: alpha, bias, C +=, fused row sums) of n <= 8 pending products of one dtype
-extern "C" int valor_gemm_reduce_group(void* stream, int dtype, const void* pendings, int n) {
+extern "C" int valor_gemm_reduce_group(void* stream, int dtype, const valor_gemm_pending* pendings, int n) {
     if (n <= 0) return VALOR_OK;
     if (!pendings || n > VALOR_REDUCE_GROUP) return VALOR_ERR_ARG;
     ReduceGroupArgs a;
     a.n = 0; a.first[0] = 0;
     for (int i = 0; i < n; ++i) {
-        const PendingBlob* pb = (const PendingBlob*)((const char*)pendings + (size_t)i * 256);
+        const PendingBlob* pb = (const PendingBlob*)(pendings + i);
         if (!pb->valid || pb->p.kslices <= 1) continue;
         if (pb->dtype != dtype) return VALOR_ERR_ARG;
         a.g[a.n] = pb->p;
@@ -822,7 +821,7 @@ extern "C" int valor_gemm_reduce_group(void* stream, int dtype, const void* pend
 // valor_gemm_group_problem describes one product in `blob` (nothing is launched); VALOR_ERR_ARG = not a product the group takes (the
 // caller issues it through valor_gemm / valor_gemm_deferred): anything but a bf16  C += alpha A^T . B  that gemm_family sends to family 3.
 #define VALOR_BLOB_QUEUED 2       // PendingBlob::valid of a described, not yet launched problem
-extern "C" int valor_gemm_group_problem(void* blob, int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
+extern "C" int valor_gemm_group_problem(valor_gemm_pending* blob, int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
                                         void* C, int64_t ldc, float alpha, int accumulate, void* rowsum_out, int rowsum_accumulate) {
     if (!blob) return VALOR_ERR_ARG;
     PendingBlob* pb = (PendingBlob*)blob;
@@ -847,19 +846,19 @@ extern "C" int valor_gemm_group_problem(void* blob, int dtype, int M, int N, int
     return VALOR_OK;
 }
 
-// ONE launch for the n <= 8 products described in `blobs` (n x 256 bytes, valor_gemm_group_problem). The slice plan is gemm_group_plan's;
+// ONE launch for the n <= 8 products described in `blobs` (valor_gemm_group_problem). The slice plan is gemm_group_plan's;
 // partial tiles go to `workspace` (bf16 under policy key 1), which must stay untouched until valor_gemm_reduce_group(stream, dtype, blobs, n)
 // -- the caller's next call -- has been enqueued: the blobs leave here as that call's pending products. A product the plan leaves unsplit
 // has accumulated into C when the launch is through and is skipped by the reduction. Kernel: the four-wave slot loop of gemm8q.hip when the
 // group's shortest K loop exceeds the key-12 threshold (48 K-tiles; key 12 = 0 / 1: never / always), else the eight-wave pipelined loop.
-extern "C" int valor_gemm_group(void* stream, int dtype, void* blobs, int n, void* workspace, int64_t workspace_bytes) {
+extern "C" int valor_gemm_group(void* stream, int dtype, valor_gemm_pending* blobs, int n, void* workspace, int64_t workspace_bytes) {
     if (n == 0) return VALOR_OK;
     if (!blobs || n < 0 || n > VALOR_GEMM_GROUP || dtype != VALOR_DT_BF16 || workspace_bytes < 0) return VALOR_ERR_ARG;
     if ((uintptr_t)workspace & 255) return VALOR_ERR_ARG;
     GemmGroupShape shape[VALOR_GEMM_GROUP];
     GemmGroupSlice plan[VALOR_GEMM_GROUP];
     for (int i = 0; i < n; ++i) {
-        const PendingBlob* pb = (const PendingBlob*)((const char*)blobs + (size_t)i * 256);
+        const PendingBlob* pb = (const PendingBlob*)(blobs + i);
         if (pb->valid != VALOR_BLOB_QUEUED || pb->dtype != dtype) return VALOR_ERR_ARG;
         shape[i].M = pb->p.M; shape[i].N = pb->p.N; shape[i].K = pb->p.K; shape[i].rowsum = pb->p.rowsum_out != nullptr;
     }
@@ -870,7 +869,7 @@ extern "C" int valor_gemm_group(void* stream, int dtype, void* blobs, int n, voi
     GemmGroupArgs a;
     a.n = n; a.first[0] = 0;
     for (int i = 0; i < n; ++i) {
-        PendingBlob* pb = (PendingBlob*)((char*)blobs + (size_t)i * 256);
+        PendingBlob* pb = (PendingBlob*)(blobs + i);
         GemmArgs& p = pb->p;
         p.kslices = plan[i].slices;
         p.ksteps_per_slice = plan[i].ksteps;

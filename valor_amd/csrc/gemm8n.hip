@@ -684,9 +684,6 @@ extern "C" int valor_gemm_set_narrow_sched(int v) {
     return old;
 }
 
-extern "C" int valor_gemm_set_tr_asm(int v);
-extern "C" int valor_gemm_set_fast_epilogue(int v);
-
 void launch_gemm_8ph2(hipStream_t st, int transA, int transB, const GemmArgs& p_in) {
     GemmArgs p = p_in;
     const int fast_mode = gemm_fast_epilogue_now(), tr_asm = gemm_tr_asm_now();

@@ -247,11 +247,10 @@ int launch_gemm_skinny(hipStream_t st, const GemmArgs& p);
 // ---- tuning knobs. Process defaults (valor_gemm_set_policy / _set_variant / ...; env presets) live in globals; a CALL can override any
 // of them through a valor_gemm_policy (include/valor_hip.h) handed to valor_gemm_tuned / valor_gemm_kernel_for_tuned: the entry points
 // park a pointer to it in a thread-local for the duration of the call, every read below looks there first. -1 = the process default.
-struct GemmTuning { int key[12]; int variant, tr_asm, fast_epilogue, sched_256, sched_narrow; };
-extern thread_local const GemmTuning* t_gemm_tuning;
+extern thread_local const valor_gemm_policy* t_gemm_tuning;
 extern int g_gemm_policy_default[13];     // valor_gemm_set_policy (gemm.hip); key 12 is a process default only (the per-call struct keeps its 17 ints)
 static inline int gemm_policy(int k) {
-    const GemmTuning* o = t_gemm_tuning;
+    const valor_gemm_policy* o = t_gemm_tuning;
     return (o && k < 12 && o->key[k] >= 0) ? o->key[k] : g_gemm_policy_default[k];
 }
 #define GEMM_KNOB(FIELD_, GLOBAL_) ((t_gemm_tuning && t_gemm_tuning->FIELD_ >= 0) ? t_gemm_tuning->FIELD_ : (GLOBAL_))

@@ -24,8 +24,6 @@
 
 #include "common.h"
 
-extern "C" int valor_reducer_destroy(void* reducer);
-
 // The handful of RCCL / NCCL types and constants this file needs, declared here instead of including <rccl/rccl.h>: the library is bound at
 // run time (below), so nothing of RCCL is needed to BUILD libvalor_hip.so either. Values are those of the stable NCCL ABI (nccl.h /
 // rccl.h: ncclSuccess 0, ncclSum 0, ncclFloat32 7, ncclBfloat16 9, a 128-byte opaque unique id, an opaque communicator pointer).

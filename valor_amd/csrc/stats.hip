@@ -33,8 +33,6 @@
 #define STATS_FIELDS 8
 #define STATS_FOLD_TILE 1024
 
-extern "C" int valor_adamw_chunk();
-
 struct StatsLr {
     float lr[STATS_MAX_GROUPS];
 };

@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import lib
-from .lib import ACT_NONE, DT_BF16, DT_F32
+from .lib import ACT_NONE, DT_BF16, DT_F32, GEMM_PENDING_BYTES
 
 _WS = {}
 _WS_BYTES = 256 << 20
@@ -85,12 +85,12 @@ class ReduceQueue:
         import ctypes
         self.stream = stream
         self.ws = torch.empty(self.BYTES, dtype=torch.uint8, device=device)
-        self.blobs = (ctypes.c_char * (256 * self.GROUP))()
+        self.blobs = (ctypes.c_char * (GEMM_PENDING_BYTES * self.GROUP))()
         self.nd, self.off, self.done, self.dtype = 0, 0, [], None       # nd: products launched, their reduction deferred
         self.targets = set()       # output / row-sum buffers of the pending products (see gemm(): no two of them may be the same)
         # products waiting for their grouped launch: their descriptions, the tensors they will read and write (kept alive until the
         # launch is enqueued) and the storages of their operands (guard_write: nobody may overwrite those before the launch)
-        self.gblobs = (ctypes.c_char * (256 * self.GROUP))()
+        self.gblobs = (ctypes.c_char * (GEMM_PENDING_BYTES * self.GROUP))()
         self.gws = torch.empty(self.GROUP_WS, dtype=torch.uint8, device=device) if self.group_wgrad else None
         self.gn, self.gtiles, self.held, self.operands = 0, 0, [], set()
 
@@ -117,7 +117,7 @@ class ReduceQueue:
         import ctypes
         if self.gws is None:
             self.gws = torch.empty(self.GROUP_WS, dtype=torch.uint8, device=out.device)
-        rc = lib.load().valor_gemm_group_problem(ctypes.addressof(self.gblobs) + 256 * self.gn, dt, M, N, K_, _ptr(a), lda, _ptr(b), ldb,
+        rc = lib.load().valor_gemm_group_problem(ctypes.addressof(self.gblobs) + GEMM_PENDING_BYTES * self.gn, dt, M, N, K_, _ptr(a), lda, _ptr(b), ldb,
                                                  _ptr(out), ldc, float(alpha), 1, _ptr(rowsum_out), int(rowsum_accumulate))
         if rc == -1:
             return False
@@ -145,7 +145,7 @@ class ReduceQueue:
             # (queue() and gemm() keep n + gn <= GROUP). The launch goes to the queue's stream, whichever stream is current.
             lib.call("valor_gemm_group", self.stream.cuda_stream, self.dtype, ctypes.cast(self.gblobs, ctypes.c_void_p), self.gn,
                      self.gws.data_ptr(), self.gws.numel())
-            ctypes.memmove(ctypes.addressof(self.blobs) + 256 * n, self.gblobs, 256 * self.gn)
+            ctypes.memmove(ctypes.addressof(self.blobs) + GEMM_PENDING_BYTES * n, self.gblobs, GEMM_PENDING_BYTES * self.gn)
             n += self.gn
         if n:
             lib.call("valor_gemm_reduce_group", self.stream.cuda_stream, self.dtype, ctypes.cast(self.blobs, ctypes.c_void_p), n)
@@ -284,7 +284,7 @@ def gemm(a, b, *, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, want_pr
             q.targets |= tg
             ReduceQueue._arm()
             return out
-        blob = ctypes.addressof(q.blobs) + 256 * q.nd
+        blob = ctypes.addressof(q.blobs) + GEMM_PENDING_BYTES * q.nd
         lib.call("valor_gemm_deferred", _stream(), dt, int(trans_a), int(trans_b), M, N, K,
                  _ptr(a), lda, _ptr(b), ldb, _ptr(out), ldc, _ptr(bias), act, 0, _ptr(dact_aux), ldaux,
                  float(alpha), int(accumulate), out_f32, q.ws.data_ptr() + q.off, q.PIECE, _ptr(rowsum_out), int(rowsum_accumulate), blob)
