@@ -482,6 +482,31 @@ int valor_fine_fused_fwd_fp8(void* stream, const uint8_t* codesA, const float* s
                              const float* maskA, const float* maskB, const float* wA, const float* wB, float* score, int NA, int NB,
                              int T, int Nv, int D);
 
+/* ---- retrieval search on an MXFP4 clip bank (csrc/search_mx.hip; valor_amd/search.py RetrievalIndex with bank_dtype="mxfp4"). gfx950.
+ * The OCP MX v1.0 block-scaled forms: one E8M0 scale byte (2^(byte - 127)) per block of 32 consecutive elements of a row. The format
+ * ids are the hardware's own (the cbsz / blgp field of v_mfma_scale_f32_16x16x128_f8f6f4).
+ * valor_mx_quantize_rows: every row of x (dtype VALOR_DT_BF16 / VALOR_DT_F32, [rows, ld], ld >= cols, cols % 32 == 0, rows 16-byte
+ *   aligned) becomes codes (fmt VALOR_MX_E4M3: uint8 [rows, cols]; VALOR_MX_E2M1: uint8 [rows, cols / 2], element 2i in the low nibble
+ *   of byte i; dense, 16-byte aligned) and scale bytes uint8 [rows, cols / 32]. Per block: amax = max |x|, e = floor(log2 amax) (a zero
+ *   or fp32-subnormal amax counts as -127), s = max(e - emax, -127) with emax 8 (e4m3) / 2 (e2m1), scale byte s + 127 (never 255),
+ *   code = RNE(min(max(x * 2^-s, -max), max)) with max 448 / 6: the power-of-two multiply is exact, ties go to the even code, the
+ *   sign of zero and the element format's subnormals are kept; an all-zero block has byte 0 and zero codes. The caller keeps
+ *   non-finite values out. rows == 0: no-op. VALOR_ERR_ARG before any launch on a null or misaligned pointer, an unknown dtype or fmt,
+ *   ld < cols, cols <= 0 or cols % 32 != 0.
+ * valor_fine_fused_fwd_mx: the scores-only mode of valor_fine_fused_fwd on such rows: score[a, b] fp32 [NA, NB] of
+ *   compute_fine_matrix_slice (pretrain.py:191-211) on the dequantised rows code * 2^(byte - 127). codesA uint8 [NA, T, D] (MX e4m3,
+ *   the queries), scaleA uint8 [NA, T, D / 32]; codesB uint8 [NB, Nv, D / 2] (MX e2m1, the bank), scaleB uint8 [NB, Nv, D / 32]; masks
+ *   and SOFTMAXED token weights as in valor_fine_fused_fwd. The element products and the scales are exact in fp32; only the
+ *   accumulation rounds. D % 128 == 0, 1 <= T, Nv <= 64, each code tensor below 0x7f000000 bytes and 16-byte aligned, the scale
+ *   tensors 4-byte aligned. No backward pass exists for it. NA == 0 or NB == 0: no-op. VALOR_ERR_ARG before any launch otherwise. */
+#define VALOR_MX_E4M3 0
+#define VALOR_MX_E2M1 4
+int valor_mx_quantize_rows(void* stream, int dtype, const void* x, int64_t ld, int64_t rows, int cols, int fmt, uint8_t* codes,
+                           uint8_t* scales);
+int valor_fine_fused_fwd_mx(void* stream, const uint8_t* codesA, const uint8_t* scaleA, const uint8_t* codesB, const uint8_t* scaleB,
+                            const float* maskA, const float* maskB, const float* wA, const float* wB, float* score, int NA, int NB,
+                            int T, int Nv, int D);
+
 /* ---- retrieval search, pair scores: every query against ITS OWN candidate list, read by index from a feature store (csrc/search_pairs.hip;
  * valor_amd/search.py score_pairs, RetrievalIndex.rescore / search(within=) / the two-stage search of an fp8 bank). gfx950.
  *   featA bf16 [NA, T, D]; maskA (the text mask) and wA (the SOFTMAXED text token weights) fp32 [NA, T], as in valor_fine_fused_fwd.

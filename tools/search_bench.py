@@ -25,7 +25,15 @@ it on the bf16 features, the exact top k is returned) on the same shapes, in one
 a "device" and with a "host" store at shortlists of k, 2 k, 4 k and 256. Per (NB, NQ, k) and variant: the median ms per search with the
 spread, the time over the fp8-only search of the same run, and the share of the bf16 bank's k best clips that the variant returns.
 The host store's search synchronises once per call (device events still span it: the stream idles meanwhile). Default --out
-profiles/search_rescore_bench.json."""
+profiles/search_rescore_bench.json.
+
+--bank-dtype mxfp4 | all times the MXFP4 bank (RetrievalIndex bank_dtype="mxfp4": MX e2m1 codes + E8M0 block scale bytes, queries
+quantised per call to MX e4m3, valor_fine_fused_fwd_mx on the block-scaled MFMA) alone / beside the bf16 and the fp8 bank, on the same
+shapes, features and queries in one process, in alternating timed windows as above (bf16, fp8, mxfp4, bf16, ...). Per (NB, NQ, k) and
+bank: the median search ms with the spread, the bank bytes and read rate, the time over the fp8 bank of the same run, and the share of
+the bf16 bank's top-k clips that the code bank alone returns. With --rescore the mxfp4 bank also keeps a "device" store and the
+two-stage search is timed at shortlists of k, 4 k, 8 k and 256, with the share of the bf16 top k it returns (the exact answer wherever
+the shortlist holds it). Default --out profiles/search_mx_bench.json."""
 import argparse
 import json
 import os
@@ -165,6 +173,70 @@ def compare_rescore(a, dev):
             "cases": cases}
 
 
+def compare_mx(a, dev):
+    """--bank-dtype mxfp4 / all (with or without --rescore)"""
+    kinds = ("bf16", "fp8", "mxfp4") if a.bank_dtype == "all" else ("mxfp4",)
+    free = torch.cuda.mem_get_info()[0]
+    cases = []
+    overlap = lambda got, want, k, NB, NQ: round(sum(len(set(g_) & set(w_)) for g_, w_ in zip(got, want)) / (min(k, NB) * NQ), 4)
+    for NB in a.nb:
+        if NB * NV * (D * (5.6 if a.rescore else 3.6) + 24) * 1.2 > free:         # bf16 bank, fp8 and mxfp4 codes, the device store
+            print(f"NB={NB}: the banks do not fit", flush=True)
+            continue
+        g = torch.Generator(device=dev).manual_seed(1)
+        fb = unit_bf16(NB, NV, dev, 2)
+        wb_raw = torch.randn((NB, NV), generator=g, device=dev)
+        bf16 = S.RetrievalIndex.from_features(fb, wb_raw, group="tva")
+        banks = {"bf16": bf16, "fp8": bf16.quantize(), "mxfp4": bf16.quantize(bank_dtype="mxfp4")}
+        banks = {kind: banks[kind] for kind in kinds}
+        stored = bf16.quantize(bank_dtype="mxfp4", exact="device") if a.rescore else None
+        for NQ in a.nq:
+            fa = unit_bf16(NQ, T, dev, 3)
+            wa_raw = torch.randn((NQ, T), generator=g, device=dev)
+            mask = (torch.arange(T, device=dev)[None] < torch.randint(8, T + 1, (NQ, 1), generator=g, device=dev)).float()
+            q = {"feat_t": fa, "mask": mask, "weight": wa_raw}
+            iters = max(3, min(a.iters, int(2e8 / (NB * NQ))))
+            for k in a.k:
+                variants = {kind: (lambda kind=kind: banks[kind].search(None, q, k)) for kind in kinds}
+                if stored is not None:
+                    for s_ in sorted({min(s_, S.MAX_SHORTLIST) for s_ in (k, 4 * k, 8 * k, S.MAX_SHORTLIST)}):
+                        variants[f"mxfp4+device/{s_}"] = lambda s_=s_: stored.search(None, q, k, shortlist=s_)
+                ms = {name: [] for name in variants}
+                for _ in range(a.rounds):
+                    for name, fn in variants.items():
+                        ms[name].append(timed(fn, iters))
+                med = {name: sorted(v)[len(v) // 2] for name, v in ms.items()}
+                want = bf16.search(None, q, k).indices.cpu().tolist()
+                res = {"NB": NB, "NQ": NQ, "k": k, "iters": iters, "rounds": a.rounds, "variants": {}}
+                if stored is not None:
+                    res["default_shortlist"] = stored.default_shortlist(k)
+                for name, fn in variants.items():
+                    row = {"search_ms": round(med[name], 4), "search_ms_min_max": [round(min(ms[name]), 4), round(max(ms[name]), 4)],
+                           "topk_overlap_with_bf16": overlap(fn().indices.cpu().tolist(), want, k, NB, NQ)}
+                    if name in banks:
+                        nbytes = banks[name].bank_bytes()
+                        row.update(chunk=banks[name].default_chunk(NQ, T), bank_GB=round(nbytes / 1e9, 4), bank_GBps=round(nbytes / med[name] / 1e6, 1))
+                    if "fp8" in med:
+                        row["over_fp8"] = round(med[name] / med["fp8"], 3)
+                    if name != "mxfp4":
+                        row["over_mxfp4_only"] = round(med[name] / med["mxfp4"], 3)
+                    res["variants"][name] = row
+                if stored is not None:
+                    res["mxfp4+device_bank_GB"] = round(stored.bank_bytes() / 1e9, 4)
+                if NB * NQ * 4 * 4 < free:
+                    res["largest_score_difference_mxfp4_bf16"] = round(float((banks["mxfp4"].scores(None, q) - bf16.scores(None, q)).abs().max()), 6)
+                print(json.dumps(res), flush=True)
+                cases.append(res)
+        banks.clear()
+        del bf16, stored, fb, wb_raw
+        torch.cuda.empty_cache()
+    return {"bench": "search_mx", "geometry": {"T": T, "Nv": NV, "D": D, "feature_dtype": "bfloat16", "banks": list(kinds), "rescore": bool(a.rescore)},
+            "device": torch.cuda.get_device_name(0), "hbm_peak_TBps": HBM_PEAK / 1e12, "hbm_achievable_TBps": HBM_ACHIEVABLE / 1e12,
+            "timing": "device events over warmed calls; the median of `rounds` windows per variant, the variants alternating inside a round",
+            "overlap": "share of the bf16 bank's k best clips that the variant returns (random unit vectors: a lower bound for structured data)",
+            "cases": cases}
+
+
 def write(doc, out):
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as fh:
@@ -178,14 +250,18 @@ def main():
     ap.add_argument("--nq", type=int, nargs="+", default=[1, 16, 64])
     ap.add_argument("--k", type=int, nargs="+", default=[10, 100])
     ap.add_argument("--iters", type=int, default=200, help="most calls per timed window (large cases take fewer)")
-    ap.add_argument("--bank-dtype", choices=("bf16", "fp8", "both"), default="bf16", help="fp8 / both: the fp8 bank instead of / beside the bf16 bank")
+    ap.add_argument("--bank-dtype", choices=("bf16", "fp8", "both", "mxfp4", "all"), default="bf16",
+                    help="fp8 / both: the fp8 bank instead of / beside the bf16 bank; mxfp4 / all: the MXFP4 bank alone / beside the bf16 and the fp8 bank")
     ap.add_argument("--rounds", type=int, default=3, help="--bank-dtype fp8 / both: timed windows per bank")
     ap.add_argument("--rescore", action="store_true", help="the two-stage search on an fp8 bank with an exact store beside the bf16 and the fp8-only search")
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (bf16), profiles/search_fp8_bench.json (fp8, both) or "
-                                                "profiles/search_rescore_bench.json (--rescore)")
+                                                "profiles/search_rescore_bench.json (--rescore); profiles/search_mx_bench.json (mxfp4, all)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "search_bench.py measures on the GPU"
     dev = torch.device("cuda:0")
+    if a.bank_dtype in ("mxfp4", "all"):
+        write(compare_mx(a, dev), a.out or os.path.join(ROOT, "profiles", "search_mx_bench.json"))
+        return
     if a.rescore:
         write(compare_rescore(a, dev), a.out or os.path.join(ROOT, "profiles", "search_rescore_bench.json"))
         return

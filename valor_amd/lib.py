@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("VALOR_HIP_LIB") or os.path.join(_HERE, "libvalor_hip.
 
 DT_BF16 = 0
 DT_F32 = 1
+MX_E4M3, MX_E2M1 = 0, 4      # VALOR_MX_* of include/valor_hip.h: the hardware's format ids of the block-scaled MFMA
 
 ACT_NONE, ACT_GELU_ERF, ACT_QUICK_GELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3, 4
 ACT_DERIV = 16      # flag: `preact` / `dact_aux` hold act'(x) instead of x (include/valor_hip.h)
@@ -140,6 +141,8 @@ SIGNATURES = {
     "valor_topk_rows": [_vp, _vp, _i64, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _i64],
     "valor_fp8_quantize_rows": [_vp, _i, _vp, _i64, _i64, _i, _vp, _vp],
     "valor_fine_fused_fwd_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
+    "valor_mx_quantize_rows": [_vp, _i, _vp, _i64, _i64, _i, _i, _vp, _vp],
+    "valor_fine_fused_fwd_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
     "valor_fine_score_pairs": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i],
     "valor_fine_align_pairs": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "valor_adamw_chunk": [],

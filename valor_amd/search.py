@@ -18,6 +18,14 @@ incoming rows with valor_fp8_quantize_rows; search() quantises the query rows pe
 valor_fine_fused_fwd_fp8 (the e4m3 MFMA form of valor_fine_fused_fwd, scores only). The quantisation law and the score law are restated
 on the host below (quantize_rows_host, fp8_scores_host). An index built without bank_dtype is what it was.
 
+bank_dtype="mxfp4" (fine banks only, opt-in; csrc/search_mx.hip): the bank keeps OCP MX e2m1 codes [NB, Nv, D / 2] (two elements per
+byte, element 2i in the low nibble) and one E8M0 scale byte per block of 32 elements [NB, Nv, D / 32] -- D / 2 + D / 32 bytes per token
+row, a little over half of an fp8 bank. Rows are encoded by valor_mx_quantize_rows (the OCP MX v1.0 conversion); search() quantises the
+query rows per call to MX e4m3 with the same kernel and scores a chunk with valor_fine_fused_fwd_mx, whose block-scaled MFMA takes
+the two formats and applies both scales in hardware. fp4 scores are coarse: the answer a user wants comes from the exact store and the
+two-stage search below, which an mxfp4 bank has exactly as an fp8 bank has them. The laws are restated on the host
+(mx_quantize_rows_host, mx_dequantize_host, mx_scores_host).
+
 Pair scores (csrc/search_pairs.hip): valor_fine_score_pairs scores every query against ITS OWN list of clips, read by index from a bf16
 feature store (score_pairs; the law restated in fp64 by pair_scores_host). Three things stand on it:
   rescore(model, queries, candidates)   the exact scores [NQ, C] of given bank indices (-1 allowed: -inf).
@@ -38,8 +46,9 @@ summed per modality (Alignment.clip_credit_by_modality) and the best clip token 
 
 Out of scope: dual_softmax (it needs the whole matrix), the va / vta / atv directions, a bank sharded over GPUs,
 deletion, approximate search, a coarse first stage, kernel reads of host memory (the host store is gathered and copied), fp32 or
-coarse pair scores; for fp8 banks also coarse banks (they need an fp8 GEMM), block-scaled (MX) codes, and fp8 anywhere in validate_ret
-or training; alignments on coarse banks or straight on fp8 codes, the clip -> text direction, word strings, span selection."""
+coarse pair scores; for fp8 and mxfp4 banks also coarse banks (they need a GEMM of their own) and quantised codes anywhere in
+validate_ret or training; e2m1 queries and MX-e4m3 or fp6 banks (the kernel's format arguments would allow them); alignments on coarse
+banks or straight on codes, the clip -> text direction, word strings, span selection."""
 import ctypes
 
 import torch
@@ -115,7 +124,9 @@ def topk_workspace_bytes(R, C, k):
 
 
 # ------------------------------------------------------------------ the fp8 bank's laws on the host (checks only)
-BANK_DTYPES = (None, "fp8")
+BANK_DTYPES = (None, "fp8", "mxfp4")
+_QUANTISED = ("fp8", "mxfp4")                                         # banks kept as codes and scales
+_SCORE_KERNEL = {"fp8": "valor_fine_fused_fwd_fp8", "mxfp4": "valor_fine_fused_fwd_mx"}
 _FP8_MAX, _FP8_TINY = 448.0, 2.0 ** -64
 
 
@@ -181,12 +192,117 @@ def _scores_fp8(qc, qs, bc, bs, maskA, maskB, wA, wB, out):
     return out
 
 
+# ------------------------------------------------------------------ the mxfp4 bank's laws on the host (checks only) and the wrappers
+MX_E4M3, MX_E2M1 = lib.MX_E4M3, lib.MX_E2M1                           # VALOR_MX_*: the hardware's format ids
+_MX_FORMATS = {MX_E4M3: (8, 448.0), MX_E2M1: (2, 6.0)}                # format -> (emax, largest magnitude)
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)                # the magnitude of every e2m1 code; bit 3 is the sign
+
+
+def _mx_format(fmt):
+    if fmt not in _MX_FORMATS:
+        raise ValueError(f"fmt {fmt!r}: MX_E4M3 ({MX_E4M3}) or MX_E2M1 ({MX_E2M1})")
+    return _MX_FORMATS[fmt]
+
+
+def mx_quantize_rows_host(x, fmt):
+    """What valor_mx_quantize_rows computes, restated on the CPU (the OCP MX v1.0 conversion): x [..., D], D % 32 == 0 -> (uint8 codes
+    [..., D] for MX_E4M3 / [..., D / 2] for MX_E2M1, element 2i in the low nibble of byte i; uint8 E8M0 scale bytes [..., D / 32]). Per
+    block of 32: amax = max |x|, e = the fp32 exponent field of amax - 127 (floor(log2 amax); zero and subnormal amax: -127),
+    s = max(e - emax, -127), byte = s + 127, code = RNE(clamp(x * 2^-s, -max, max)) -- the product is formed exactly (in fp64), ties go
+    to the even code, the sign of zero and the element format's subnormals are kept."""
+    emax, vmax = _mx_format(fmt)
+    x = x.detach().float().cpu().contiguous()
+    D = x.shape[-1]
+    if D % 32 or D == 0:
+        raise ValueError(f"mx_quantize_rows_host: rows of a multiple of 32 elements, got {tuple(x.shape)}")
+    blk = x.reshape(x.shape[:-1] + (D // 32, 32))
+    amax = blk.abs().amax(-1).contiguous()
+    e = ((amax.view(torch.int32) >> 23) & 0xff) - 127
+    s = (e - emax).clamp(min=-127)                                       # the upper clamp (127) is out of a finite fp32's reach
+    mul = ((127 - s) << 23).to(torch.int32).view(torch.float32)          # 2^-s, built from its bits
+    y = (blk.double() * mul.double()[..., None]).clamp(-vmax, vmax)
+    if fmt == MX_E4M3:
+        codes = y.float().to(torch.float8_e4m3fn).view(torch.uint8).reshape(x.shape)
+    else:
+        m = y.abs()
+        # seven compares at the midpoints of 0, .5, 1, 1.5, 2, 3, 4, 6: `>` where the lower neighbour has the even code, `>=` otherwise
+        c = sum(((m > t) if strict else (m >= t)).to(torch.uint8)
+                for t, strict in ((0.25, True), (0.75, False), (1.25, True), (1.75, False), (2.5, True), (3.5, False), (5.0, True)))
+        c = (c | (torch.signbit(blk).to(torch.uint8) << 3)).reshape(x.shape[:-1] + (D // 2, 2))
+        codes = c[..., 0] | (c[..., 1] << 4)
+    return codes.contiguous(), (s + 127).to(torch.uint8)
+
+
+def mx_dequantize_host(codes, scales, fmt):
+    """The values MX codes stand for, fp64 [..., D] on the CPU: element * 2^(scale byte - 127)."""
+    _mx_format(fmt)
+    codes, scales = codes.detach().cpu().contiguous(), scales.detach().cpu()
+    if fmt == MX_E4M3:
+        el = codes.view(torch.float8_e4m3fn).float().double()
+    else:
+        nib = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(codes.shape[:-1] + (2 * codes.shape[-1],)).long()
+        el = torch.tensor(E2M1_VALUES, dtype=torch.float64)[nib & 7] * (1.0 - 2.0 * (nib >> 3).double())
+    D = el.shape[-1]
+    if tuple(scales.shape) != tuple(el.shape[:-1]) + (D // 32,) or scales.dtype != torch.uint8:
+        raise ValueError(f"mx_dequantize_host: uint8 scale bytes {list(el.shape[:-1]) + [D // 32]}, got {tuple(scales.shape)} {scales.dtype}")
+    two = torch.pow(torch.tensor(2.0, dtype=torch.float64), scales.double() - 127.0)
+    return (el.reshape(el.shape[:-1] + (D // 32, 32)) * two[..., None]).reshape(el.shape)
+
+
+def mx_scores_host(codesA, scaleA, codesB, scaleB, maskA, maskB, wA, wB):
+    """What valor_fine_fused_fwd_mx computes, in fp64 on the CPU: compute_fine_matrix_slice (pretrain.py:191-211) on the dequantised
+    rows. codesA uint8 [NA, T, D] (MX e4m3), scaleA uint8 [NA, T, D / 32], codesB uint8 [NB, Nv, D / 2] (MX e2m1), scaleB uint8 [NB, Nv,
+    D / 32], masks and SOFTMAXED token weights [NA, T] / [NB, Nv]. [NA, NB] fp64."""
+    f64 = lambda t: t.detach().cpu().double()
+    sim = torch.einsum("atd,bvd->abtv", mx_dequantize_host(codesA, scaleA, MX_E4M3), mx_dequantize_host(codesB, scaleB, MX_E2M1))
+    x = sim * f64(maskA)[:, None, :, None] * f64(maskB)[None, :, None, :]
+    return (torch.einsum("abt,at->ab", x.max(dim=3)[0], f64(wA)) + torch.einsum("abv,bv->ab", x.max(dim=2)[0], f64(wB))) / 2.0
+
+
+def mx_quantize_rows(x, fmt):
+    """valor_mx_quantize_rows on device bf16 / fp32 rows x [..., D] (D % 32 == 0; a 2-D x may be a column slice of a wider matrix):
+    (uint8 codes [..., D] (MX_E4M3) or [..., D / 2] (MX_E2M1), dense; uint8 scale bytes [..., D / 32]). A non-finite value raises
+    ValueError, as quantize_rows does."""
+    _mx_format(fmt)
+    K._check_gpu(x)
+    if x.dtype not in (torch.bfloat16, torch.float32) or x.dim() < 1 or x.shape[-1] % 32 or x.shape[-1] == 0:
+        raise ValueError(f"mx_quantize_rows: bf16 or fp32 rows of a multiple of 32 elements, got {tuple(x.shape)} {x.dtype}")
+    cols = x.shape[-1]
+    strided = x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= cols and (x.stride(0) * x.element_size()) % 16 == 0 and x.data_ptr() % 16 == 0
+    if not strided:
+        x = x.contiguous()
+    if not bool(torch.isfinite(x).all()):
+        raise ValueError("mx_quantize_rows: the rows hold a non-finite value")
+    rows = x.numel() // cols
+    codes = torch.empty(x.shape[:-1] + (cols if fmt == MX_E4M3 else cols // 2,), dtype=torch.uint8, device=x.device)
+    scales = torch.empty(x.shape[:-1] + (cols // 32,), dtype=torch.uint8, device=x.device)
+    lib.call("valor_mx_quantize_rows", K._stream(), 0 if x.dtype == torch.bfloat16 else 1, x.data_ptr(), x.stride(0) if strided else cols, rows,
+             cols, fmt, codes.data_ptr(), scales.data_ptr())
+    return codes, scales
+
+
+def _scores_mx(qc, qs, bc, bs, maskA, maskB, wA, wB, out):
+    """out [NA, nb] (dense fp32) = valor_fine_fused_fwd_mx on contiguous codes / scale bytes, the A rows in pieces under the kernel's byte limit"""
+    NA, T, D = qc.shape
+    nb, Nv = bc.shape[:2]
+    st = K._stream()
+    ra = max(1, min(NA, (E._FUSED_BYTES - 1) // (T * D)))
+    for a0 in range(0, NA, ra):
+        na = min(ra, NA - a0)
+        lib.call("valor_fine_fused_fwd_mx", st, qc[a0:a0 + na].data_ptr(), qs[a0:a0 + na].data_ptr(), bc.data_ptr(), bs.data_ptr(),
+                 maskA[a0:a0 + na].data_ptr(), maskB.data_ptr(), wA[a0:a0 + na].data_ptr(), wB.data_ptr(), out[a0:a0 + na].data_ptr(), na, nb, T, Nv, D)
+    return out
+
+
 # ------------------------------------------------------------------ pair scores: the law on the host (checks only) and the wrapper
 EXACT_MODES = (None, "device", "host")
 MAX_SHORTLIST = 256                   # valor_topk_rows selects at most 256 per row
 # the default shortlist of a two-stage search is min(MAX_SHORTLIST, SHORTLIST_FACTOR * k). The 4 began as a starting point nobody had
 # measured; DESIGN.md section 3.4 (profiles/search_rescore_bench.json) holds the measurement and says whether it moved.
 SHORTLIST_FACTOR = 4
+# an mxfp4 walk is coarser: on the bench geometry 4 k returned 0.984 - 1.0 of the exact top 10, 8 k all of it, at under 0.2 % more time at
+# 10^6 clips and 64 queries (DESIGN.md section 3.4, profiles/search_mx_bench.json)
+SHORTLIST_FACTOR_MX = 8
 
 
 def pair_scores_host(featA, maskA, wA, store, wstore, cand):
@@ -475,7 +591,9 @@ class RetrievalIndex:
     bank_dtype "fp8" (fine banks): the parts are stored as e4m3 codes and row scales. `feats` are then bf16 / fp32 device features,
     quantised here, or -- with `scales` (one fp32 [clips, tokens] tensor per part) and `dtype` (the feature dtype the codes were made
     from) -- the uint8 codes themselves, on any device.
-    exact "device" / "host" (fp8 banks of bf16 features): the features the codes were made from are kept as well, on the bank's device
+    bank_dtype "mxfp4" (fine banks): the parts are stored as MX e2m1 codes [clips, tokens, D / 2] and E8M0 block scale bytes; given as
+    codes, `scales` are the uint8 [clips, tokens, D / 32] scale bytes. Everything an fp8 bank has, it has.
+    exact "device" / "host" (fp8 and mxfp4 banks of bf16 features): the features the codes were made from are kept as well, on the bank's device
     or in pinned host memory (the device then holds only the codes); search() re-scores its shortlist on them. With codes given,
     `exact_feats` are those features, one bf16 [clips, tokens, D] tensor per part."""
 
@@ -489,9 +607,11 @@ class RetrievalIndex:
             raise ValueError(f"bank_dtype {bank_dtype!r}: one of {BANK_DTYPES}")
         if bank_dtype == "fp8" and contra_type != "fine":
             raise ValueError("bank_dtype='fp8': only fine banks are covered (a coarse bank needs an fp8 GEMM)")
+        if bank_dtype == "mxfp4" and contra_type != "fine":
+            raise ValueError("bank_dtype='mxfp4': only fine banks are covered (a coarse bank needs a block-scaled GEMM)")
         if exact not in EXACT_MODES:
             raise ValueError(f"exact {exact!r}: one of {EXACT_MODES}")
-        if exact is not None and bank_dtype != "fp8":
+        if exact is not None and bank_dtype not in _QUANTISED:
             raise ValueError("exact=: only an fp8 bank keeps a second, exact store (a bf16 bank is its own: rescore() reads it directly)")
         self.group, self.contra_type, self.late_fusion, self.bank_dtype = group, contra_type, bool(late_fusion), bank_dtype
         self.exact = exact
@@ -526,6 +646,32 @@ class RetrievalIndex:
                     raise ValueError("exact=: the store holds the bf16 features the codes were made from, one [clips, tokens, D] tensor per "
                                      "part (valor_fine_score_pairs scores bf16 only)")
                 # "device": a copy of its own (the caller's tensor is not aliased, as the codes are not); "host": pinned, growing
+                self._exact = [_Bank(e, pin=True) if exact == "host" else _Bank(e.to(feats[0].device).clone()) for e in exact_feats]
+            self._scales = [_Bank(s) for s in scales]
+        if bank_dtype == "mxfp4":
+            # given as features: [clips, tokens, D] bf16 / fp32, quantised here; given as codes (`scales`): uint8 [clips, tokens, D / 2]
+            # with uint8 scale bytes [clips, tokens, D / 32]. D is the feature dimension either way.
+            given = scales is not None
+            for f in feats:
+                D = f.shape[-1] * (2 if given else 1)
+                if D % 128 or D == 0 or f.shape[1] > 64 or f.shape[1] < 1:
+                    raise ValueError(f"bank_dtype='mxfp4': D % 128 == 0 and 1 .. 64 tokens per clip (valor_fine_fused_fwd_mx has no GEMM "
+                                     f"fallback), got {tuple(f.shape[:2]) + (D,)}")
+            if not given:
+                self._dtype = feats[0].dtype
+                exact_feats = feats if exact is not None else None
+                feats, scales = zip(*[mx_quantize_rows(f, MX_E2M1) for f in feats])
+            else:
+                if (feats[0].dtype != torch.uint8 or dtype not in (torch.bfloat16, torch.float32) or len(scales) != nparts
+                        or any(tuple(s.shape) != tuple(f.shape[:2]) + (f.shape[2] // 16,) or s.dtype != torch.uint8 for f, s in zip(feats, scales))):
+                    raise ValueError("an mxfp4 bank given as codes: uint8 [clips, tokens, D / 2], uint8 scale bytes [clips, tokens, D / 32], "
+                                     "dtype bf16 / fp32")
+                self._dtype = dtype
+            if exact is not None:
+                if (self._dtype != torch.bfloat16 or exact_feats is None or len(exact_feats) != nparts
+                        or any(e.dtype != torch.bfloat16 or tuple(e.shape) != tuple(f.shape[:2]) + (2 * f.shape[2],) for e, f in zip(exact_feats, feats))):
+                    raise ValueError("exact=: the store holds the bf16 features the codes were made from, one [clips, tokens, D] tensor per "
+                                     "part (valor_fine_score_pairs scores bf16 only)")
                 self._exact = [_Bank(e, pin=True) if exact == "host" else _Bank(e.to(feats[0].device).clone()) for e in exact_feats]
             self._scales = [_Bank(s) for s in scales]
         self._feats = [_Bank(f) for f in feats]
@@ -567,7 +713,12 @@ class RetrievalIndex:
     @property
     def dtype(self):
         """the feature dtype the index was built from (an fp8 bank: what its codes were quantised from, and what queries may be)"""
-        return self._dtype if self.bank_dtype == "fp8" else self._feats[0].data.dtype
+        return self._dtype if self.bank_dtype in _QUANTISED else self._feats[0].data.dtype
+
+    @property
+    def dim(self):
+        """the feature dimension D (an mxfp4 bank's code rows hold D / 2 bytes)"""
+        return int(self._feats[0].data.shape[-1]) * (2 if self.bank_dtype == "mxfp4" else 1)
 
     @property
     def feats(self):
@@ -579,7 +730,8 @@ class RetrievalIndex:
 
     @property
     def scales(self):
-        """an fp8 bank's fp32 row scales [NB, Nv] per part (`feats` are then the uint8 codes); None otherwise"""
+        """an fp8 bank's fp32 row scales [NB, Nv] per part, an mxfp4 bank's uint8 E8M0 block scale bytes [NB, Nv, D / 32] (`feats` are
+        then the uint8 codes); None otherwise"""
         return None if self._scales is None else [b.view() for b in self._scales]
 
     @property
@@ -600,10 +752,12 @@ class RetrievalIndex:
         return self.contra_type == "fine" and len(self._feats) == 2
 
     def fingerprint(self):
-        fp = {"group": self.group, "contra_type": self.contra_type, "late_fusion": self.late_fusion, "D": int(self._feats[0].data.shape[-1]),
+        fp = {"group": self.group, "contra_type": self.contra_type, "late_fusion": self.late_fusion, "D": self.dim,
               "tokens": [int(b.data.shape[1]) if self.contra_type == "fine" else 1 for b in self._feats], "dtype": str(self.dtype)}
         if self.bank_dtype == "fp8":
             fp["bank_dtype"] = "fp8_e4m3"
+        if self.bank_dtype == "mxfp4":
+            fp["bank_dtype"] = "mxfp4_e2m1"
         if self.exact is not None:
             fp["exact"] = self.exact
         return fp
@@ -629,6 +783,8 @@ class RetrievalIndex:
             token_layout = [token_layout]                                # one part given as the list itself
         if bank_dtype == "fp8" and contra_type != "fine":
             raise ValueError("bank_dtype='fp8': only fine banks are covered (a coarse bank needs an fp8 GEMM)")
+        if bank_dtype == "mxfp4" and contra_type != "fine":
+            raise ValueError("bank_dtype='mxfp4': only fine banks are covered (a coarse bank needs a block-scaled GEMM)")
         if group not in GROUPS:
             raise ValueError(f"group {group!r}: one of {GROUPS} (the va / vta / atv directions are not searchable)")
         feats = list(feats) if isinstance(feats, (list, tuple)) else [feats]
@@ -644,13 +800,15 @@ class RetrievalIndex:
         ids = list(range(feats[0].shape[0])) if ids is None else list(ids)
         return cls(group, contra_type, late_fusion, feats, ws, ids, bank_dtype, exact=exact, token_layout=token_layout)
 
-    def quantize(self, exact=None):
-        """A new fp8 index over this fine bf16 / fp32 bank, quantised on the device; this index is untouched. exact "device" / "host":
-        the new index keeps a copy of the bf16 features beside the codes."""
+    def quantize(self, exact=None, bank_dtype="fp8"):
+        """A new fp8 (or, bank_dtype="mxfp4", MXFP4) index over this fine bf16 / fp32 bank, quantised on the device; this index is
+        untouched. exact "device" / "host": the new index keeps a copy of the bf16 features beside the codes."""
         if self.bank_dtype is not None:
             raise ValueError("the bank is quantised already")
+        if bank_dtype not in _QUANTISED:
+            raise ValueError(f"quantize: bank_dtype {bank_dtype!r}: one of {_QUANTISED}")
         return RetrievalIndex(self.group, self.contra_type, self.late_fusion, self.feats, [None if w is None else w.clone() for w in self.weights],
-                              self.ids, "fp8", exact=exact, token_layout=self.token_layout)
+                              self.ids, bank_dtype, exact=exact, token_layout=self.token_layout)
 
     @staticmethod
     def encode_gallery(model, batch, group):
@@ -686,7 +844,7 @@ class RetrievalIndex:
     @torch.no_grad()
     def build(cls, model, loader, group, bank_dtype=None, exact=None):
         """Encode every batch of `loader` (valor_collate batches with 'ids') once and keep the bank on the model's device
-        (bank_dtype "fp8": as e4m3 codes, each batch quantised as it arrives; exact: the bf16 rows are kept too)."""
+        (bank_dtype "fp8" / "mxfp4": as e4m3 / MX e2m1 codes, each batch quantised as it arrives; exact: the bf16 rows are kept too)."""
         index = None
         model.eval()
         for batch in loader:
@@ -736,6 +894,19 @@ class RetrievalIndex:
                     bank.append(f)
             for bank, s in zip(self._scales, scales):
                 bank.append(s)
+        if self.bank_dtype == "mxfp4":
+            for bank, f in zip(self._feats, feats):
+                if tuple(f.shape[1:]) != (int(bank.data.shape[1]), self.dim):
+                    raise ValueError(f"bank rows {tuple(f.shape[1:])} against {(int(bank.data.shape[1]), self.dim)}")
+                if self._exact is not None and f.dtype != torch.bfloat16:
+                    raise ValueError("an index with an exact store takes bf16 rows")
+            rows = feats
+            feats, scales = zip(*[mx_quantize_rows(f, MX_E2M1) for f in feats])
+            if self._exact is not None:                                  # after the quantiser: it refuses non-finite rows
+                for bank, f in zip(self._exact, rows):
+                    bank.append(f)
+            for bank, s in zip(self._scales, scales):
+                bank.append(s)
         for bank, f in zip(self._feats, feats):
             bank.append(f)
         for bank, w in zip(self._weights, weights):
@@ -745,14 +916,16 @@ class RetrievalIndex:
 
     # ------------------------------------------------------------------ persistence
     def save(self, path):
-        """Formats 1 (features), 2 (fp8 codes) and 3 (codes and the exact store). The token layout of a fused 'tva' bank (the one that
+        """Formats 1 (features), 2 (fp8 codes), 3 (fp8 codes and the exact store), 4 (mxfp4 codes) and 5 (mxfp4 codes and the exact
+        store). The token layout of a fused 'tva' bank (the one that
         cannot be inferred) travels as the extra key "token_layout", outside the fingerprint; files without the key are what they were."""
-        if self.bank_dtype == "fp8":
-            blob = {"format": "valor_amd.RetrievalIndex/2", "fingerprint": self.fingerprint(), "ids": self.ids,
+        if self.bank_dtype in _QUANTISED:
+            mx = self.bank_dtype == "mxfp4"
+            blob = {"format": "valor_amd.RetrievalIndex/4" if mx else "valor_amd.RetrievalIndex/2", "fingerprint": self.fingerprint(), "ids": self.ids,
                     "codes": [f.cpu().clone() for f in self.feats], "scales": [s.cpu().clone() for s in self.scales],
                     "weights": [w.cpu().clone() for w in self.weights]}
-            if self.exact is not None:                                   # format 3 = format 2 + the exact store
-                blob["format"] = "valor_amd.RetrievalIndex/3"
+            if self.exact is not None:                                   # format 3 = format 2 + the exact store, format 5 = format 4 + it
+                blob["format"] = "valor_amd.RetrievalIndex/5" if mx else "valor_amd.RetrievalIndex/3"
                 blob["exact_feats"] = [e.cpu().clone() for e in self.exact_feats]
         else:
             blob = {"format": "valor_amd.RetrievalIndex/1", "fingerprint": self.fingerprint(), "ids": self.ids,
@@ -764,15 +937,14 @@ class RetrievalIndex:
     @classmethod
     def load(cls, path, device):
         blob = torch.load(path, map_location="cpu", weights_only=True)      # tensors, strings, numbers, lists and dicts only
-        if not isinstance(blob, dict) or blob.get("format") not in ("valor_amd.RetrievalIndex/1", "valor_amd.RetrievalIndex/2",
-                                                                         "valor_amd.RetrievalIndex/3"):
+        if not isinstance(blob, dict) or blob.get("format") not in tuple(f"valor_amd.RetrievalIndex/{n}" for n in (1, 2, 3, 4, 5)):
             raise ValueError(f"{path}: not a RetrievalIndex file")
         fp = blob["fingerprint"]
-        if blob["format"].endswith(("/2", "/3")):
-            third = blob["format"].endswith("/3")
+        if blob["format"].endswith(("/2", "/3", "/4", "/5")):
+            third = blob["format"].endswith(("/3", "/5"))                 # with the exact store
             feature_dtype = {str(t): t for t in (torch.bfloat16, torch.float32)}.get(fp.get("dtype"))
             index = cls(fp["group"], fp["contra_type"], fp["late_fusion"], [c.to(device) for c in blob["codes"]],
-                        [w.to(device) for w in blob["weights"]], blob["ids"], "fp8", scales=[s.to(device) for s in blob["scales"]], dtype=feature_dtype,
+                        [w.to(device) for w in blob["weights"]], blob["ids"], "mxfp4" if blob["format"].endswith(("/4", "/5")) else "fp8", scales=[s.to(device) for s in blob["scales"]], dtype=feature_dtype,
                         exact=fp.get("exact") if third else None, exact_feats=blob["exact_feats"] if third else None,
                         token_layout=blob.get("token_layout"))
         else:
@@ -808,9 +980,9 @@ class RetrievalIndex:
         ft = q["feat_t"]
         if not ft.is_cuda or not self.device.type == "cuda":
             raise lib.ValorHipError("RetrievalIndex.search needs the bank and the queries on the GPU (no CPU fallback)")
-        dtype_ok = ft.dtype in (torch.bfloat16, torch.float32) if self.bank_dtype == "fp8" else ft.dtype == self.dtype
-        if ft.shape[-1] != self._feats[0].data.shape[-1] or not dtype_ok or ft.dim() != (3 if self.contra_type == "fine" else 2):
-            raise ValueError(f"query features {tuple(ft.shape)} {ft.dtype} against a {self.contra_type} bank of D={self._feats[0].data.shape[-1]}, {self.dtype}")
+        dtype_ok = ft.dtype in (torch.bfloat16, torch.float32) if self.bank_dtype in _QUANTISED else ft.dtype == self.dtype
+        if ft.shape[-1] != self.dim or not dtype_ok or ft.dim() != (3 if self.contra_type == "fine" else 2):
+            raise ValueError(f"query features {tuple(ft.shape)} {ft.dtype} against a {self.contra_type} bank of D={self.dim}, {self.dtype}")
         ft = ft.contiguous()
         if self.contra_type == "coarse":
             return ft, None, None
@@ -826,6 +998,8 @@ class RetrievalIndex:
         lib.call("valor_fine_weight_softmax", K._stream(), raw.data_ptr(), mask.data_ptr(), wq.data_ptr(), NQ, T)
         if self.bank_dtype == "fp8" and T > 64:
             raise ValueError("an fp8 bank scores queries of at most 64 tokens (valor_fine_fused_fwd_fp8)")
+        if self.bank_dtype == "mxfp4" and T > 64:
+            raise ValueError("an mxfp4 bank scores queries of at most 64 tokens (valor_fine_fused_fwd_mx)")
         return ft, mask, wq
 
     def _fused(self, ft, part):
@@ -855,6 +1029,9 @@ class RetrievalIndex:
         if self.bank_dtype == "fp8":                                     # ft = the queries' (codes, scales)
             _scores_fp8(ft[0], ft[1], fb, self._scales[part].data[c0:c0 + nb], mask, ones, wq, self._weights[part].data[c0:c0 + nb], out)
             return
+        if self.bank_dtype == "mxfp4":                                   # ft = the queries' (MX e4m3 codes, scale bytes)
+            _scores_mx(ft[0], ft[1], fb, self._scales[part].data[c0:c0 + nb], mask, ones, wq, self._weights[part].data[c0:c0 + nb], out)
+            return
         if self.contra_type == "coarse":
             K.gemm(ft, fb, out=out, out_dtype=torch.float32)
             return
@@ -875,6 +1052,8 @@ class RetrievalIndex:
                 for b in self._feats]
         if self.bank_dtype == "fp8":
             ft = quantize_rows(ft)                                       # the query rows, once per call
+        if self.bank_dtype == "mxfp4":
+            ft = mx_quantize_rows(ft, MX_E4M3)                           # the query rows, once per call, to MX e4m3
         for c0 in range(0, NB, chunk):
             nb = min(chunk, NB - c0)
             outs = [b[:NQ * nb].view(NQ, nb) for b in bufs]
@@ -889,9 +1068,9 @@ class RetrievalIndex:
         """the bf16 feature store per part that pair scores read, or ValueError with the reason (there is no fallback)"""
         if self.contra_type != "fine":
             raise ValueError("pair scores cover fine banks only (a coarse score is one GEMM row: use scores())")
-        if self.bank_dtype == "fp8":
+        if self.bank_dtype in _QUANTISED:
             if self._exact is None:
-                raise ValueError("this fp8 bank keeps no exact store (build it with exact='device' or exact='host'): its candidates cannot be "
+                raise ValueError(f"this {self.bank_dtype} bank keeps no exact store (build it with exact='device' or exact='host'): its candidates cannot be "
                                  "re-scored exactly")
             return self._exact
         if self.dtype != torch.bfloat16:
@@ -985,8 +1164,8 @@ class RetrievalIndex:
         return within_finish(top_val, top_pos, srt)
 
     def default_shortlist(self, k):
-        """candidates the fp8 walk of a two-stage search returns for re-scoring when the caller names no number"""
-        return min(MAX_SHORTLIST, SHORTLIST_FACTOR * int(k))
+        """candidates the fp8 (mxfp4) walk of a two-stage search returns for re-scoring when the caller names no number"""
+        return min(MAX_SHORTLIST, (SHORTLIST_FACTOR_MX if self.bank_dtype == "mxfp4" else SHORTLIST_FACTOR) * int(k))
 
     @torch.no_grad()
     def search(self, model, batch_or_tokens, k, chunk=None, *, within=None, shortlist=None, explain=False, sim=False):
@@ -997,7 +1176,7 @@ class RetrievalIndex:
         bank, by exact pair scores (rescore()'s coverage), in the same order; the bank is not walked.
         shortlist (an fp8 bank with an exact store): the fp8 walk returns `shortlist` candidates (k <= shortlist <= 256), they are
         re-scored on the exact features and the exact top k is returned with the exact scores. None = default_shortlist(k) = min(256,
-        4 k); 0 = fp8 scores only, which is all an index without a store does. With a "host" store the shortlist indices are read back,
+        4 k) (an mxfp4 bank: min(256, 8 k), and the walk is the mxfp4 walk throughout); 0 = fp8 scores only, which is all an index without a store does. With a "host" store the shortlist indices are read back,
         their rows gathered and copied: ONE host synchronisation per search; with a "device" store there is none.
         explain=True (every path; explain()'s coverage, checked before anything runs): the result carries `.alignment`, the Alignment
         of exactly the returned indices (empty slots: 255 / 0), with the token similarities when sim=True. Scores and indices are
@@ -1012,7 +1191,8 @@ class RetrievalIndex:
             if within is not None:
                 raise ValueError("within= scores its candidates exactly already: no shortlist")
             if self._exact is None:
-                raise ValueError("shortlist: a two-stage search needs an fp8 bank with an exact store (exact='device' or 'host')")
+                raise ValueError(f"shortlist: a two-stage search needs {'an mxfp4' if self.bank_dtype == 'mxfp4' else 'an fp8'} bank with an "
+                                 f"exact store (exact='device' or 'host')")
             if not k <= shortlist <= MAX_SHORTLIST:
                 raise ValueError(f"k <= shortlist <= {MAX_SHORTLIST} (valor_topk_rows), got k={k}, shortlist={shortlist}")
         if within is not None or explain:
