@@ -465,6 +465,32 @@ int valor_topk_workspace_bytes(int R, int C, int k, int64_t* bytes);
 int valor_topk_rows(void* stream, const float* score, int64_t ld, int R, int C, int64_t col_base, int k, int merge, float* top_val,
                     int64_t* top_idx, void* workspace, int64_t workspace_bytes);
 
+/* ---- retrieval search: the selection with a column filter and one result per group (csrc/search_select.hip; RetrievalIndex after
+ * remove(), and search(where=, collapse=)). A superset of valor_topk_rows: score, ld, R, C, col_base, k, merge, top_val, top_idx, the
+ * total order (value descending, then index ascending, a NaN below every number, -0 == +0), the -inf / -1 padding, the streaming
+ * contract and the independence of the result from how the work is split are that entry's. The index of a candidate is
+ * i = col_base + c for a column, top_idx[r, p] for an entry merged in; both additions are addressed by it.
+ *   keep   uint8 (a bool array as it is), or NULL: every candidate is eligible. The candidate i of row r is eligible iff
+ *          keep[r * keep_ld + i] != 0; keep_ld == 0: one array shared by all rows. With merge, the entries already in top_idx are
+ *          checked too: one that is no longer eligible drops out.
+ *   group  int32, 4-byte aligned, or NULL: no grouping. g = group[r * group_ld + i] (group_ld == 0: shared). The eligible candidates of
+ *          one id g >= 0 are ONE result, represented by the best of them under the total order (equal values: the lowest index); a
+ *          candidate with g < 0 is a group of its own. top_val / top_idx receive the k best representatives, best first: no group id
+ *          appears twice in a row. A later, better member (a later column, segment or merged chunk) replaces its group's
+ *          representative, a later, worse one vanishes; with fewer than k eligible groups the remaining slots hold -inf / -1.
+ *   Both arrays must cover every index the call meets: col_base + C entries, and with merge every index >= 0 in top_idx. The keep
+ *   byte and the group id are read only for candidates that beat the running threshold (the k-th best distinct representative;
+ *   none while fewer than k groups are known), so the pruning stays exact. With keep and group NULL the outputs equal
+ *   valor_topk_rows' bit for bit.
+ *   workspace: valor_topk_select_workspace_bytes(R, C, k) bytes, 16-byte aligned (the layout of valor_topk_workspace_bytes: the group of
+ *   a segment's key is read through `group` again by the merge). Two launches, as valor_topk_rows.
+ *   R == 0: no-op. VALOR_ERR_ARG before anything is launched on every ground valor_topk_rows names, a negative keep_ld or group_ld,
+ *   a misaligned group. */
+int valor_topk_select_workspace_bytes(int R, int C, int k, int64_t* bytes);
+int valor_topk_rows_select(void* stream, const float* score, int64_t ld, int R, int C, int64_t col_base, int k, int merge,
+                           const uint8_t* keep, int64_t keep_ld, const int32_t* group, int64_t group_ld, float* top_val, int64_t* top_idx,
+                           void* workspace, int64_t workspace_bytes);
+
 /* ---- retrieval search on an fp8 clip bank (csrc/search_fp8.hip; valor_amd/search.py RetrievalIndex with bank_dtype="fp8"). gfx950.
  * valor_fp8_quantize_rows: every row of x (dtype VALOR_DT_BF16 / VALOR_DT_F32, [rows, ld], ld >= cols, cols % 16 == 0, rows 16-byte
  *   aligned) becomes cols OCP e4m3fn codes (uint8 [rows, cols], dense, 16-byte aligned) and one fp32 scale. All in fp32,

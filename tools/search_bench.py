@@ -33,7 +33,17 @@ shapes, features and queries in one process, in alternating timed windows as abo
 bank: the median search ms with the spread, the bank bytes and read rate, the time over the fp8 bank of the same run, and the share of
 the bf16 bank's top-k clips that the code bank alone returns. With --rescore the mxfp4 bank also keeps a "device" store and the
 two-stage search is timed at shortlists of k, 4 k, 8 k and 256, with the share of the bf16 top k it returns (the exact answer wherever
-the shortlist holds it). Default --out profiles/search_mx_bench.json."""
+the shortlist holds it). Default --out profiles/search_mx_bench.json.
+
+--removed-frac F and / or --group-size G time the selection with removal, a filter and one result per group (valor_topk_rows_select) on
+the bf16 bank, beside the plain search of the same bank (valor_topk_rows: the walk an index that removed nothing runs, unchanged), the
+variants alternating inside each of `--rounds` rounds: "plain"; "removed" (a share F of the clips tombstoned at random); "where" (a
+filter admitting a share 1 - F, nothing removed); "collapse" (consecutive groups of G clips, one result per group); "removed+collapse".
+Per (NB, NQ, k) and variant: the median ms per search with the spread and the time over the plain search. The selection calls alone
+(valor_topk_rows / valor_topk_rows_select over the chunks of one walk, on a score buffer of the chunk's shape) are timed the same way.
+--parent FILE adds the plain search of another build to the document: FILE is what the default mode of this tool (no --bank-dtype, no
+--rescore) wrote when run from the parent commit's tree on the same machine; its search_ms and topk_ms are kept per (NB, NQ, k) under
+"parent_plain_search". Default --out profiles/search_select_bench.json."""
 import argparse
 import json
 import os
@@ -237,6 +247,89 @@ def compare_mx(a, dev):
             "cases": cases}
 
 
+def compare_select(a, dev):
+    """--removed-frac / --group-size"""
+    free = torch.cuda.mem_get_info()[0]
+    frac, gsize = a.removed_frac or 0.0, a.group_size or 0
+    cases = []
+    for NB in a.nb:
+        if NB * NV * (D * 2 + 4) * 1.2 > free:
+            print(f"NB={NB}: the bank does not fit", flush=True)
+            continue
+        g = torch.Generator(device=dev).manual_seed(1)
+        fb = unit_bf16(NB, NV, dev, 2)
+        wb_raw = torch.randn((NB, NV), generator=g, device=dev)
+        labels = [j // gsize for j in range(NB)] if gsize else None
+        make = lambda groups=None: S.RetrievalIndex.from_features(fb, wb_raw, group="tva", groups=groups)      # the banks alias fb
+        plain = make()
+        gone = torch.nonzero(torch.rand(NB, generator=g, device=dev) < frac).view(-1)
+        where = torch.rand(NB, generator=g, device=dev) >= frac
+        variants = {"plain": (plain, {})}
+        if frac:
+            removed = make()
+            removed.remove(indices=gone)
+            variants.update({"removed": (removed, {}), "where": (plain, {"where": where})})
+        if gsize:
+            grouped = make(labels)
+            variants["collapse"] = (grouped, {"collapse": True})
+            if frac:
+                both = make(labels)
+                both.remove(indices=gone)
+                variants["removed+collapse"] = (both, {"collapse": True})
+        for NQ in a.nq:
+            fa = unit_bf16(NQ, T, dev, 3)
+            wa_raw = torch.randn((NQ, T), generator=g, device=dev)
+            mask = (torch.arange(T, device=dev)[None] < torch.randint(8, T + 1, (NQ, 1), generator=g, device=dev)).float()
+            q = {"feat_t": fa, "mask": mask, "weight": wa_raw}
+            chunk = plain.default_chunk(NQ, T)
+            iters = max(3, min(a.iters, int(2e8 / (NB * NQ))))
+            bufs = [torch.randn((NQ, min(chunk, NB)), device=dev)]
+            for k in a.k:
+                state = (torch.full((NQ, k), float("-inf"), device=dev), torch.full((NQ, k), -1, dtype=torch.int64, device=dev))
+                ws = torch.empty((max(S.topk_select_workspace_bytes(NQ, b.shape[1], k) for b in bufs),), dtype=torch.uint8, device=dev)
+
+                def selection(index, kw):
+                    keep, group = index._selection(kw.get("where"), kw.get("collapse", False), NQ)
+                    for c0 in range(0, NB, chunk):
+                        b = bufs[0][:, :min(chunk, NB - c0)]
+                        if keep is None and group is None:
+                            S.topk_rows(b, k, col_base=c0, state=state, workspace=ws)
+                        else:
+                            S.topk_rows_select(b, k, col_base=c0, state=state, workspace=ws, keep=keep, group=group, check_state=False)   # as the index calls it
+
+                fns = {name: (lambda index=index, kw=kw: index.search(None, q, k, **kw)) for name, (index, kw) in variants.items()}
+                sel = {name: (lambda index=index, kw=kw: selection(index, kw)) for name, (index, kw) in variants.items()}
+                ms, sel_ms = {name: [] for name in fns}, {name: [] for name in fns}
+                for _ in range(a.rounds):
+                    for name in fns:
+                        ms[name].append(timed(fns[name], iters))
+                        sel_ms[name].append(timed(sel[name], iters))
+                med = lambda v: sorted(v)[len(v) // 2]
+                res = {"NB": NB, "NQ": NQ, "k": k, "chunk": chunk, "iters": iters, "rounds": a.rounds, "variants": {}}
+                for name in fns:
+                    res["variants"][name] = {"search_ms": round(med(ms[name]), 4), "search_ms_min_max": [round(min(ms[name]), 4), round(max(ms[name]), 4)],
+                                             "over_plain": round(med(ms[name]) / med(ms["plain"]), 3), "selection_ms": round(med(sel_ms[name]), 4),
+                                             "selection_over_plain": round(med(sel_ms[name]) / med(sel_ms["plain"]), 3),
+                                             "results": int((fns[name]().indices >= 0).sum()) // NQ}
+                print(json.dumps(res), flush=True)
+                cases.append(res)
+        variants.clear()
+        del plain, fb, wb_raw
+        torch.cuda.empty_cache()
+    parent = None
+    if a.parent:
+        with open(a.parent) as fh:
+            theirs = json.load(fh)
+        parent = {"what": "the default mode of tools/search_bench.py run from the parent commit's tree on the same machine (--parent): the plain "
+                          "search and its valor_topk_rows calls alone",
+                  "cases": [{key: c[key] for key in ("NB", "NQ", "k", "search_ms", "topk_ms")} for c in theirs["cases"]]}
+    return {"bench": "search_select", "parent_plain_search": parent, "geometry": {"T": T, "Nv": NV, "D": D, "feature_dtype": "bfloat16"}, "device": torch.cuda.get_device_name(0),
+            "removed_frac": frac, "group_size": gsize,
+            "timing": "device events over warmed calls; the median of `rounds` windows per variant, the variants alternating inside a round",
+            "plain": "an index that removed nothing, has no groups and gets no filter: valor_topk_rows, the walk of the parent commit",
+            "selection_ms": "the selection calls of one walk alone, on random scores of the chunk's shape", "cases": cases}
+
+
 def write(doc, out):
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as fh:
@@ -254,11 +347,19 @@ def main():
                     help="fp8 / both: the fp8 bank instead of / beside the bf16 bank; mxfp4 / all: the MXFP4 bank alone / beside the bf16 and the fp8 bank")
     ap.add_argument("--rounds", type=int, default=3, help="--bank-dtype fp8 / both: timed windows per bank")
     ap.add_argument("--rescore", action="store_true", help="the two-stage search on an fp8 bank with an exact store beside the bf16 and the fp8-only search")
+    ap.add_argument("--removed-frac", type=float, default=None, help="the selection with this share of the clips removed / filtered out, beside the plain search")
+    ap.add_argument("--parent", default=None, help="with --removed-frac / --group-size: the search_bench.json the parent commit's tool wrote on this machine")
+    ap.add_argument("--group-size", type=int, default=None, help="the selection with one result per group of this many consecutive clips, beside the plain search")
     ap.add_argument("--out", default=None, help="default profiles/search_bench.json (bf16), profiles/search_fp8_bench.json (fp8, both) or "
                                                 "profiles/search_rescore_bench.json (--rescore); profiles/search_mx_bench.json (mxfp4, all)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "search_bench.py measures on the GPU"
     dev = torch.device("cuda:0")
+    if a.removed_frac is not None or a.group_size is not None:
+        if not 0.0 <= (a.removed_frac or 0.0) < 1.0 or (a.group_size or 1) < 1 or a.bank_dtype != "bf16" or a.rescore:
+            ap.error("--removed-frac in [0, 1), --group-size >= 1, on the bf16 bank")
+        write(compare_select(a, dev), a.out or os.path.join(ROOT, "profiles", "search_select_bench.json"))
+        return
     if a.bank_dtype in ("mxfp4", "all"):
         write(compare_mx(a, dev), a.out or os.path.join(ROOT, "profiles", "search_mx_bench.json"))
         return

@@ -14,121 +14,13 @@
 //   topk_merge_kernel    one workgroup per row: the segments' keys and, with merge, the k entries already in top_val / top_idx go
 //                        through the same accumulator; the k best are written back as value / index (-inf / -1 for a missing one).
 //
-// The accumulator: TK_CAP = 512 keys in LDS (6 KB), a counter, and the running k-th best as a threshold in registers. A lane whose key
+// The accumulator (csrc/topk.h, shared with search_select.hip): TK_CAP = 512 keys in LDS (6 KB), a counter, and the running k-th best as a threshold in registers. A lane whose key
 // beats the threshold takes a slot (one LDS atomic per wave: ballot, leader add, prefix popcount). When the buffer is full the workgroup
 // sorts it (bitonic, best first), keeps the first k, and the k-th becomes the threshold; lanes that found no slot try again unless the
 // new threshold rules them out. Pruning against the k-th best of a subset is exact. After the first thousand columns few keys pass (k / n
 // of them at column n), and a step costs one barrier. The missing-candidate sentinel (0, INT64_MAX) loses to every real key, a NaN's
 // included, and is never written as an index: the host refuses col_base + C above INT64_MAX - 1.
-#include "common.h"
-#include <math.h>
-
-#define TK_THREADS 256
-#define TK_CAP 512
-#define TK_STEP 1024
-#define TK_NONE INT64_MAX
-
-DEVINL uint32_t tk_ord(float v) {
-    if (v != v) return 0u;
-    if (v == 0.f) return 0x80000000u;
-    const uint32_t b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-DEVINL float tk_val(uint32_t o) {
-    if (o == 0u) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
-}
-DEVINL bool tk_beats(uint32_t oa, int64_t ia, uint32_t ob, int64_t ib) { return oa > ob || (oa == ob && ia < ib); }
-
-struct TkState {
-    uint32_t* ord;      // LDS [TK_CAP]
-    int64_t* idx;       // LDS [TK_CAP]
-    int* cnt;           // LDS
-    uint32_t thr_o;     // the k-th best so far (uniform over the workgroup)
-    int64_t thr_i;
-    int k;
-};
-
-// best first; every thread of the workgroup; ends behind a barrier
-DEVINL void tk_sort(const TkState& s) {
-    const int tid = threadIdx.x;
-    for (int size = 2; size <= TK_CAP; size <<= 1) {
-        for (int j = size >> 1; j > 0; j >>= 1) {
-            const int lo = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), hi = lo | j;
-            const uint32_t oa = s.ord[lo], ob = s.ord[hi];
-            const int64_t ia = s.idx[lo], ib = s.idx[hi];
-            const bool fwd = (lo & size) == 0;
-            if (fwd ? tk_beats(ob, ib, oa, ia) : tk_beats(oa, ia, ob, ib)) {
-                s.ord[lo] = ob; s.idx[lo] = ib;
-                s.ord[hi] = oa; s.idx[hi] = ia;
-            }
-            __syncthreads();
-        }
-    }
-}
-
-DEVINL void tk_init(TkState& s, uint32_t* ord, int64_t* idx, int* cnt, int k) {
-    s.ord = ord; s.idx = idx; s.cnt = cnt; s.k = k;
-    s.thr_o = 0u; s.thr_i = TK_NONE;
-    if (threadIdx.x == 0) *cnt = 0;
-    __syncthreads();
-}
-
-// Every thread of the workgroup calls this together, each with its own key or want = false.
-DEVINL void tk_push(TkState& s, bool want, uint32_t o, int64_t i) {
-    const int lane = threadIdx.x & 63;
-    while (__syncthreads_or(want)) {
-        const uint64_t m = __ballot(want);
-        if (m) {
-            const int leader = __ffsll((unsigned long long)m) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(s.cnt, __popcll(m));
-            base = __shfl(base, leader, 64);
-            const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-            if (want && pos < TK_CAP) {
-                s.ord[pos] = o; s.idx[pos] = i;
-                want = false;
-            }
-        }
-        __syncthreads();
-        if (*s.cnt >= TK_CAP) {           // full (slots 0 .. TK_CAP - 1 are all written): keep the k best, raise the threshold
-            tk_sort(s);
-            s.thr_o = s.ord[s.k - 1];
-            s.thr_i = s.idx[s.k - 1];
-            if (threadIdx.x == 0) *s.cnt = s.k;
-            want = want && tk_beats(o, i, s.thr_o, s.thr_i);
-        }
-    }
-}
-
-// pad with the sentinel and sort: the k best are slots 0 .. k - 1 afterwards
-DEVINL void tk_finish(const TkState& s) {
-    const int n = *s.cnt;               // <= TK_CAP: tk_push leaves no full buffer behind
-    for (int p = threadIdx.x; p < TK_CAP; p += TK_THREADS)
-        if (p >= n) { s.ord[p] = 0u; s.idx[p] = TK_NONE; }
-    __syncthreads();
-    tk_sort(s);
-}
-
-template <bool VEC4> DEVINL void tk_load4(const float* row, int64_t j0, int C, float* v) {
-    const float nanv = __uint_as_float(0x7fc00000u);
-    if constexpr (VEC4) {
-        const int64_t j = j0 + 4 * (int)threadIdx.x;
-        if (j < C) {                    // ld % 4 == 0 and j % 4 == 0: j + 3 < ld, the load stays inside the row
-            const f32x4_t t = *(const f32x4_t*)(row + j);
-            v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-        } else {
-            v[0] = v[1] = v[2] = v[3] = nanv;
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t j = j0 + (int)threadIdx.x + TK_THREADS * e;
-            v[e] = (j < C) ? row[j] : nanv;
-        }
-    }
-}
-template <bool VEC4> DEVINL int64_t tk_col(int64_t j0, int e) { return VEC4 ? j0 + 4 * (int)threadIdx.x + e : j0 + (int)threadIdx.x + TK_THREADS * e; }
+#include "topk.h"
 
 template <bool VEC4>
 __global__ __launch_bounds__(TK_THREADS) void topk_segment_kernel(const float* __restrict__ score, int64_t ld, int C, int64_t col_base, int k,
@@ -141,7 +33,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_segment_kernel(const float* _
     const float* row = score + (int64_t)r * ld;
     const int64_t c0 = (int64_t)sg * seg;
     const int64_t c1 = (c0 + seg < C) ? c0 + seg : C;
-    TkState s;
+    TkState<false> s;
     tk_init(s, sh_ord, sh_idx, &sh_cnt, k);
     float cur[4], nxt[4] = {0.f, 0.f, 0.f, 0.f};
     tk_load4<VEC4>(row, c0, (int)c1, cur);
@@ -181,7 +73,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_merge_kernel(const uint32_t* 
     __shared__ uint32_t sh_ord[TK_CAP];
     __shared__ int sh_cnt;
     const int r = blockIdx.x;
-    TkState s;
+    TkState<false> s;
     tk_init(s, sh_ord, sh_idx, &sh_cnt, k);
     if (merge) {                        // k <= 256: one entry per thread
         const int p = threadIdx.x;
@@ -214,27 +106,6 @@ __global__ __launch_bounds__(TK_THREADS) void topk_merge_kernel(const uint32_t* 
 }
 
 // ---------------------------------------------------------------- host entries
-static inline int64_t tk_align16(int64_t n) { return (n + 15) / 16 * 16; }
-// segments of a row: at most one per 4096 columns (C = 4099: two segments of 3072), each a multiple of TK_STEP columns, and no more than fill
-// the machine a few times over (about 2048 workgroups in all)
-static void tk_plan(int R, int C, int* nseg, int* seg) {
-    const int64_t most = ((int64_t)C + 4095) / 4096, want = (2048 + (int64_t)R - 1) / R;
-    int64_t n = most < want ? most : want;
-    if (n < 1) n = 1;
-    int64_t sz = (((int64_t)C + n - 1) / n + TK_STEP - 1) / TK_STEP * TK_STEP;
-    if (sz < TK_STEP) sz = TK_STEP;
-    n = ((int64_t)C + sz - 1) / sz;
-    *nseg = (int)(n < 1 ? 1 : n);
-    *seg = (int)sz;
-}
-// workspace layout: [indices: R * nseg * k int64 | keys: R * nseg * k uint32], each part 16-byte aligned
-static int64_t tk_workspace(int R, int C, int k) {
-    int nseg, seg;
-    tk_plan(R, C, &nseg, &seg);
-    const int64_t n = (int64_t)R * nseg * k;
-    return tk_align16(n * 8) + tk_align16(n * 4);
-}
-
 extern "C" int valor_topk_workspace_bytes(int R, int C, int k, int64_t* bytes) {
     if (!bytes || R < 0 || C < 0 || k < 1 || k > 256) return VALOR_ERR_ARG;
     *bytes = R == 0 ? 0 : tk_workspace(R, C, k);

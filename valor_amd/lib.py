@@ -139,6 +139,8 @@ SIGNATURES = {
     "valor_retrieval_ranks": [_vp, _vp, _i64, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i],
     "valor_topk_workspace_bytes": [_i, _i, _i, _c.POINTER(_i64)],
     "valor_topk_rows": [_vp, _vp, _i64, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _i64],
+    "valor_topk_select_workspace_bytes": [_i, _i, _i, _c.POINTER(_i64)],
+    "valor_topk_rows_select": [_vp, _vp, _i64, _i, _i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64],
     "valor_fp8_quantize_rows": [_vp, _i, _vp, _i64, _i64, _i, _vp, _vp],
     "valor_fine_fused_fwd_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
     "valor_mx_quantize_rows": [_vp, _i, _vp, _i64, _i64, _i, _i, _vp, _vp],

@@ -44,8 +44,20 @@ returns them as an Alignment for given bank indices, search(..., explain=True) a
 scores and indices of the search are untouched. `token_layout` names the modality of every clip token, so the clip credits can be
 summed per modality (Alignment.clip_credit_by_modality) and the best clip token named (Alignment.best_clip_token).
 
+Removal, filters, groups (csrc/search_select.hip): valor_topk_rows_select is valor_topk_rows with a keep byte and a group id per
+candidate (topk_rows_select; the law restated by topk_select_host). Three things stand on it:
+  remove(ids= | indices=)               tombstones clips in a device bool array: no search path returns them again; positions keep
+                                        their meaning, compact() rewrites every store without them and returns the old -> new map,
+                                        update() is remove + add_features.
+  search(..., where=mask)               only the clips a device bool mask admits ([NB], or [NQ, NB] per query), ANDed with the alive array.
+  groups= / search(..., collapse=True)  one hashable label per clip (the video a segment was cut from); collapse returns one clip per
+                                        group, the group's best admitted one. A two-stage search filters in its first stage and
+                                        collapses in the second, on the exact scores.
+An index that removed nothing, has no groups and gets no where= runs valor_topk_rows, as it did.
+
 Out of scope: dual_softmax (it needs the whole matrix), the va / vta / atv directions, a bank sharded over GPUs,
-deletion, approximate search, a coarse first stage, kernel reads of host memory (the host store is gathered and copied), fp32 or
+attribute predicates evaluated on the device (the caller builds the mask), more than one result per group, a collapsing first stage,
+approximate search, a coarse first stage, kernel reads of host memory (the host store is gathered and copied), fp32 or
 coarse pair scores; for fp8 and mxfp4 banks also coarse banks (they need a GEMM of their own) and quantised codes anywhere in
 validate_ret or training; e2m1 queries and MX-e4m3 or fp6 banks (the kernel's format arguments would allow them); alignments on coarse
 banks or straight on codes, the clip -> text direction, word strings, span selection."""
@@ -120,6 +132,104 @@ def topk_rows(score, k, col_base=0, state=None, workspace=None):
 def topk_workspace_bytes(R, C, k):
     n = ctypes.c_int64()
     lib.call("valor_topk_workspace_bytes", int(R), int(C), int(k), ctypes.byref(n))
+    return n.value
+
+
+def topk_select_host(score, k, base=0, state=None, keep=None, group=None):
+    """What valor_topk_rows_select computes, restated with stable sorts: topk_host's candidates and order, and
+    keep  (bool / uint8 [N] for all rows or [R, N]; None: all): the candidate of index i is eligible iff keep[..., i] != 0 -- the
+          state's entries are checked like the columns';
+    group (integer [N] or [R, N]; None: no grouping): the eligible candidates of one id g >= 0 are one result, represented by the
+          first of them in sorted order; g < 0 is a group of its own. The k best representatives are returned.
+    With both None this is topk_host. Returns (val fp32 [R, k], idx int64 [R, k]) on the CPU."""
+    score = score.detach().float().cpu()
+    R, C = score.shape
+    val = score
+    idx = (torch.arange(C, dtype=torch.int64) + base)[None].expand(R, C)
+    valid = torch.ones((R, C), dtype=torch.bool)
+    if state is not None:
+        sv, si = state[0].detach().float().cpu(), state[1].detach().long().cpu()
+        val, idx, valid = torch.cat((sv, val), 1), torch.cat((si, idx), 1), torch.cat((si >= 0, valid), 1)
+    pad = max(0, k - val.shape[1])
+    if pad:
+        val = torch.cat((val, torch.zeros((R, pad))), 1)
+        idx = torch.cat((idx, torch.full((R, pad), -1, dtype=torch.int64)), 1)
+        valid = torch.cat((valid, torch.zeros((R, pad), dtype=torch.bool)), 1)
+    N = val.shape[1]
+    at = lambda table: (table[None].expand(R, -1) if table.dim() == 1 else table).gather(1, idx.clamp(min=0))
+    if keep is not None:
+        valid = valid & (at(keep.detach().cpu()) != 0)
+    gid = at(group.detach().cpu().long()) if group is not None else torch.full((R, N), -1, dtype=torch.int64)
+    nan = torch.isnan(val)
+    klass = torch.where(valid, nan.long(), torch.full_like(idx, 2))                 # numbers, then NaNs, then nothing
+    key = torch.where(nan | ~valid, torch.full_like(val, float("-inf")), val)
+    # least significant key first, every sort stable: index ascending, value descending, class ascending
+    order = torch.sort(idx, dim=1, stable=True)[1]
+    order = order.gather(1, torch.sort(key.gather(1, order), dim=1, descending=True, stable=True)[1])
+    order = order.gather(1, torch.sort(klass.gather(1, order), dim=1, stable=True)[1])
+    ok = valid.gather(1, order)
+    # one key per group: the id, or for a candidate on its own (and for nothing) a negative key no other position has. A stable sort
+    # by that key puts a group's members side by side in rank order: every member behind the first is a duplicate.
+    rank = torch.arange(N, dtype=torch.int64)[None].expand(R, N)
+    g = gid.gather(1, order)
+    gkey = torch.where(ok & (g >= 0), g, -1 - rank)
+    by_group = torch.sort(gkey, dim=1, stable=True)
+    later = torch.zeros((R, N), dtype=torch.bool)
+    later[:, 1:] = by_group[0][:, 1:] == by_group[0][:, :-1]
+    dup = torch.zeros((R, N), dtype=torch.bool).scatter(1, by_group[1], later)
+    first = torch.sort(dup.long(), dim=1, stable=True)[1][:, :k]                   # the representatives in rank order, then the rest
+    order, ok = order.gather(1, first), ok.gather(1, first) & ~dup.gather(1, first)
+    out_v = torch.where(ok, val.gather(1, order), torch.full((R, k), float("-inf")))
+    out_i = torch.where(ok, idx.gather(1, order), torch.full((R, k), -1, dtype=torch.int64))
+    return out_v, out_i
+
+
+def _select_table(name, t, dtypes, R, need, device):
+    """a keep / group array for valor_topk_rows_select: (tensor, leading dimension); [N] (ld 0) or [R, N], N >= need, unit stride"""
+    if (not torch.is_tensor(t) or t.dtype not in dtypes or t.device != device or t.dim() not in (1, 2) or t.shape[-1] < need
+            or (t.dim() == 2 and t.shape[0] != R) or (t.shape[-1] > 1 and t.stride(-1) != 1)):
+        raise ValueError(f"{name}: a {' / '.join(str(d) for d in dtypes)} tensor [N] or [{R}, N] on {device} with N >= {need} and unit stride")
+    return t, (0 if t.dim() == 1 else (t.stride(0) if R > 1 else max(t.stride(0), t.shape[1])))
+
+
+def topk_rows_select(score, k, col_base=0, state=None, workspace=None, keep=None, group=None, check_state=True):
+    """valor_topk_rows_select: topk_rows with keep (bool / uint8 [N] or [R, N], indexed by col_base + column) and group (int32, same
+    shapes); either may be None. THE TABLES ARE ADDRESSED BY INDEX, NOT BY COLUMN: they must cover col_base + C entries AND every index
+    the state holds, because the merge reads keep / group of the state's entries too -- tables cut to the current chunk are an
+    out-of-bounds read on the device. Both are checked here and raise ValueError; the state's largest index costs one read-back, which
+    check_state=False leaves out for a caller whose tables cover everything it folds (RetrievalIndex: they span the bank)."""
+    K._check_gpu(score)
+    if score.dtype != torch.float32 or score.dim() != 2 or score.stride(1) != 1:
+        raise ValueError("score: an fp32 [rows, columns] matrix with unit column stride")
+    R, C = score.shape
+    merge = state is not None
+    if merge:
+        top_val, top_idx = state
+        K._check_gpu(top_val, top_idx)
+        if (tuple(top_val.shape) != (R, k) or tuple(top_idx.shape) != (R, k) or top_val.dtype != torch.float32 or top_idx.dtype != torch.int64
+                or not top_val.is_contiguous() or not top_idx.is_contiguous()):
+            raise ValueError(f"state: contiguous fp32 / int64 [{R}, {k}] tensors")
+    else:
+        top_val = torch.empty((R, k), dtype=torch.float32, device=score.device)
+        top_idx = torch.empty((R, k), dtype=torch.int64, device=score.device)
+    keep, keep_ld = (None, 0) if keep is None else _select_table("keep", keep, (torch.bool, torch.uint8), R, int(col_base) + C, score.device)
+    group, group_ld = (None, 0) if group is None else _select_table("group", group, (torch.int32,), R, int(col_base) + C, score.device)
+    if merge and check_state and (keep is not None or group is not None) and k:
+        held, covered = int(top_idx.max()), min(t.shape[-1] for t in (keep, group) if t is not None)
+        if held >= covered:
+            raise ValueError(f"the state holds index {held}, the keep / group tables cover {covered} entries: size them for every index folded so far")
+    need = topk_select_workspace_bytes(R, C, k)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=score.device)
+    lib.call("valor_topk_rows_select", K._stream(), score.data_ptr(), score.stride(0) if R > 1 else max(score.stride(0), C), R, C, int(col_base),
+             int(k), int(merge), None if keep is None else keep.data_ptr(), keep_ld, None if group is None else group.data_ptr(), group_ld,
+             top_val.data_ptr(), top_idx.data_ptr(), workspace.data_ptr(), workspace.numel())
+    return top_val, top_idx
+
+
+def topk_select_workspace_bytes(R, C, k):
+    n = ctypes.c_int64()
+    lib.call("valor_topk_select_workspace_bytes", int(R), int(C), int(k), ctypes.byref(n))
     return n.value
 
 
@@ -526,17 +636,32 @@ def within_host(score, cand, k):
 class SearchResult:
     """scores fp32 [NQ, k] and indices int64 [NQ, k] on the device (-inf / -1 where the bank has fewer than k clips); `.ids` reads the
     indices back and maps them to the bank's clip ids (None for -1). `alignment`: the Alignment of exactly these indices after
-    search(..., explain=True), None otherwise. Iterating gives (ids, scores, indices)."""
+    search(..., explain=True), None otherwise. `groups`: the group id of every returned clip, int32 [NQ, k] on the device (-1: no
+    clip, or a clip without a group); `.group_labels` reads them back and maps them to the index's labels (None for -1). Iterating
+    gives (ids, scores, indices)."""
 
-    def __init__(self, scores, indices, bank_ids, alignment=None):
+    def __init__(self, scores, indices, bank_ids, alignment=None, groups=None, labels=()):
         self.scores, self.indices, self._bank_ids, self._ids = scores, indices, bank_ids, None
         self.alignment = alignment
+        self._groups, self._labels, self._group_labels = groups, labels, None
 
     @property
     def ids(self):
         if self._ids is None:
             self._ids = [[self._bank_ids[j] if j >= 0 else None for j in row] for row in self.indices.cpu().tolist()]
         return self._ids
+
+    @property
+    def groups(self):
+        if self._groups is None:                                         # an index without groups
+            self._groups = torch.full(self.indices.shape, -1, dtype=torch.int32, device=self.indices.device)
+        return self._groups
+
+    @property
+    def group_labels(self):
+        if self._group_labels is None:
+            self._group_labels = [[self._labels[g] if g >= 0 else None for g in row] for row in self.groups.cpu().tolist()]
+        return self._group_labels
 
     def __iter__(self):
         return iter((self.ids, self.scores, self.indices))
@@ -680,6 +805,131 @@ class RetrievalIndex:
         self.token_layout = self._token_layout(token_layout)
         # only a fused 'tva' bank's layout cannot be inferred from the group and the token counts: it alone is saved and handed on
         self._layout_saved = self.token_layout is not None and group == "tva" and nparts == 1
+        # the selection's bookkeeping: nothing until remove() / groups= ask for it, and an index without it calls valor_topk_rows
+        self._alive, self._removed = None, 0                             # device bool [capacity]: False = removed
+        self._groups, self.group_labels, self._label_id = None, [], {}   # device int32 [capacity] (-1: none); id -> label; label -> id
+        self._positions = None                                           # clip id -> positions, built by remove(ids=)
+
+    # ------------------------------------------------------------------ removal and groups
+    @property
+    def live(self):
+        """the number of clips not removed (len() stays the number of positions)"""
+        return len(self.ids) - self._removed
+
+    @property
+    def alive(self):
+        """device bool [NB]: False for a removed clip; None while nothing was removed"""
+        return None if self._alive is None else self._alive.view()
+
+    @property
+    def groups(self):
+        """device int32 [NB]: every clip's group id into group_labels, -1 for a clip of no group; None for an index without groups"""
+        return None if self._groups is None else self._groups.view()
+
+    def _append_groups(self, n, labels, before=None):
+        """the group column of n rows about to be appended to a bank of `before` rows (default: its present length): labels one
+        hashable per row (None: no group) or None altogether; the label table grows by the labels not seen before"""
+        if labels is None:
+            if self._groups is not None:
+                self._groups.append(torch.full((n,), -1, dtype=torch.int32, device=self.device))
+            return
+        labels = list(labels)
+        if len(labels) != n:
+            raise ValueError(f"groups: one label per row ({n}), got {len(labels)}")
+        gid = []
+        for lab in labels:
+            if lab is not None and lab not in self._label_id:
+                self._label_id[lab] = len(self.group_labels)
+                self.group_labels.append(lab)
+            gid.append(-1 if lab is None else self._label_id[lab])
+        rows = torch.tensor(gid, dtype=torch.int32).to(self.device)
+        if self._groups is None:                                         # the rows added before carried no label
+            before = len(self.ids) if before is None else before
+            self._groups = _Bank(torch.cat((torch.full((before,), -1, dtype=torch.int32, device=self.device), rows)))
+        else:
+            self._groups.append(rows)
+
+    def remove(self, ids=None, indices=None):
+        """Tombstone clips, named by clip id (every position holding the id) or by bank index: they are never returned by search() again,
+        on any path; an entry of a within= list that names one counts as -1. Positions keep their meaning (compact() reclaims the
+        rows), rescore() / explain() on explicit indices still read them. An id the bank does not hold raises KeyError, an index outside
+        it IndexError, before anything changes. Returns the number of clips newly removed (one read-back)."""
+        if (ids is None) == (indices is None):
+            raise ValueError("remove: ids= or indices=, one of them")
+        NB = len(self.ids)
+        if ids is not None:
+            if self._positions is None:
+                self._positions = {}
+                for j, cid in enumerate(self.ids):
+                    self._positions.setdefault(cid, []).append(j)
+            pos = []
+            for cid in ids:
+                if cid not in self._positions:
+                    raise KeyError(f"remove: the bank holds no clip of id {cid!r}")
+                pos += self._positions[cid]
+        else:
+            pos = [int(j) for j in (indices.tolist() if torch.is_tensor(indices) else indices)]
+            if any(j < 0 or j >= NB for j in pos):
+                raise IndexError(f"remove: bank indices lie in [0, {NB})")
+        if not pos:
+            return 0
+        if self._alive is None:
+            self._alive = _Bank(torch.ones((NB,), dtype=torch.bool, device=self.device))
+        pos = torch.unique(torch.tensor(pos, dtype=torch.int64)).to(self.device)
+        alive = self._alive.view()
+        newly = int(alive[pos].sum())
+        alive[pos] = False
+        self._removed += newly
+        return newly
+
+    def compact(self):
+        """Rewrite every store without the removed rows (features or codes, scales, weights, the exact store, ids, groups; the label
+        table keeps the labels that still have a clip, in the order of their first one). Afterwards the index is what from_features /
+        build on the surviving rows would have made. Returns the old -> new index map, int64 [old NB] on the device, -1 for a removed
+        row."""
+        NB = len(self.ids)
+        dev = self.device
+        if self._alive is None or not self._removed:
+            self._alive, self._removed = None, 0
+            return torch.arange(NB, dtype=torch.int64, device=dev)
+        stay = torch.nonzero(self._alive.view()).view(-1)
+        remap = torch.full((NB,), -1, dtype=torch.int64, device=dev)
+        remap[stay] = torch.arange(stay.numel(), dtype=torch.int64, device=dev)
+        stay_host = stay.cpu()
+        shrink = lambda bank: None if bank is None else _Bank(bank.view().index_select(0, stay_host if bank.pin else stay), pin=bank.pin)
+        self._feats = [shrink(b) for b in self._feats]
+        self._weights = [shrink(b) for b in self._weights]
+        if self._scales is not None:
+            self._scales = [shrink(b) for b in self._scales]
+        if self._exact is not None:
+            self._exact = [shrink(b) for b in self._exact]
+        self.ids = [self.ids[j] for j in stay_host.tolist()]
+        if self._groups is not None:
+            old, labels = self._groups.view().index_select(0, stay).cpu().tolist(), self.group_labels
+            self._groups, self.group_labels, self._label_id = None, [], {}
+            self._append_groups(len(old), [labels[g] if g >= 0 else None for g in old], before=0)
+        self._alive, self._removed, self._positions, self._stage = None, 0, None, {}
+        return remap
+
+    def update(self, ids, feats, weights, groups=None, token_layout=None):
+        """Replace clips: remove(ids=ids), then add_features(feats, weights, ids, ...). The new rows take new positions at the end; the
+        old ones stay tombstoned until compact(). If the new rows are refused (a non-finite row of a quantised bank, another token
+        count or layout, a wrong number of labels) the removal is undone and the error raised: the index is what it was. Returns the
+        number of clips removed."""
+        ids = list(ids)
+        had = self._alive is not None
+        before = self._alive.view().clone() if had else None
+        removed = self.remove(ids=ids)
+        try:
+            self.add_features(feats, weights, ids, token_layout=token_layout, groups=groups)
+        except Exception:
+            if had:
+                self._alive.view().copy_(before)
+            else:
+                self._alive = None
+            self._removed -= removed
+            raise
+        return removed
 
     def _token_layout(self, given):
         """per part a list of (modality, count) over the clip's token axis, or None (a coarse bank; a fused 'tva' bank nobody described).
@@ -771,14 +1021,16 @@ class RetrievalIndex:
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_features(cls, feats, weights=None, ids=None, *, group="tv", contra_type="fine", late_fusion=False, weights_softmaxed=False,
-                      bank_dtype=None, exact=None, token_layout=None):
+                      bank_dtype=None, exact=None, token_layout=None, groups=None):
         """An index over given tensors (device tensors; a CPU index can be saved and loaded but not searched). feats: [NB, Nv, D] (fine)
         or [NB, D] (coarse), or a (video, audio) pair for late_fusion 'tva'. weights (fine, one parts): the RAW token weights [NB, Nv],
         softmaxed here as validate_ret does; None = unit weights, which is what late_fusion always uses. weights_softmaxed: `weights`
         (one tensor per part) already are the softmaxed values. bank_dtype "fp8": the features are quantised on the device and dropped,
         unless exact "device" / "host" keeps them for the two-stage search. token_layout: per part a list of (modality, count) along the
         clip's token axis, e.g. [[("video", 8), ("audio", 2)]] for a fused 'tva' bank (one part: the list itself will do); 'tv', 'ta' and
-        late-fusion banks infer theirs, a fused 'tva' bank without one has None (Alignment's per-modality methods then refuse)."""
+        late-fusion banks infer theirs, a fused 'tva' bank without one has None (Alignment's per-modality methods then refuse).
+        groups: one hashable label per clip (None: no group), e.g. the video a segment was cut from: search(collapse=True) returns
+        one clip per label."""
         if token_layout and isinstance(token_layout[0], (list, tuple)) and token_layout[0] and isinstance(token_layout[0][0], str):
             token_layout = [token_layout]                                # one part given as the list itself
         if bank_dtype == "fp8" and contra_type != "fine":
@@ -798,7 +1050,9 @@ class RetrievalIndex:
                 raise ValueError("late_fusion scores use unit token weights: pass none")
             ws = [_softmax_ones_mask(torch.ones(f.shape[:2], dtype=torch.float32, device=f.device) if w is None else w) for f, w in zip(feats, raw)]
         ids = list(range(feats[0].shape[0])) if ids is None else list(ids)
-        return cls(group, contra_type, late_fusion, feats, ws, ids, bank_dtype, exact=exact, token_layout=token_layout)
+        index = cls(group, contra_type, late_fusion, feats, ws, ids, bank_dtype, exact=exact, token_layout=token_layout)
+        index._append_groups(len(ids), groups, before=0)
+        return index
 
     def quantize(self, exact=None, bank_dtype="fp8"):
         """A new fp8 (or, bank_dtype="mxfp4", MXFP4) index over this fine bf16 / fp32 bank, quantised on the device; this index is
@@ -807,8 +1061,10 @@ class RetrievalIndex:
             raise ValueError("the bank is quantised already")
         if bank_dtype not in _QUANTISED:
             raise ValueError(f"quantize: bank_dtype {bank_dtype!r}: one of {_QUANTISED}")
-        return RetrievalIndex(self.group, self.contra_type, self.late_fusion, self.feats, [None if w is None else w.clone() for w in self.weights],
-                              self.ids, bank_dtype, exact=exact, token_layout=self.token_layout)
+        index = RetrievalIndex(self.group, self.contra_type, self.late_fusion, self.feats, [None if w is None else w.clone() for w in self.weights],
+                               self.ids, bank_dtype, exact=exact, token_layout=self.token_layout)
+        index._copy_selection(self.alive, self.groups, self.group_labels)
+        return index
 
     @staticmethod
     def encode_gallery(model, batch, group):
@@ -842,9 +1098,12 @@ class RetrievalIndex:
 
     @classmethod
     @torch.no_grad()
-    def build(cls, model, loader, group, bank_dtype=None, exact=None):
+    def build(cls, model, loader, group, bank_dtype=None, exact=None, group_key=None):
         """Encode every batch of `loader` (valor_collate batches with 'ids') once and keep the bank on the model's device
-        (bank_dtype "fp8" / "mxfp4": as e4m3 / MX e2m1 codes, each batch quantised as it arrives; exact: the bf16 rows are kept too)."""
+        (bank_dtype "fp8" / "mxfp4": as e4m3 / MX e2m1 codes, each batch quantised as it arrives; exact: the bf16 rows are kept too).
+        group_key: the batch key that holds one group label per clip (e.g. the video a segment was cut from), or a callable
+        batch -> labels."""
+        labels = lambda batch: None if group_key is None else (group_key(batch) if callable(group_key) else batch[group_key])
         index = None
         model.eval()
         for batch in loader:
@@ -852,27 +1111,32 @@ class RetrievalIndex:
                 feats, ws, layout = cls._encode_gallery(model, batch, group)
                 index = cls(group, model.spec.contra_type, bool(model.spec.late_fusion), feats, ws, list(batch["ids"]), bank_dtype, exact=exact,
                             token_layout=layout)
+                index._append_groups(len(index), labels(batch), before=0)
             else:
-                index.add(model, batch)
+                index.add(model, batch, groups=labels(batch))
         if index is None:
             raise ValueError("RetrievalIndex.build: the loader is empty")
         return index
 
     @torch.no_grad()
-    def add(self, model, batch):
-        """Extend the bank in place by one gallery batch; earlier indices keep their meaning."""
+    def add(self, model, batch, groups=None):
+        """Extend the bank in place by one gallery batch; earlier indices keep their meaning. groups: one label per clip, or None."""
         self._check_model(model)
         model.eval()
         feats, ws, layout = self._encode_gallery(model, batch, self.group)
-        self.add_features(feats, ws, batch["ids"], token_layout=layout)
+        self.add_features(feats, ws, batch["ids"], token_layout=layout, groups=groups)
 
-    def add_features(self, feats, weights, ids, token_layout=None):
+    def add_features(self, feats, weights, ids, token_layout=None, groups=None):
         """add() on encoded rows: one tensor per part, weights already softmaxed (None for coarse). An fp8 bank takes bf16 / fp32
         features and quantises them first; a non-finite row raises ValueError before anything is appended. token_layout: the rows'
-        own layout, if the caller knows it; it must be the bank's (rows of another layout, or of another token count, are refused)."""
+        own layout, if the caller knows it; it must be the bank's (rows of another layout, or of another token count, are refused).
+        groups: one hashable label per row (None: no group); rows added without one belong to no group."""
         ids = list(ids)
         if len(feats) != len(self._feats) or any(f.shape[0] != len(ids) for f in feats):
             raise ValueError("one feature tensor per bank part, one row per id")
+        groups = None if groups is None else list(groups)
+        if groups is not None and len(groups) != len(ids):
+            raise ValueError(f"groups: one label per row ({len(ids)})")
         if self.contra_type == "fine":
             for bank, f in zip(self._feats, feats):
                 if f.dim() != 3 or f.shape[1] != bank.data.shape[1]:
@@ -912,13 +1176,21 @@ class RetrievalIndex:
         for bank, w in zip(self._weights, weights):
             if bank is not None:
                 bank.append(w)
+        self._append_groups(len(ids), groups)
+        if self._alive is not None:
+            self._alive.append(torch.ones((len(ids),), dtype=torch.bool, device=self.device))
+        if self._positions is not None:
+            for j, cid in enumerate(ids, len(self.ids)):
+                self._positions.setdefault(cid, []).append(j)
         self.ids += ids
 
     # ------------------------------------------------------------------ persistence
     def save(self, path):
         """Formats 1 (features), 2 (fp8 codes), 3 (fp8 codes and the exact store), 4 (mxfp4 codes) and 5 (mxfp4 codes and the exact
         store). The token layout of a fused 'tva' bank (the one that
-        cannot be inferred) travels as the extra key "token_layout", outside the fingerprint; files without the key are what they were."""
+        cannot be inferred) travels as the extra key "token_layout", outside the fingerprint; files without the key are what they were.
+        So do the selection's arrays: "alive" (bool [NB], only after a remove()), "groups" (int32 [NB]) and "group_labels" (only for an
+        index with groups; labels a weights-only load admits: strings, numbers, tuples of them)."""
         if self.bank_dtype in _QUANTISED:
             mx = self.bank_dtype == "mxfp4"
             blob = {"format": "valor_amd.RetrievalIndex/4" if mx else "valor_amd.RetrievalIndex/2", "fingerprint": self.fingerprint(), "ids": self.ids,
@@ -932,6 +1204,10 @@ class RetrievalIndex:
                     "feats": [f.cpu().clone() for f in self.feats], "weights": [None if w is None else w.cpu().clone() for w in self.weights]}
         if self._layout_saved:
             blob["token_layout"] = [[[m, n] for m, n in part] for part in self.token_layout]
+        if self._removed:
+            blob["alive"] = self.alive.cpu().clone()
+        if self._groups is not None:
+            blob["groups"], blob["group_labels"] = self.groups.cpu().clone(), list(self.group_labels)
         torch.save(blob, path)
 
     @classmethod
@@ -952,7 +1228,23 @@ class RetrievalIndex:
                         [None if w is None else w.to(device) for w in blob["weights"]], blob["ids"], token_layout=blob.get("token_layout"))
         if index.fingerprint() != fp:
             raise ValueError(f"{path}: the stored tensors do not match the stored fingerprint {fp}")
+        index._copy_selection(blob.get("alive"), blob.get("groups"), blob.get("group_labels"))
         return index
+
+    def _copy_selection(self, alive, groups, labels):
+        """take over another index's (or a file's) alive array, group ids and label table; None: the index has none"""
+        NB = len(self.ids)
+        if alive is not None:
+            if tuple(alive.shape) != (NB,) or alive.dtype != torch.bool:
+                raise ValueError(f"alive: a bool [{NB}] tensor")
+            self._alive = _Bank(alive.to(self.device).clone())
+            self._removed = NB - int(alive.sum())
+        if groups is not None:
+            labels = list(labels or ())
+            if tuple(groups.shape) != (NB,) or groups.dtype != torch.int32 or (NB and int(groups.max()) >= len(labels)):
+                raise ValueError(f"groups: an int32 [{NB}] tensor of ids into the {len(labels)} group_labels")
+            self._groups = _Bank(groups.to(self.device).clone())
+            self.group_labels, self._label_id = labels, {lab: g for g, lab in enumerate(labels)}
 
     # ------------------------------------------------------------------ queries
     @torch.no_grad()
@@ -1154,21 +1446,43 @@ class RetrievalIndex:
         ft, mask, wq = self._queries(model, batch_or_tokens)
         return self._pair_scores(ft, mask, wq, self._check_candidates(candidates, ft.shape[0]))
 
-    def _select_within(self, ft, mask, wq, cand, k):
-        """the k best of every row of candidates under the search's total order: (scores [NQ, k], bank indices [NQ, k])"""
+    def _select_within(self, ft, mask, wq, cand, k, keep=None, group=None):
+        """the k best of every row of candidates under the search's total order: (scores [NQ, k], bank indices [NQ, k]). keep (bool
+        [NB] or [NQ, NB]): a candidate it rules out counts as -1; group (int32 [NB]): one result per group. Both are gathered per
+        candidate position and go to valor_topk_rows_select; without them the selection is valor_topk_rows."""
         if cand.shape[1] == 0:                                           # an empty list: nothing to select from
             NQ = cand.shape[0]
             return (torch.full((NQ, k), float("-inf"), dtype=torch.float32, device=cand.device), torch.full((NQ, k), -1, dtype=torch.int64, device=cand.device))
         srt = within_prepare(cand, len(self))
-        top_val, top_pos = topk_rows(self._pair_scores(ft, mask, wq, srt), k)
+        if keep is None and group is None:
+            top_val, top_pos = topk_rows(self._pair_scores(ft, mask, wq, srt), k)
+            return within_finish(top_val, top_pos, srt)
+        at = lambda table: (table[None].expand(srt.shape[0], -1) if table.dim() == 1 else table).gather(1, srt.clamp(min=0))
+        if keep is not None:
+            srt = torch.where(at(keep), srt, torch.full_like(srt, -1))
+        group_pos = None if group is None else torch.where(srt >= 0, at(group), torch.full_like(srt, -1, dtype=torch.int32)).contiguous()
+        top_val, top_pos = topk_rows_select(self._pair_scores(ft, mask, wq, srt), k, keep=(srt >= 0).contiguous(), group=group_pos)
         return within_finish(top_val, top_pos, srt)
+
+    def _selection(self, where, collapse, NQ):
+        """(keep, group) of a search: keep = the alive array ANDed with `where` (bool [NB] or [NQ, NB] on the device), or None when both
+        are absent; group = the group ids when collapse. (None, None): the plain selection."""
+        NB = len(self)
+        keep = self.alive if self._removed else None
+        if where is not None:
+            if (not torch.is_tensor(where) or where.dtype != torch.bool or where.device != self.device
+                    or tuple(where.shape) not in ((NB,), (NQ, NB))):
+                raise ValueError(f"where: a bool [{NB}] or [{NQ}, {NB}] tensor on {self.device}")
+            keep = where.contiguous() if keep is None else where & keep
+        return keep, (self.groups if collapse else None)
 
     def default_shortlist(self, k):
         """candidates the fp8 (mxfp4) walk of a two-stage search returns for re-scoring when the caller names no number"""
         return min(MAX_SHORTLIST, (SHORTLIST_FACTOR_MX if self.bank_dtype == "mxfp4" else SHORTLIST_FACTOR) * int(k))
 
     @torch.no_grad()
-    def search(self, model, batch_or_tokens, k, chunk=None, *, within=None, shortlist=None, explain=False, sim=False):
+    def search(self, model, batch_or_tokens, k, chunk=None, *, within=None, shortlist=None, explain=False, sim=False, where=None,
+               collapse=False):
         """The k best clips of every query: SearchResult (ids: list of lists, on demand; scores, indices: device [NQ, k]), best first,
         equal scores in index order. model None: batch_or_tokens = {'feat_t', 'mask', 'weight'} holds encoded queries (feat_t [NQ, T, D]
         or [NQ, D]; the text mask and RAW token weights of a fine model, None = ones).
@@ -1180,10 +1494,21 @@ class RetrievalIndex:
         their rows gathered and copied: ONE host synchronisation per search; with a "device" store there is none.
         explain=True (every path; explain()'s coverage, checked before anything runs): the result carries `.alignment`, the Alignment
         of exactly the returned indices (empty slots: 255 / 0), with the token similarities when sim=True. Scores and indices are
-        those of the search without it, bit for bit: the alignment's own score is not substituted."""
+        those of the search without it, bit for bit: the alignment's own score is not substituted.
+        where (bool [NB] for all queries or [NQ, NB] per query, on the device): only clips it admits are returned, on every path (an
+        entry of a within= list it rules out counts as -1). Removed clips are ruled out the same way, always.
+        collapse=True (an index with groups): one result per group, the group's best admitted clip; clips of no group stand for
+        themselves. The result's `.groups` / `.group_labels` name the groups. In a two-stage search the first stage applies the filter
+        and does NOT collapse (its scores are approximate: it must not choose a group's representative), so the shortlist counts
+        clips, the second stage collapses the exact scores, and a result may hold fewer than k groups when few groups fill the
+        shortlist: a larger `shortlist` is the remedy.
+        With nothing removed, no where and no collapse the selection is valor_topk_rows, as it was; otherwise it is
+        valor_topk_rows_select (csrc/search_select.hip) with the shared arrays, chunk by chunk."""
         if not 1 <= int(k) <= 256:
             raise ValueError("1 <= k <= 256 (valor_topk_rows)")
         k = int(k)
+        if collapse and self._groups is None:
+            raise ValueError("collapse=True: the index has no groups (from_features / add_features / build take them)")
         if shortlist is None:
             shortlist = self.default_shortlist(k) if (self._exact is not None and within is None) else 0
         shortlist = int(shortlist)
@@ -1201,9 +1526,12 @@ class RetrievalIndex:
         NQ = ft.shape[0]
         if explain:
             self._pair_queries(ft)
-        attach = lambda val, idx: SearchResult(val, idx, self.ids, self._explain(ft, mask, wq, idx, bool(sim)) if explain else None)
+        keep, group = self._selection(where, bool(collapse), NQ)
+        gathered = lambda idx: None if self._groups is None else torch.where(idx >= 0, self.groups[idx.clamp(min=0)], torch.full_like(idx, -1, dtype=torch.int32))
+        attach = lambda val, idx: SearchResult(val, idx, self.ids, self._explain(ft, mask, wq, idx, bool(sim)) if explain else None,
+                                               gathered(idx), self.group_labels)
         if within is not None:
-            return attach(*self._select_within(ft, mask, wq, self._check_candidates(within, NQ), k))
+            return attach(*self._select_within(ft, mask, wq, self._check_candidates(within, NQ), k, keep, group))
         if shortlist:
             self._pair_queries(ft)
             k_out, k = k, shortlist
@@ -1211,12 +1539,16 @@ class RetrievalIndex:
         top_idx = torch.full((NQ, k), -1, dtype=torch.int64, device=ft.device)
         ws = None
         for c0, score in self._chunks(ft, mask, wq, chunk):
-            need = topk_workspace_bytes(NQ, score.shape[1], k)
+            need = topk_workspace_bytes(NQ, score.shape[1], k)                   # the select entry's workspace is the same
             if ws is None or ws.numel() < need:
                 ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=ft.device)
-            topk_rows(score, k, col_base=c0, state=(top_val, top_idx), workspace=ws)
+            if keep is None and (group is None or shortlist):
+                topk_rows(score, k, col_base=c0, state=(top_val, top_idx), workspace=ws)
+            else:                                                        # a first stage filters and leaves the collapsing to the second
+                topk_rows_select(score, k, col_base=c0, state=(top_val, top_idx), workspace=ws, keep=keep, group=None if shortlist else group,
+                                 check_state=False)                      # the tables span the bank
         if shortlist:                                                    # the second stage: exact scores of the fp8 walk's candidates
-            top_val, top_idx = self._select_within(ft, mask, wq, top_idx, k_out)
+            top_val, top_idx = self._select_within(ft, mask, wq, top_idx, k_out, keep, group)
         return attach(top_val, top_idx)
 
     @torch.no_grad()
