@@ -642,6 +642,28 @@ int valor_mask_tokens(void* stream, const int64_t* tokens, const int32_t* k, int
  * total). A row never writes past row_off[i + 1] (n for the last row). labels [b, T] int64, T <= 512, Ttot >= T; idx / lab_out [G*n]. */
 int valor_masked_rows(void* stream, const int64_t* labels, const int32_t* row_off, int b, int T, int G, int64_t Ttot, int64_t r0,
                       int64_t n, int64_t* idx, int64_t* lab_out);
+/* ---- video patch dropout (csrc/patchdrop.hip): every frame keeps k of its Pn patches (+ the class token) in training.
+ * valor_patch_keep draws the subsets. Frame f belongs to draw group g = f / group (group = 1: a subset per frame; group = the frames of
+ * a clip: one subset per clip, "tube"); N % group == 0. Patch p of group g has the key w0 | w1 << 32 of
+ * Philox4x32-10(seed, offset + *rng_base + g*Pn + p) (rng_base: null or ONE device counter read when the kernel runs, as in every dropout
+ * entry); the group keeps its k smallest keys, ties to the lower p. idx [N, k] int32: the kept positions of each frame, ascending;
+ * slot [N, Pn] int32: the slot of a kept position, -1 for a dropped one. 1 <= k <= Pn <= 1024. The call consumes (N / group) * Pn counters.
+ * No atomics: the outputs are a function of the arguments (and *rng_base) alone. */
+int valor_patch_keep(void* stream, int N, int Pn, int k, int group, uint64_t seed, uint64_t offset, const uint64_t* rng_base,
+                     int32_t* idx, int32_t* slot);
+/* valor_patchify for the kept patches only: out row f*k + j = patch idx[f, j] of image f (idx [N, k] int32 as valor_patch_keep leaves it;
+ * an entry outside 0 .. (H/P)*(W/P) - 1 is clamped). ld_out / pad columns as valor_patchify. */
+int valor_patchify_kept(void* stream, int dtype, const float* in, const int32_t* idx, void* out, int N, int C, int H, int W, int P,
+                        int k, int64_t ld_out);
+/* out [N, 1 + k, E]: out[f][0] = cls + pos[0]; out[f][1 + j] = patches[f*k + j] (+ bias) + pos[1 + idx[f, j]] -- the arithmetic of
+ * valor_assemble_tokens_fwd, so the result equals the gathered rows of its output bit for bit. pos [Pn + 1, E]. */
+int valor_assemble_tokens_kept_fwd(void* stream, int dtype, const void* patches, const void* cls, const void* pos, const void* bias,
+                                   const int32_t* idx, void* out, int N, int Pn, int k, int E);
+/* dout [N, 1 + k, E] -> dpatches [N*k, E] = its patch rows; dpos [Pn + 1, E]: row 0 = sum_f dout[f][0] (also to dcls [E] when not null),
+ * row 1 + p = sum over the frames with slot[f, p] >= 0 of dout[f][1 + slot[f, p]], in frame order (deterministic; exactly 0 where no
+ * frame kept p). accumulate: dpos / dcls += (gradient-arena slots). */
+int valor_assemble_tokens_kept_bwd(void* stream, int dtype, const void* dout, const int32_t* slot, void* dpatches, void* dpos, void* dcls,
+                                   int N, int Pn, int k, int E, int accumulate);
 /* The head of one decoding step against a K|V cache, per sequence r with its new token tok[r] at text position *t_dev (device scalar):
  * x[r, j] = BertEmbeddings before its LayerNorm (bert.py:190-218) of tok[r] at position t (j = 0) and of mask_id at t + 1 (j = 1, J = 2);
  * kmask[r, P + t] = tok[r] != 0 ? 0 : neg (bert.py:857,885); amask [R, J, L] = the step's additive attention rows (causal over the text,

@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-val
 HOT_KERNELS = ("beam_pool_step_kernel", "beam_group_step_kernel", "gemm_8ph_kernel", "gemm_8q_kernel", "gemm_8ph2_kernel", "gemm_glds_kernel", "gemm_splitk_reduce", "attn_res_", "attn_x_", "attn_xu_", "ln_fwd", "ln_bwd", "adamw_kernel", "xent_",
                "fine_fused_fwd", "fine_fused_fwd_fp8_kernel", "fine_ds_chunk_kernelIDF16bLi16", "win_fwd", "win_bwd_dkv", "topk_segment_kernel",
                "topk_merge_kernel", "topk_select_segment_kernel", "topk_select_merge_kernel", "fine_score_pairs_kernel", "fine_align_pairs_kernel", "grad_partial_kernel", "update_partial_kernel", "ema_kernel", "trie_constrain_kernel",
-               "trie_score_level_kernel")
+               "trie_score_level_kernel", "patch_keep_kernel", "patchify_kept_kernel", "assemble_kept_")
 # ... except the instantiations whose register demand is known and documented: the key-stationary cross-attention with six
 # eight query sub-tiles keeps 128 accumulator registers of O per wave; the backward's dropout variant of four sub-tiles (the six-sub-tile
 # backward is gone: attention_xu.hip owns that geometry).

@@ -174,6 +174,10 @@ SIGNATURES = {
     "valor_cast_from_f32": [_vp, _i, _vp, _vp, _i64],
     "valor_mask_tokens": [_vp, _vp, _vp, _i, _i, _u64, _u64, _i64, _i64, _i64, _vp, _vp],
     "valor_masked_rows": [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _vp, _vp],
+    "valor_patch_keep": [_vp, _i, _i, _i, _i, _u64, _u64, _vp, _vp, _vp],
+    "valor_patchify_kept": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64],
+    "valor_assemble_tokens_kept_fwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i],
+    "valor_assemble_tokens_kept_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i],
     "valor_dact_mul": [_vp, _i, _vp, _vp, _vp, _i64, _i],
     "valor_mean_f32": [_vp, _vp, _i64, _vp],
     "valor_xent_weighted_bwd": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _i64, _i, _i64],

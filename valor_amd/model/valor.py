@@ -97,6 +97,20 @@ def _opt(opts, name, default):
 MASKER_MODES = ("host", "device")
 
 
+def patch_keep_count(Pn, rate=0.0, keep=None):
+    """kept patches per frame of video patch dropout: `keep` (the exact count, 1 .. Pn) when given, else max(1, Pn - int(Pn * rate)) for
+    a rate in [0, 1). Pn = nothing is dropped."""
+    if keep is not None:
+        k = int(keep)
+        if not 1 <= k <= Pn:
+            raise ValueError(f"video_patch_keep {k}: 1 .. {Pn} patches per frame")
+        return k
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"video_patch_dropout {rate}: a rate in [0, 1)")
+    return max(1, Pn - int(Pn * rate))
+
+
 def token_masker_mode(opts):
     """the `token_masker` option: 'host' (TokenMasker, the reference's draw order: the parity mode and the default) or 'device'
     (DeviceTokenMasker); VALOR_MASKER, when set, overrides it."""
@@ -309,6 +323,11 @@ class VALOR(nn.Module):
             raise NotImplementedError("fineweight_type='none' is a TypeError in the reference too (pretrain.py:330)")
         self.spec = spec
         self.drop_path = float(_opt(opts, "drop_path_rate", spec.swin_drop_path))   # videoswin.py:393 (active in training)
+        # video patch dropout (FLIP / open_clip; 'tube' = VideoMAE's tube masking): in training every frame keeps k of its Pn patches +
+        # the class token, and the ViT, the cross K|V projections and the decoder's cross-attention run on 1 + k rows per frame
+        self.patch_keep, self.patch_dropout_mode = self._patch_dropout_options(opts, spec)
+        self.last_patch_keep = None       # (idx [b*F, k], slot [b*F, Pn]) of the latest video encoder call with patch dropout (device tensors)
+        self._pd_tables, self._pd_group, self._pd_ran = {}, 1, False
         self.dtype = dtype
         self.device = torch.device(device)
         self.use_task_prompt = bool(_opt(opts, "use_task_prompt", False))
@@ -354,6 +373,33 @@ class VALOR(nn.Module):
             if all(self._ref_is_frozen(r) for r in refs):
                 self.P[name].requires_grad_(False)
                 self.frozen_names.add(name)
+
+    def _patch_dropout_options(self, opts, spec):
+        """`video_patch_dropout` (rate in [0, 1)), `video_patch_keep` (the exact count, overrides the rate) and `video_patch_dropout_mode`
+        ('frame': a subset per frame, 'tube': one per clip) -> (k, mode); k = Pn means off. k = max(1, Pn - int(Pn * rate))."""
+        rate = float(_opt(opts, "video_patch_dropout", 0.0) or 0.0)
+        keep = _opt(opts, "video_patch_keep", None)
+        mode = _opt(opts, "video_patch_dropout_mode", "frame")
+        if mode not in ("frame", "tube"):
+            raise ValueError(f"video_patch_dropout_mode {mode!r}: 'frame' or 'tube'")
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"video_patch_dropout {rate}: a rate in [0, 1)")
+        if rate == 0.0 and keep is None:
+            return None, mode
+        if spec.video_encoder == "swin":
+            raise NotImplementedError("video patch dropout with the VideoSwin encoder: its windows need the full patch grid")
+        if self.scst_finetuning:
+            raise NotImplementedError("video patch dropout with scst_finetuning: the sampler and the loss pass would see different clips")
+        Pn = spec.vis_tokens - 1
+        k = patch_keep_count(Pn, rate, keep)
+        if k < Pn:
+            print(f"[valor_amd] video patch dropout: {k} of {Pn} patches per frame ({mode}), {1 + k} tokens", flush=True)
+        return (k if k < Pn else None), mode
+
+    def _patch_dropout_active(self):
+        """training passes only: with autograd, or the no-autograd pass a differentiated one repeats (TrainEngine.feature_pass, which must
+        draw the training pass's subsets). Evaluation, generation and search keep every token."""
+        return self.patch_keep is not None and self.training and not ops._inference()
 
     def _ref_is_frozen(self, ref):
         """the reference's freezing rules on one of ITS parameter names"""
@@ -764,19 +810,31 @@ class VALOR(nn.Module):
         return out[:, :L].contiguous() if prompt is not None else out
 
     def forward_video_encoder(self, video_pixels):
-        """modeling.py:449-465 (clip) -> VisionTransformer.forward clip.py:259-274. Returns [b, F, 197, W]."""
+        """modeling.py:449-465 (clip) -> VisionTransformer.forward clip.py:259-274. Returns [b, F, 197, W] ([b, F, 1 + k, W] under patch dropout)."""
         if self.spec.video_encoder == "swin":
             return self.forward_video_encoder_swin(video_pixels)
         P, sp = self.P, self.spec
         b, n, c, h, w = video_pixels.shape
         imgs = self._dev(video_pixels.reshape(b * n, c, h, w).float())
+        pd = self._patch_dropout_active()
+        # patch dropout: 1 + k rows per frame; 'tube' draws one subset per clip (groups of n frames). The draw is part of the encoder
+        # function, so a captured graph replays it (fresh subsets through the device counter) and nothing enters as a graph input
+        tokens = 1 + self.patch_keep if pd else sp.vis_tokens
+        self._pd_group, self._pd_ran = (n if self.patch_dropout_mode == "tube" else 1), False
         if self._use_graphs() and not self.frozen_vision:      # (a frozen tower has no backward pass to capture)
             seg = self._graph_segs.get("vit")
             if seg is None:
                 from .. import graphs
                 seg = self._graph_segs["vit"] = graphs.GraphedSegment("vit", self._video_encoder_clip)
-            return seg(imgs).view(b, n, sp.vis_tokens, sp.vis_width)
-        return self._video_encoder_clip(imgs).view(b, n, sp.vis_tokens, sp.vis_width)
+            key, n_cap = (b * n, self.patch_keep, self._pd_group, ops.DropoutState.offset), len(seg.captured)
+            out = seg(imgs, key_extra=key[1:3] if pd else None)
+            if pd and len(seg.captured) > n_cap:
+                self._pd_tables[key] = self.last_patch_keep     # this call captured: the tables live in the graph's static memory ...
+            elif pd and not self._pd_ran:
+                self.last_patch_keep = self._pd_tables[key]     # ... where every replay (which does not run the function) rewrites them
+        else:
+            out = self._video_encoder_clip(imgs)
+        return out.view(b, n, tokens, sp.vis_width)
 
     def _use_graphs(self):
         """hipGraph replay of the encoders (valor_amd/graphs.py): training steps only, on a GPU, once enable_graphs() was called"""
@@ -793,6 +851,7 @@ class VALOR(nn.Module):
             for seg in self._graph_segs.values():
                 seg.release()
             self._graph_segs = {}
+            self._pd_tables = {}
             from .. import graphs
             graphs.release_all()
             ops.DropoutState.disable_device_base()        # back to host mode: by-value windows only, nothing left set for a later model / device
@@ -806,12 +865,20 @@ class VALOR(nn.Module):
         kp = (wconv.shape[1] + vec - 1) // vec * vec
         # ViT-L/14: 3 * 14 * 14 = 588 contraction elements per patch; the GEMM stages 16-byte chunks, so operand rows are
         # zero-padded to the next chunk (592). Pure data movement; the weight's gradient flows back through the column slice.
-        patches = ops.patchify(imgs, sp.patch, self.dtype, pad_to=kp)
+        Pn = sp.vis_tokens - 1
+        keep = None
+        if self._patch_dropout_active():
+            keep = self.last_patch_keep = ops.patch_keep(bn, Pn, self.patch_keep, self._pd_group if bn % self._pd_group == 0 else 1, imgs.device)
+            self._pd_ran = True
+        patches = ops.patchify(imgs, sp.patch, self.dtype, pad_to=kp, keep=None if keep is None else keep[0])
         if kp != wconv.shape[1]:
             wconv = ops.pad_cols(wconv, kp)
         tok = ops.linear(patches, wconv, None)
-        Pn = sp.vis_tokens - 1
-        x = ops.assemble_tokens(tok, P["clip_model.visual.class_embedding"], P["clip_model.visual.positional_embedding"], None, bn, Pn)
+        if keep is not None:
+            x = ops.assemble_tokens_kept(tok, P["clip_model.visual.class_embedding"], P["clip_model.visual.positional_embedding"], None,
+                                         keep[0], keep[1], bn, Pn)
+        else:
+            x = ops.assemble_tokens(tok, P["clip_model.visual.class_embedding"], P["clip_model.visual.positional_embedding"], None, bn, Pn)
         x = ops.layer_norm(x, P["clip_model.visual.ln_pre.weight"], P["clip_model.visual.ln_pre.bias"], 1e-5)
         return self._clip_blocks(x, "clip_model.visual.transformer", sp.vis_layers, sp.vis_heads, None,
                                  P["clip_model.visual.ln_post.weight"], P["clip_model.visual.ln_post.bias"])
@@ -1760,7 +1827,7 @@ class VALOR(nn.Module):
                 if sp.video_encoder == "swin":                     # token mean, then frame mean = the mean over all F * X rows
                     pooled = ops.group_mean(video_output.reshape(-1, sp.video_dim), F * video_output.shape[2])
                 else:
-                    vo, cls_v = ops.tap_rows(video_output.reshape(-1, sp.vis_width), self._const_idx(b * F, sp.vis_tokens))
+                    vo, cls_v = ops.tap_rows(video_output.reshape(-1, sp.vis_width), self._const_idx(b * F, video_output.shape[2]))
                     video_output = vo.view(video_output.shape)          # what the decoder inputs read below (ops.TapRowsFn)
                     pooled = ops.group_mean(cls_v, F)
                 if sp.clip_heads:
@@ -1799,7 +1866,7 @@ class VALOR(nn.Module):
                 feat_v = ops.l2_normalize(ops.linear(pooled, P["contra_head_v.linear.weight"], None)).view(b, F, -1)
             elif "v" in "".join(contra_task):
                 b, F = video_output.shape[:2]
-                idx = self._const_idx(b * F, sp.vis_tokens)
+                idx = self._const_idx(b * F, video_output.shape[2])
                 vo, cls_v = ops.tap_rows(video_output.reshape(-1, sp.vis_width), idx)
                 video_output = vo.view(video_output.shape)              # what the decoder inputs read below (ops.TapRowsFn)
                 if sp.clip_heads:                                  # pretrain.py:89-92

@@ -145,6 +145,13 @@ class DropoutState:
         cls.offset += int(n_elements) + 1
         return cls.seed, off
 
+    @classmethod
+    def draw_counters(cls, n):
+        """window of exactly n Philox counters, one whole draw each (patch_keep: a 64-bit key per counter)"""
+        off = cls.offset
+        cls.offset += int(n)
+        return cls.seed, off
+
 
 def _2d(x):
     return x.reshape(-1, x.shape[-1])
@@ -1150,6 +1157,65 @@ def assemble_tokens(patches, cls, pos, bias, N, Pn):
     return AssembleFn.apply(patches, cls, pos, bias, N, Pn)
 
 
+class AssembleKeptFn(Function):
+    """AssembleFn on the kept patches of every frame (video patch dropout, csrc/patchdrop.hip): patches [N * k, E] are the rows of the
+    positions idx [N, k] -> tokens [N, 1 + k, E], each patch under ITS positional row. slot [N, Pn] is idx's inverse (patch_keep leaves
+    both): the backward sums a position's gradient over the frames that kept it. Gradient sinks as in AssembleFn."""
+
+    @staticmethod
+    def forward(ctx, patches, cls, pos, bias, idx, slot, N, Pn):
+        E = patches.shape[-1]
+        k = idx.shape[1]
+        if tuple(idx.shape) != (N, k) or tuple(slot.shape) != (N, Pn) or idx.dtype != torch.int32 or slot.dtype != torch.int32 \
+                or patches.shape[0] != N * k or pos.numel() != (Pn + 1) * E:
+            raise ValueError(f"assemble_tokens_kept: idx {tuple(idx.shape)} {idx.dtype} / slot {tuple(slot.shape)} {slot.dtype} / patches "
+                             f"{tuple(patches.shape)} / pos {tuple(pos.shape)} do not describe N = {N} frames of k of Pn = {Pn} patches")
+        idx, slot = idx.contiguous(), slot.contiguous()
+        out = torch.empty((N, k + 1, E), dtype=patches.dtype, device=patches.device)
+        lib.call("valor_assemble_tokens_kept_fwd", _st(), _dt(patches), _p(patches), _p(cls), _p(pos), _p(bias), _p(idx), _p(out), N, Pn, k, E)
+        ctx.cfg = (N, Pn, k, E, cls.shape, pos.shape)
+        ctx.params = (cls, pos, bias)
+        ctx.slot = slot
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        N, Pn, k, E, cshape, pshape = ctx.cfg
+        pc, pp, pb = ctx.params
+        dout = dout.contiguous()
+        dpatch = torch.empty((N * k, E), dtype=dout.dtype, device=dout.device)
+        sc, sp = _sink(pc), _sink(pp)
+        dcls = dposr = None
+        if sc is not None and sp is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
+            lib.call("valor_assemble_tokens_kept_bwd", _st(), _dt(dout), _p(dout), _p(ctx.slot), _p(dpatch), _p(sp), _p(sc), N, Pn, k, E, 1)
+            _sunk(pc); _sunk(pp)
+        else:
+            dpos = torch.empty((Pn + 1, E), dtype=dout.dtype, device=dout.device)
+            lib.call("valor_assemble_tokens_kept_bwd", _st(), _dt(dout), _p(dout), _p(ctx.slot), _p(dpatch), _p(dpos), None, N, Pn, k, E, 0)
+            dcls, dposr = dpos[0].clone().view(cshape), dpos.view(pshape)
+        return dpatch, dcls, dposr, _colsum_grad(dpatch, pb, ctx.needs_input_grad[3]), None, None, None, None
+
+
+def assemble_tokens_kept(patches, cls, pos, bias, idx, slot, N, Pn):
+    return AssembleKeptFn.apply(patches, cls, pos, bias, idx, slot, N, Pn)
+
+
+def patch_keep(N, Pn, k, group=1, device=None):
+    """Video patch dropout's subset draw (valor_patch_keep): every group of `group` consecutive frames keeps the k of its Pn patches with
+    the smallest Philox keys -> (idx [N, k] int32, the kept positions ascending; slot [N, Pn] int32, its inverse, -1 = dropped). The draw
+    takes (N / group) * Pn counters of the step's DropoutState window and adds the device-resident base when it RUNS, so a captured
+    graph replays it with fresh subsets and rewind() / exact resume reproduce it."""
+    N, Pn, k, group = int(N), int(Pn), int(k), int(group)
+    if N <= 0 or not 1 <= k <= Pn or group < 1 or N % group:
+        raise ValueError(f"patch_keep: N = {N} frames in groups of {group}, k = {k} of Pn = {Pn} patches")
+    device = torch.device("cuda") if device is None else device
+    idx = torch.empty((N, k), dtype=torch.int32, device=device)
+    slot = torch.empty((N, Pn), dtype=torch.int32, device=device)
+    seed, off = DropoutState.draw_counters((N // group) * Pn)
+    lib.call("valor_patch_keep", _st(), N, Pn, k, group, int(seed), int(off), K.RNG_BASE, _p(idx), _p(slot))
+    return idx, slot
+
+
 class PadColsFn(Function):
     """w [N, K] -> zero-padded [N, Kp] copy (data movement only); backward hands the first K gradient columns back."""
 
@@ -1169,13 +1235,22 @@ def pad_cols(w, kp):
     return PadColsFn.apply(w, kp)
 
 
-def patchify(images_f32, P, out_dtype, pad_to=0):
+def patchify(images_f32, P, out_dtype, pad_to=0, keep=None):
     """[N,C,H,W] fp32 -> [N*(H/P)*(W/P), C*P*P] GEMM operand rows in the compute dtype (no grad). pad_to > C*P*P: rows of pad_to
-    columns, zero beyond C*P*P (ViT-L/14: 588 -> 592, whole 16-byte chunks for the GEMM's staging)."""
+    columns, zero beyond C*P*P (ViT-L/14: 588 -> 592, whole 16-byte chunks for the GEMM's staging). keep: idx [N, k] int32 of
+    patch_keep -> the N * k rows of the kept patches only (row f * k + j = patch keep[f, j] of image f)."""
     N, C, H, W = images_f32.shape
     images_f32 = images_f32.contiguous()
     K = C * P * P
     rows = N * (H // P) * (W // P)
+    if keep is not None:
+        if keep.dtype != torch.int32 or keep.dim() != 2 or keep.shape[0] != N or not 1 <= keep.shape[1] <= rows // N:
+            raise ValueError(f"patchify: keep {tuple(keep.shape)} {keep.dtype} is no int32 [N = {N}, k <= {rows // N}] table")
+        keep = keep.contiguous()
+        k = keep.shape[1]
+        out = (torch.zeros if pad_to > K else torch.empty)((N * k, max(pad_to, K)), dtype=out_dtype, device=images_f32.device)
+        lib.call("valor_patchify_kept", _st(), _dt(out), _p(images_f32), _p(keep), _p(out), N, C, H, W, P, k, out.shape[1])
+        return out
     if pad_to > K:
         out = torch.zeros((rows, pad_to), dtype=out_dtype, device=images_f32.device)
     else:
